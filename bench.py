@@ -28,15 +28,20 @@ How N ranks come to exist (`--gpus N`, N > 1):
     ncclCommInitAll (smk_comm_init_all) -- no torch.distributed, no rendezvous.
 torch.distributed (gloo, CPU) is used only to broadcast the RCCL unique id and for the timing barrier.
 
-The K timed steps are one window; the window is repeated (5 times, and until >= 0.5 s have been timed) and
-the MEDIAN window is reported, so `value`, `ms_per_step` are per K steps as the contract asks while short
-windows no longer decide the number (`windows_ms` lists them all).
+The K timed steps are one window, and `value`, `ms_per_step` are taken from it: a plain run times exactly K steps.
+`--dump-outputs DIR` then writes the factors that window's last step left, W.npy and H.npy (fp64; a seeded sample
+of rows of W / columns of H where the whole factor would exceed the size limit), for comparing two builds output
+for output: the inputs are generated from fixed seeds.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run does only that.  `--full` adds what takes time beyond the headline: more windows of K steps (5, and
+until >= 0.5 s have been timed; `windows_ms` lists them all, the first one is the headline's), the CPU baseline,
+the 8-GPU projection of the C4 line and `--api-path`.
+
+Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
   roofline     -- the dominant kernel (bigprod_kernel, both passes): algorithmic bytes per launch
                   (m * n_local * sizeof(A element)) / its average launch duration, measured live
                   with HIP events on the solver's stream, against the 8 TB/s HBM peak.
-  cpu_baseline -- the CPU oracle (a port, not the reference binary) on a bounded sample of the
+  cpu_baseline -- --full: the CPU oracle (a port, not the reference binary) on a bounded sample of the
                   same workload, timed on this host's cores; N = 1 only.
 """
 import argparse
@@ -75,7 +80,7 @@ HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_PEAK_TF = {"bf16": 2500.0, "f32": 157.3}
 
 from bench_launch import (_hb, beat, lim, launch, rccl_choices, rccl_env_defaults, rccl_log_excerpt, start_rank_watchdog,
-                          StdoutGuard)
+                          StdoutGuard, DUMP_BYTES_PER_ARRAY, write_outputs)
 
 
 def cpu_baseline(m, n, k, alg, quant, budget_s=20.0, data="uniform"):
@@ -213,7 +218,18 @@ def parse_args(argv=None):
                          "geometry and the row blocks of that world, every collective issued through RCCL with ONE rank "
                          "(device-local).  Times the per-rank work of an N-GPU run without the xGMI transfers; the factors "
                          "it produces are meaningless (the other ranks' blocks never arrive)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline window: repeated windows, the CPU baseline (unless --no-cpu-baseline), the 8-GPU "
+                         "projection of the C4 line, --api-path")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="one GPU: after the timed steps write W.npy and H.npy (fp64, what smk_solver_get_factors returns) to DIR; "
+                         f"factors over {DUMP_BYTES_PER_ARRAY // 10**6} MB are cut to a seeded sample of rows of W / columns of H")
+    args = ap.parse_args(argv)
+    if args.api_path and not args.full:
+        ap.error("--api-path is a --full measurement")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs is a one-GPU option")
+    return args
 
 
 # ---- report ---------------------------------------------------------------------------------------------------------
@@ -256,6 +272,7 @@ def build_report(args, world, elapsed, windows, rank0, ranks_report, collectives
         "exposed_comm_ms_per_step_rank0": ranks_report[0].get("exposed_comm_ms") if sharded else None,
         "per_rank": ranks_report if sharded else None,
         "windows": len(windows), "windows_ms": [round(w * 1e3, 4) for w in windows],
+        "windows_median_ms_per_step": sorted(windows)[len(windows) // 2] / args.steps * 1e3,
         "timed_region_s": sum(windows),
         "roofline": {
             "bound": "hbm",
@@ -556,18 +573,18 @@ def run_rank(args):
     test_hook = bool(os.environ.get("SMK_BENCH_DUMP_W"))          # the 2-process test compares W after exactly K steps
     beat("window 0", limit=lim(args, 120.0))
     windows = [window()]
+    elapsed = windows[0]
+    if test_hook or args.dump_outputs:
+        Wd, Hd = solver.factors(normalize=False)     # every rank takes part in the gather of W
+        if test_hook and rank == 0:                  # test hook: W (replicated) after the timed steps, rank 0
+            np.save(os.environ["SMK_BENCH_DUMP_W"], Wd)
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, Wd, Hd)
     wlimit = max(args.stall_s, 30.0 * windows[0])
-    while not test_hook and (len(windows) < 5 or sum(windows) < 0.5) and len(windows) < 200:
+    while args.full and not test_hook and (len(windows) < 5 or sum(windows) < 0.5) and len(windows) < 200:
         beat(f"window {len(windows)}", limit=wlimit)
         windows.append(window())
-    elapsed = sorted(windows)[len(windows) // 2]
     beat("report", limit=lim(args, 400.0))
-
-    dump = os.environ.get("SMK_BENCH_DUMP_W")        # test hook: W (replicated) after the timed steps, rank 0
-    if dump:
-        Wd, _ = solver.factors(normalize=False)
-        if rank == 0:
-            np.save(dump, Wd)
 
     ms0, c0 = solver.kernel_time(0)
     ms1, c1 = solver.kernel_time(1)
@@ -593,9 +610,9 @@ def run_rank(args):
             out["rccl_choices"] = rccl_choices()
         if args.check_every_iteration:
             out["config"]["check_route"] = solver.kernel_name(2)        # where the last check's sums were formed
-        if args.workload == "c4" and args.data == "uniform" and not args.single_copy and not args.check_every_iteration:
+        if args.full and args.workload == "c4" and args.data == "uniform" and not args.single_copy and not args.check_every_iteration:
             out["projection"] = projection_8gpu(m, n, k, alg, out["ms_per_step"] if world == 1 and args.emulate_world <= 1 else None)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(m, n, k, alg, 1 if storage == "bf16" else 0, data=args.data)
         if args.api_path and world == 1 and args.emulate_world <= 1:
             solver.close()
@@ -695,7 +712,7 @@ def run_single_process(args):
                 wait()
                 if r == 0:
                     windows.append(max(shared["dts"]))
-                    shared["go_on"] = not test_hook and (len(windows) < 5 or sum(windows) < 0.5) and len(windows) < 200
+                    shared["go_on"] = args.full and not test_hook and (len(windows) < 5 or sum(windows) < 0.5) and len(windows) < 200
                 wait()
                 if not shared["go_on"]:
                     break
@@ -738,7 +755,7 @@ def run_single_process(args):
         beat("done")
         return 1
     beat("report", limit=lim(args, 60.0))
-    elapsed = sorted(windows)[len(windows) // 2]
+    elapsed = windows[0]
     if test_hook and shared["W"] is not None:
         np.save(os.environ["SMK_BENCH_DUMP_W"], shared["W"])
     out = build_report(args, N, elapsed, windows, shared["rank0"], shared["reports"], collectives,

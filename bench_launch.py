@@ -6,7 +6,8 @@
     child process group, relays rank 0's single JSON line and falls back to `--single-process` (one process, a thread per device);
   * RCCL's own log: the excerpt printed after a run (rings / trees / transport) and, under SMK_BENCH_RCCL_TUNING=1, its per-size
     algorithm / protocol choices for the JSON line (`rccl_choices`);
-  * `StdoutGuard`: stdout carries only the JSON line (RCCL prints banners there).
+  * `StdoutGuard`: stdout carries only the JSON line (RCCL prints banners there);
+  * `write_outputs`: the factors of `--dump-outputs`.
 Tests: tests/test_bench_launcher.py (CPU), tests/test_gpu_dist.py."""
 import json
 import os
@@ -15,6 +16,26 @@ import threading
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
+DUMP_BYTES_PER_ARRAY = 30 * 10**6           # W.npy + H.npy stay under 64 MB
+
+
+def write_outputs(directory, W, H):
+    """W (m x k) and H (k x n) as DIR/W.npy and DIR/H.npy in fp64.  A factor larger than DUMP_BYTES_PER_ARRAY is cut to a
+    sample of rows of W / columns of H drawn with a fixed seed from its shape alone, so that two runs with the same
+    arguments write the same entries."""
+    import numpy as np
+
+    def sample(X, axis):
+        X = np.asarray(X, dtype=np.float64)
+        keep = DUMP_BYTES_PER_ARRAY // (X.nbytes // X.shape[axis])
+        if X.shape[axis] <= keep:
+            return X
+        idx = np.sort(np.random.default_rng(X.shape[axis]).choice(X.shape[axis], size=keep, replace=False))
+        return np.take(X, idx, axis=axis)
+
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "W.npy"), sample(W, 0))
+    np.save(os.path.join(directory, "H.npy"), sample(H, 1))
 
 def lim(args, floor):
     """stage limit: long stages (matrix fill, solver set-up, the first collectives, the CPU baseline) get `floor` seconds
@@ -221,6 +242,8 @@ def launch(args):
               "--data", args.data, "--stall-s", str(args.stall_s)] + (["--single-copy"] if args.single_copy else [])
     if args.no_cpu_baseline:
         common.append("--no-cpu-baseline")
+    if args.full:
+        common.append("--full")
     me = os.path.join(ROOT, "bench.py")
     plans = []
     if not args.single_process:

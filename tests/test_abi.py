@@ -73,7 +73,9 @@ def test_host_generator_equals_oracle():
 
 def test_csv_roundtrip_and_reference_bytes(tmp_path):
     """w.csv/h.csv writer and init-file reader: byte-compare with the reference's own
-    WriteDelimitedFile / LoadDelimitedFile (oracle/_ref, compiled from /root/reference)."""
+    WriteDelimitedFile / LoadDelimitedFile (oracle/_ref; their answers: tests/golden/ref_csv_results.npz)."""
+    from ref_results import RefResults
+    results = RefResults("csv", "libref_csv.so")
     import smallk_amd
     L = smallk_amd._lib.lib()
     rng = np.random.default_rng(0)
@@ -86,16 +88,18 @@ def test_csv_roundtrip_and_reference_bytes(tmp_path):
         assert L.smk_load_csv(str(mine).encode(), out.ctypes.data_as(C.POINTER(C.c_double)), 35, C.byref(h), C.byref(w)) == 1
         assert (h.value, w.value) == (7, 5)
         assert np.allclose(out, M, rtol=10.0 ** (-prec + 1) if prec < 17 else 1e-15)
-        ref_so = os.path.join(ROOT, "oracle", "_ref", "libref_csv.so")
-        if os.path.exists(ref_so):
-            ref = C.CDLL(ref_so)
+        text = mine.read_bytes()
+
+        def live(ref):
             theirs = tmp_path / "theirs.csv"
-            assert ref.ref_write_csv(M.ctypes.data_as(C.POINTER(C.c_double)), 7, 7, 5, str(theirs).encode(), prec) == 1
-            assert mine.read_bytes() == theirs.read_bytes()
+            rc_w = ref.ref_write_csv(M.ctypes.data_as(C.POINTER(C.c_double)), 7, 7, 5, str(theirs).encode(), prec)
             out2 = np.zeros((7, 5), order="F")
-            assert ref.ref_load_csv(str(mine).encode(), out2.ctypes.data_as(C.POINTER(C.c_double)), C.c_ulong(35),
-                                    C.byref(h), C.byref(w)) == 1
-            assert np.array_equal(out, out2)
+            rc_l = ref.ref_load_csv(str(mine).encode(), out2.ctypes.data_as(C.POINTER(C.c_double)), C.c_ulong(35),
+                                    C.byref(h), C.byref(w))
+            return rc_w, theirs.read_text(), rc_l, out2
+        rc_w, theirs, rc_l, out2 = results.get("csv", (M, prec, text.decode()), live)
+        assert rc_w == 1 and text == str(theirs).encode()
+        assert rc_l == 1 and np.array_equal(out, out2)
     # leading comment / blank lines are skipped (delimited_file.cpp:35-70)
     f = tmp_path / "c.csv"
     f.write_text("# comment\n\n% another\n1,2\n3,4\n")

@@ -1,6 +1,7 @@
 """CPU tests for flat clustering: the host post-processing of the product (assignments, fuzzy
 assignments, top terms, result files -- no GPU needed) against the oracle restatement and against
-the reference's own code compiled into oracle/_ref/libref_flat.so; the oracle's NnlsHals."""
+the reference's own code compiled into oracle/_ref/libref_flat.so (its answers: tests/golden/ref_flat_results.npz,
+tests/ref_results.py); the oracle's NnlsHals."""
 import ctypes as C
 import os
 
@@ -8,9 +9,10 @@ import numpy as np
 import pytest
 
 from hier_cases import planted
+from ref_results import RefResults
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_flat.so")
+RESULTS = RefResults("flat", "libref_flat.so")
 _up, _fp, _dp = C.POINTER(C.c_uint), C.POINTER(C.c_float), C.POINTER(C.c_double)
 
 
@@ -32,13 +34,14 @@ def test_assignments_and_fuzzy(ties):
         a, p = pf.compute_assignments(H), pf.compute_fuzzy_assignments(H)
         assert np.array_equal(a, of.compute_assignments(H))
         assert np.array_equal(p, of.compute_fuzzy_assignments(H))          # float32, bit for bit
-        if os.path.exists(REF_SO):
-            ref = C.CDLL(REF_SO)
+        def live(ref):
             ra = np.zeros(n, dtype=np.uint32)
             rp = np.zeros((k, n), dtype=np.float32, order="F")
             ref.ref_compute_assignments(H.ctypes.data_as(_dp), k, k, n, ra.ctypes.data_as(_up))
             ref.ref_compute_fuzzy(H.ctypes.data_as(_dp), k, k, n, rp.ctypes.data_as(_fp))
-            assert np.array_equal(a, ra) and np.array_equal(p, rp)
+            return ra, rp
+        ra, rp = RESULTS.get("assignments", (H,), live)
+        assert np.array_equal(a, ra) and np.array_equal(p, rp)
     # k > n is rejected (logic_error in the reference, assignments.hpp:79-80)
     from smallk_amd import _lib as L
     H = _H(rng, 4, 3)
@@ -63,8 +66,7 @@ def test_top_terms():
     assert L.lib().smk_top_terms(2, Wt.ctypes.data_as(_dp), 3, 3, 5, out.ctypes.data_as(C.POINTER(C.c_int))) == L.BAD_PARAM
 
 
-def _ref_write(tmp, labels, P, terms, dictionary, fmt, maxterms, n, k):
-    ref = C.CDLL(REF_SO)
+def _ref_write(ref, tmp, labels, P, terms, dictionary, fmt, maxterms, n, k):
     a = np.ascontiguousarray(labels, dtype=np.uint32)
     p = np.ascontiguousarray(np.asarray(P).T, dtype=np.float32).ravel()
     t = np.ascontiguousarray(terms, dtype=np.int32)
@@ -96,8 +98,9 @@ def test_result_files_match_reference_bytes(tmp_path, fmt, empty_cluster):
     labels, P, terms = of.compute_assignments(H), of.compute_fuzzy_assignments(H), of.top_terms(W, mt)
     want = [of.assignments_text(labels), of.fuzzy_text(P), of.results_text(labels, terms, dictionary, fmt, mt, n, k)]
     assert got == want
-    if os.path.exists(REF_SO):
-        assert got == _ref_write(tmp_path, labels, P, terms, dictionary, fmt, mt, n, k)
+    ref_files = RESULTS.get("write_results", (labels, P, terms, repr(dictionary), fmt, mt, n, k),
+                            lambda ref: _ref_write(ref, tmp_path, labels, P, terms, dictionary, fmt, mt, n, k))
+    assert got == [str(x) for x in ref_files]
     # directory form: the reference's file names
     assert res.write_to_dir(str(tmp_path), dictionary, fmt)
     ext = "json" if fmt == "JSON" else "xml"

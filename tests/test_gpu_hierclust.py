@@ -111,7 +111,7 @@ def test_tree_files(gpu, tmp_path, fmt):
     assert open(pa).read() == otree.assignments_text()
     if os.path.exists(REF_SO):
         from test_hierclust import _ref_write
-        assert text == _ref_write(otree, dictionary, fmt, str(tmp_path / "ref.out"))
+        assert text == _ref_write(C.CDLL(REF_SO), otree, dictionary, fmt, str(tmp_path / "ref.out"))
     # a dictionary shorter than the term count is refused
     assert not res.write(p, dictionary[:3], fmt)
 

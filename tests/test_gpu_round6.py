@@ -228,7 +228,7 @@ print("RESULT", " ".join(out))
     assert seen[0] == seen[1], seen
 
 
-@pytest.mark.parametrize("flags", [["--check-every-iteration"], ["--api-path"]])
+@pytest.mark.parametrize("flags", [["--check-every-iteration"], ["--full", "--api-path"]])
 def test_bench_flags_of_round_6_run(flags):
     """bench.py --check-every-iteration / --api-path on the smallest workload (C1: 512 x 256, k = 8, MU): one JSON line with the
     contract's keys, the flag's own fields, and a rate that is a rate."""

@@ -1,6 +1,6 @@
 """CPU tests for HierNMF2: the oracle restatement (oracle/hierclust.py), the host-side pieces of the
 product that need no GPU (priority score, option validation), and the reference's own file
-writers / SetDiff compiled into oracle/_ref."""
+writers / SetDiff compiled into oracle/_ref (their answers: tests/golden/ref_hier_results.npz, tests/ref_results.py)."""
 import ctypes as C
 import os
 
@@ -8,9 +8,10 @@ import numpy as np
 import pytest
 
 from hier_cases import planted
+from ref_results import RefResults
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_hier.so")
+RESULTS = RefResults("hier", "libref_hier.so")
 
 
 def test_priority_product_matches_oracle():
@@ -41,22 +42,22 @@ def test_priority_known_cases():
 
 def test_setdiff_matches_reference():
     from oracle import hierclust as oh
-    if not os.path.exists(REF_SO):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    ref = C.CDLL(REF_SO)
     rng = np.random.default_rng(1)
     for _ in range(50):
         a = np.unique(rng.integers(0, 200, size=60)).astype(np.uint32)
         b = rng.choice(a, size=int(rng.integers(0, len(a))), replace=False)
         b = np.sort(b).astype(np.uint32)
-        out = np.zeros(len(a), dtype=np.uint32)
-        cnt = ref.ref_setdiff(a.ctypes.data_as(C.POINTER(C.c_uint)), len(a), b.ctypes.data_as(C.POINTER(C.c_uint)),
-                              len(b), out.ctypes.data_as(C.POINTER(C.c_uint)))
-        assert oh.set_diff(list(a), list(b)) == list(out[:cnt])
+
+        def live(ref):
+            out = np.zeros(len(a), dtype=np.uint32)
+            cnt = ref.ref_setdiff(a.ctypes.data_as(C.POINTER(C.c_uint)), len(a), b.ctypes.data_as(C.POINTER(C.c_uint)),
+                                  len(b), out.ctypes.data_as(C.POINTER(C.c_uint)))
+            return (out[:cnt],)
+        out, = RESULTS.get("setdiff", (a, b), live)
+        assert oh.set_diff(list(a), list(b)) == list(out)
 
 
-def _ref_write(tree, dictionary, fmt, path):
-    ref = C.CDLL(REF_SO)
+def _ref_write(ref, tree, dictionary, fmt, path):
     nodes = tree.nodes
     u = lambda xs: (C.c_uint * len(xs))(*xs)
     i = lambda xs: (C.c_int * len(xs))(*xs)
@@ -77,14 +78,14 @@ def _ref_write(tree, dictionary, fmt, path):
 def test_oracle_tree_text_matches_reference_writers(tmp_path, fmt):
     """oracle.tree_text == bytes produced by the reference's hierclust_{json,xml}_writer.cpp."""
     from oracle import hierclust as oh
-    if not os.path.exists(REF_SO):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
     A, _ = planted(60, 90, 3, 5)
     for clusters in (3, 6):                       # 6: the search stops early, unused nodes are written too
         tree, _ = oh.hier_nmf2(A, clusters, seed=11)
         dictionary = [f"term{i}" for i in range(A.shape[0])]
-        ref_text = _ref_write(tree, dictionary, fmt, str(tmp_path / f"ref_{clusters}.{fmt.lower()}"))
-        assert oh.tree_text(tree, dictionary, fmt) == ref_text
+        nodes = [(nd.parent, int(nd.is_left_child), nd.left, nd.right, len(nd.docs), list(nd.term_indices)) for nd in tree.nodes]
+        ref_text, = RESULTS.get("write_tree", (fmt, tree.leaf_doc_count, repr(nodes), repr(dictionary)),
+                                lambda ref: (_ref_write(ref, tree, dictionary, fmt, str(tmp_path / f"ref_{clusters}.{fmt.lower()}")),))
+        assert oh.tree_text(tree, dictionary, fmt) == str(ref_text)
 
 
 @pytest.mark.parametrize("sparse", [False, True])

@@ -40,8 +40,8 @@ def test_gather_ceiling_lookup(tmp_path, monkeypatch):
 
 def test_bench_flags_of_round_6():
     import bench
-    a = bench.parse_args(["--check-every-iteration", "--api-path", "--workload", "c2"])
-    assert a.check_every_iteration and a.api_path and a.workload == "c2"
+    a = bench.parse_args(["--check-every-iteration", "--full", "--api-path", "--workload", "c2"])
+    assert a.check_every_iteration and a.full and a.api_path and a.workload == "c2"
     a = bench.parse_args([])
     assert not a.check_every_iteration and not a.api_path and a.workload == "c4" and a.gpus == 1
     for w in ("c4s2", "c3s2"):                       # two ranks of these = the per-rank shard of the 8-GPU run

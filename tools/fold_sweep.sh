@@ -17,7 +17,7 @@ fi
 if [ "$1" = bench ]; then
   for v in 125 128 108 125 128 129; do
     echo "SMK_BP_VARIANT=$v" >> $O/r04_fold_interval_c4_bench.txt
-    SMK_BP_VARIANT=$v timeout 900 python3 bench.py --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | tail -1 >> $O/r04_fold_interval_c4_bench.txt
+    SMK_BP_VARIANT=$v timeout 900 python3 bench.py --full --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | tail -1 >> $O/r04_fold_interval_c4_bench.txt
   done
   cat $O/r04_fold_interval_c4_bench.txt
 fi

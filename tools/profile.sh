@@ -30,12 +30,12 @@ pmc() {  # name, counters, command...
   [ -n "$DB" ] && cp "$DB" $OUT/pmc_$name.db
   rm -rf $OUT/pmc_$name
 }
-B="python3 $ROOT/bench.py --no-cpu-baseline"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline"
 cd $ROOT
 # ---- bench lines (un-profiled) ----
-python3 $ROOT/bench.py 2> $OUT/bench_c4.err | tail -1 > $OUT/${TAG}_bench_c4.json
-python3 $ROOT/bench.py --workload c3 --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c3.json
-python3 $ROOT/bench.py --workload c2 --steps 200 --warmup 20 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c2.json
+python3 $ROOT/bench.py --full 2> $OUT/bench_c4.err | tail -1 > $OUT/${TAG}_bench_c4.json
+python3 $ROOT/bench.py --full --workload c3 --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c3.json
+python3 $ROOT/bench.py --full --workload c2 --steps 200 --warmup 20 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c2.json
 $B --workload c4s --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c4s.json
 for n in 2 4 8; do $B --emulate-world $n 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c4_emulate$n.json; done
 # ---- kernel tables ----
@@ -50,7 +50,7 @@ kt rank2_iteration_1M python3 $ROOT/tools/r2_iter.py 1000000 16 30
 kt wide_bpp_k192 python3 $ROOT/tools/wide_run.py 16384 8192 192 BPP 12 1
 kt wide_bpp_k512 python3 $ROOT/tools/wide_run.py 16384 8192 512 BPP 12 1
 for k in 100 160 192 256 384 512; do (cd $ROOT && for alg in BPP MU HALS; do python3 tools/wide_run.py 16384 8192 $k $alg 12 1 2>/dev/null | tail -1; done) >> $OUT/${TAG}_wide_rank_times.txt; done
-(cd $ROOT && SMK_NSPLIT=8 python3 bench.py --workload c4s --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1) > $OUT/${TAG}_bench_c4s_accurate_form.json
+(cd $ROOT && SMK_NSPLIT=8 python3 bench.py --full --workload c4s --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1) > $OUT/${TAG}_bench_c4s_accurate_form.json
 fi
 # ---- HBM traffic of the streaming kernels (separate passes) ----
 pmc c4_fetch FETCH_SIZE $B --workload c4 --steps 3 --warmup 1

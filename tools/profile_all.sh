@@ -15,7 +15,7 @@ TAG=${2:-r06}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline"
 kt() {   # name, command...
   local name=$1; shift
   timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/kt_$name -o x -- "$@" > $OUT/${name}_run.log 2>&1
@@ -65,19 +65,19 @@ evidence)
   ;;
 bench)
   cd $ROOT
-  python3 bench.py 2> $OUT/bench_c4.err | tail -1 > $OUT/${TAG}_bench_c4.json
-  python3 bench.py --workload c3 --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c3.json
-  python3 bench.py --workload c2 --steps 200 --warmup 20 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c2.json
+  python3 bench.py --full 2> $OUT/bench_c4.err | tail -1 > $OUT/${TAG}_bench_c4.json
+  python3 bench.py --full --workload c3 --steps 20 --warmup 3 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c3.json
+  python3 bench.py --full --workload c2 --steps 200 --warmup 20 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c2.json
   for w in s_reuters s_reuters_hals s_1m; do
     case $w in s_1m) steps="--steps 20 --warmup 3";; *) steps="--steps 200 --warmup 20";; esac
-    python3 bench.py --workload $w $steps 2>/dev/null | tail -1 > $OUT/${TAG}_bench_$w.json
+    python3 bench.py --full --workload $w $steps 2>/dev/null | tail -1 > $OUT/${TAG}_bench_$w.json
   done
   $B --workload c4 --check-every-iteration 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c4_checked.json
   $B --workload c3 --steps 20 --warmup 3 --check-every-iteration 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c3_checked.json
   $B --workload c2 --steps 200 --warmup 20 --check-every-iteration 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c2_checked.json
   $B --workload s_reuters --steps 200 --warmup 20 --check-every-iteration 2>/dev/null | tail -1 > $OUT/${TAG}_bench_s_reuters_checked.json
   for n in 2 4 8; do $B --emulate-world $n 2>/dev/null | tail -1 > $OUT/${TAG}_bench_c4_emulate$n.json; done
-  for w in c2 c3 c4s; do python3 bench.py --no-cpu-baseline --api-path --workload $w 2>/dev/null | tail -1 > $OUT/${TAG}_bench_${w}_api_path.json; done
+  for w in c2 c3 c4s; do python3 bench.py --full --no-cpu-baseline --api-path --workload $w 2>/dev/null | tail -1 > $OUT/${TAG}_bench_${w}_api_path.json; done
   ;;
 tables)
   kt c4full_bpp_f32 $B --workload c4 --steps 5 --warmup 2
