@@ -428,6 +428,43 @@ int smk_api_hiernmf2_with_flat(unsigned num_clusters);  /* smallk::HierNmf2WithF
 int smk_api_load_dictionary_file(const char* path);     /* LoadDictionary(string), smallk.cpp:675-691 */
 int smk_api_load_dictionary(const char* const* terms, unsigned count);          /* smallk.cpp:694-707 */
 
+/* ---- preprocess_tf: term-document pruning and tf-idf (preprocessor/src/preprocess.cpp:81-232) ---------------------------
+ * Input: a term-count matrix in CSC, checked as smk_matrix_create_sparse checks it (row indices need not be sorted inside a
+ * column).  Counts: 1 in boolean mode, 0 for a negative value, else the value truncated toward zero.  The loop prunes rows
+ * (total count < docs_per_term, or an entry in every column), short columns (< terms_per_doc entries) and duplicate columns
+ * (the one with the largest index survives) until nothing changes or max_iter iterations have run (max_iter = 0 is
+ * accepted: scores of the input as it stands).  Returns SMK_OK, or SMK_FAILURE when every column was pruned; in both cases
+ * *out is a result (on failure it holds only the iteration log and the sizes at the failure).  Everything stays on the
+ * device until a download.  smk_preprocess returns with every pass finished; the accessors below run on the calling thread's
+ * current context stream, so a result may be read from another context than the one that made it. */
+typedef struct smk_preprocess_options {
+    unsigned max_iter, docs_per_term, terms_per_doc;
+    int boolean_mode;
+} smk_preprocess_options;
+typedef struct smk_preprocess_result smk_preprocess_result;
+int smk_preprocess(const smk_preprocess_options* opts, unsigned height, unsigned width, unsigned nnz, const unsigned* col_offsets,
+                   const unsigned* row_indices, const double* data, smk_preprocess_result** out);
+void smk_preprocess_result_destroy(smk_preprocess_result* r);
+int smk_preprocess_result_sizes(const smk_preprocess_result* r, unsigned* height, unsigned* width, unsigned* nnz,
+                                unsigned* iterations);
+/* the log line of each iteration ("[i] height: h, width: w, nonzeros: n"): 3 x iterations values h, w, n */
+int smk_preprocess_result_log(const smk_preprocess_result* r, unsigned* out);
+/* host wall times of smk_preprocess: the input upload (the host-to-device copies of offsets, rows and values; the working set
+ * is allocated before it), and the device phase from the uploaded input to the resident result */
+int smk_preprocess_result_timing(const smk_preprocess_result* r, double* upload_ms, double* device_ms);
+/* the reduced matrix and index sets; any pointer may be NULL.  term_indices: height, doc_indices: width, col_offsets:
+ * width + 1, row_indices and scores: nnz */
+int smk_preprocess_result_download(const smk_preprocess_result* r, unsigned* term_indices, unsigned* doc_indices,
+                                   unsigned* col_offsets, unsigned* row_indices, double* scores);
+/* the reduced tf-idf matrix as a resident sparse matrix (with its transpose), built on the device: the matrix
+ * smk_matrix_create_sparse builds from the downloaded arrays, for smk_clust_resident and the solver */
+int smk_preprocess_result_matrix(const smk_preprocess_result* r, smk_matrix** out);
+/* reduced_matrix.mtx (TermFrequencyMatrix::WriteMtxFile, term_frequency_matrix.cpp:286-320): the banner, "h w nnz", then
+ * "row col score" 1-based in column order, fixed notation with `precision` digits; formatted on as many threads as the process
+ * may run on (its CPU affinity, at most OMP_NUM_THREADS when set), about 2^22 lines in flight.
+ * SMK_OK, or SMK_FAILURE when the file cannot be written */
+int smk_preprocess_write_mtx(const smk_preprocess_result* r, const char* path, unsigned precision);
+
 #ifdef __cplusplus
 }
 #endif

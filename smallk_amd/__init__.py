@@ -19,7 +19,11 @@ __all__ = ["DenseMatrix", "SparseMatrix", "nmf_sparse", "load_matrix_market", "N
 
 def __getattr__(name):
     """``smallk_amd.Hierclust`` / ``smallk_amd.Flatclust`` / ``smallk_amd.pyclust`` (pysmallk's clustering classes,
-    pysmallk/interface/smallk_lib.pyx:924-1420), loaded on first use."""
+    pysmallk/interface/smallk_lib.pyx:924-1420) and ``smallk_amd.Preprocessor`` (:1643-1815), loaded on first use."""
+    if name in ("Preprocessor", "preprocess"):
+        import importlib
+        mod = importlib.import_module(".preprocess", __name__)
+        return mod if name == "preprocess" else mod.Preprocessor
     if name in ("Hierclust", "Flatclust", "pyclust"):
         import importlib
         mod = importlib.import_module(".pyclust", __name__)

@@ -47,6 +47,11 @@ class ClustStats(C.Structure):
     _fields_ = [("nmf_count", C.c_int), ("max_count", C.c_int)]
 
 
+class PreprocessOptions(C.Structure):
+    """struct smk_preprocess_options (preprocess_tf's max_iter, docs_per_term, terms_per_doc, boolean_mode)."""
+    _fields_ = [("max_iter", C.c_uint), ("docs_per_term", C.c_uint), ("terms_per_doc", C.c_uint), ("boolean_mode", C.c_int)]
+
+
 class TreeNodeInfo(C.Structure):
     """struct smk_tree_node: the scalar fields of TreeNode<T> (hierclust/include/tree.hpp:31-50)."""
     _fields_ = [("priority", C.c_double), ("parent", C.c_uint), ("left_child", C.c_uint), ("right_child", C.c_uint),
@@ -215,6 +220,18 @@ SYMBOLS = {
     "smk_flatclust_write_results": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint), C.c_uint,
                                               C.POINTER(C.c_float), C.POINTER(C.c_char_p), _i64, C.POINTER(C.c_int),
                                               _i64, C.c_int, C.c_uint, C.c_uint, C.c_uint]),
+    # preprocess_tf (preprocess.cpp; reference preprocessor/src/preprocess.cpp)
+    "smk_preprocess": (C.c_int, [C.POINTER(PreprocessOptions), C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint),
+                                 C.POINTER(C.c_uint), _dp, C.POINTER(_vp)]),
+    "smk_preprocess_result_destroy": (None, [_vp]),
+    "smk_preprocess_result_sizes": (C.c_int, [_vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint),
+                                              C.POINTER(C.c_uint)]),
+    "smk_preprocess_result_log": (C.c_int, [_vp, C.POINTER(C.c_uint)]),
+    "smk_preprocess_result_timing": (C.c_int, [_vp, _dp, _dp]),
+    "smk_preprocess_result_download": (C.c_int, [_vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint),
+                                                 C.POINTER(C.c_uint), _dp]),
+    "smk_preprocess_result_matrix": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "smk_preprocess_write_mtx": (C.c_int, [_vp, C.c_char_p, C.c_uint]),
 }
 
 _lib = None

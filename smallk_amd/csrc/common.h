@@ -4,8 +4,11 @@
 #include <mutex>
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <functional>
 #include <cstddef>
 #include <string>
+
+struct smk_matrix;
 
 namespace smk {
 
@@ -482,5 +485,11 @@ void device_priority_release();
 // Returns 0, or non-zero when the caller should take the host path.
 int device_csc_transpose(i64 height, i64 ncols, i64 nnz, const i64* colptr, const unsigned* rowidx, const double* val,
                          i64* colptr_t, unsigned* rowidx_t, double* val_t, hipStream_t st);
+
+// solver.cpp: the calling thread's context stream (initialized: whether smk_initialize has run); a resident sparse matrix
+// whose CSC `fill` writes on the device (on the stream it is given), transpose as smk_matrix_create_sparse builds it
+hipStream_t context_stream(bool* initialized);
+int matrix_create_sparse_device(::smk_matrix** out, i64 height, i64 width, i64 nnz,
+                                const std::function<int(i64* colptr, unsigned* rowidx, double* val, hipStream_t st)>& fill);
 
 }  // namespace smk

@@ -889,6 +889,54 @@ int smk_matrix_create_sparse(smk_matrix** out, int64_t height, int64_t width_glo
     return SMK_OK;
 }
 
+// preprocess.cpp: the resident matrix of a preprocessing result, filled on the device by `fill` (CSC with 64-bit offsets, on the
+// context stream) and its transpose built as smk_matrix_create_sparse builds it -- the same matrix as one created from the
+// downloaded arrays
+extern "C++" {
+namespace smk {
+int matrix_create_sparse_device(smk_matrix** out, i64 height, i64 width, i64 nnz,
+                                const std::function<int(i64* colptr, unsigned* rowidx, double* val, hipStream_t st)>& fill)
+{
+    if (!out) return SMK_BAD_PARAM;
+    *out = nullptr;
+    if (!g_init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (height <= 0 || width <= 0 || nnz < 0) { set_error("empty matrix"); return SMK_BAD_PARAM; }
+    smk_matrix* a = new smk_matrix;
+    a->m = height; a->n_global = width; a->c0 = 0; a->n = width; a->storage = SMK_STORE_F32;
+    a->sparse = true; a->nnz = nnz;
+    a->st = g_stream;
+    register_matrix(a);
+    int rc = 0;
+    rc |= dev_alloc(&a->colptr, (size_t)width + 1);
+    rc |= dev_alloc(&a->colptr_t, (size_t)height + 1);
+    rc |= dev_alloc(&a->rowidx, (size_t)nnz);
+    rc |= dev_alloc(&a->rowidx_t, (size_t)nnz);
+    rc |= dev_alloc(&a->val, (size_t)nnz);
+    rc |= dev_alloc(&a->val_t, (size_t)nnz);
+    if (rc) { smk_matrix_destroy(a); return SMK_DEVICE_ERROR; }
+    if (fill(a->colptr, a->rowidx, a->val, g_stream) != 0 ||
+        device_csc_transpose(height, width, nnz, a->colptr, a->rowidx, a->val, a->colptr_t, a->rowidx_t, a->val_t, g_stream) != 0) {
+        smk_matrix_destroy(a);
+        return SMK_DEVICE_ERROR;
+    }
+    const hipError_t e = hipStreamSynchronize(g_stream);
+    if (e != hipSuccess) {
+        set_error(std::string("resident CSC: ") + hipGetErrorString(e));
+        smk_matrix_destroy(a);
+        return SMK_DEVICE_ERROR;
+    }
+    *out = a;
+    return SMK_OK;
+}
+
+hipStream_t context_stream(bool* initialized)
+{
+    if (initialized) *initialized = g_init;
+    return g_stream;
+}
+}  // namespace smk
+}  // extern "C++"
+
 // host copy of a resident CSC (32-bit offsets), fetched on first use: only column subsets whose list is not strictly
 // increasing are cut on the host
 static int ensure_host_csc(const smk_matrix* a)
