@@ -486,7 +486,7 @@ void device_priority_release();
 int device_csc_transpose(i64 height, i64 ncols, i64 nnz, const i64* colptr, const unsigned* rowidx, const double* val,
                          i64* colptr_t, unsigned* rowidx_t, double* val_t, hipStream_t st);
 
-// solver.cpp: the calling thread's context stream (initialized: whether smk_initialize has run); a resident sparse matrix
+// context.cpp: the calling thread's context stream (initialized: whether smk_initialize has run); matrix.cpp: a resident sparse matrix
 // whose CSC `fill` writes on the device (on the stream it is given), transpose as smk_matrix_create_sparse builds it
 hipStream_t context_stream(bool* initialized);
 int matrix_create_sparse_device(::smk_matrix** out, i64 height, i64 width, i64 nnz,

@@ -10,7 +10,7 @@
 //     (no kernel that still uses the memory can be in flight), at the cost of a sync on an idle device (~10 us);
 //   * a failed hipMalloc empties the device's cache and tries once more;
 //   * SMK_DEVMEM_CACHE=0 turns the cache off (every call goes to the runtime), SMK_POISON=1 still poisons every block a
-//     caller receives (dev_alloc in solver.cpp), reused or fresh;
+//     caller receives (dev_alloc in state.h), reused or fresh;
 //   * smk_finalize / smk_thread_context_end / smk_device_trim return the cached blocks of their device (dev_trim).
 #include "common.h"
 

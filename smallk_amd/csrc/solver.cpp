@@ -1,6 +1,6 @@
-// smallk_amd/csrc/solver.cpp -- host side of the C ABI (include/smallk_amd.h):
-// device-resident A, the NmfSolve<> driver loop and the three per-iteration
-// schedules (MU / HALS / BPP) expressed as launches of the kernels in kernels.hip.
+// smallk_amd/csrc/solver.cpp -- the solver handle of the C ABI (include/smallk_amd.h): planning and
+// allocation, the communicator plumbing, the NmfSolve<> driver loop and the per-iteration schedules
+// (MU / HALS / BPP / RANK2) expressed as launches of the kernels in kernels.hip.
 //
 // Device data layout (all in HBM, fp64 unless noted):
 //   A   : m_pad x n_pad   bf16|f32, column-major, zero padded (rows to 128, cols to 128)
@@ -12,1022 +12,20 @@
 //   Gw = W'W, Gh = HH' : KP x KP (KP = 8/16/32/64 padded)
 //   P1 : S1 slabs of n_pad x kpp fp64 = W'A partials,   P2 : S2 slabs of m_pad x kpp = (AH')' partials
 //   packW / packH : MFMA operand fragments of W' / H
-#include "common.h"
+#include "state.h"
 #include "comm.h"
-#include "../../include/smallk_amd.h"
 
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <functional>
-#include <vector>
 #include <deque>
 #include <algorithm>
 #include <thread>
-#include <mutex>
-
-struct smk_matrix;
-
-namespace smk {
-
-// One device context per process by default; the single-process multi-GPU driver (smk_nmf_dense_sharded) runs
-// one host thread per shard and gives each its own context through t_ctx.
-struct DeviceCtx {
-    bool init = false;
-    int cus = 256;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int live_solvers = 0;               // solver handles cache the stream: it cannot change under them
-    std::vector<struct ::smk_matrix*> mats;   // live matrices: they follow the context's stream when it is replaced
-};
-static DeviceCtx g_ctx;
-static thread_local DeviceCtx* t_ctx = nullptr;
-static inline DeviceCtx& ctx() { return t_ctx ? *t_ctx : g_ctx; }
-#define g_init (ctx().init)
-#define g_cus (ctx().cus)
-#define g_stream (ctx().stream)
-#define g_own_stream (ctx().own_stream)
-#define g_live_solvers (ctx().live_solvers)
-static thread_local std::string g_err;
-
-void set_error(const std::string& msg) { g_err = msg; }
-
-static inline double wall_us()
-{
-    using namespace std::chrono;
-    return (double)duration_cast<nanoseconds>(steady_clock::now().time_since_epoch()).count() * 1e-3;
-}
-
-template <typename T>
-static int dev_alloc(T** p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0) count = 1;
-    SMK_HIP(smk::dev_malloc((void**)p, count * sizeof(T)));
-    // debugging aid: SMK_POISON=1 fills every fresh workspace with 0xFF bytes (NaN as fp64 / fp32, -1 as int), so that a
-    // kernel reading memory nobody wrote shows up in every run instead of once in a hundred
-    static const bool poison = [] { const char* e = getenv("SMK_POISON"); return e && atoi(e) != 0; }();
-    if (poison) { SMK_HIP(hipMemset(*p, 0xFF, count * sizeof(T))); SMK_HIP(hipDeviceSynchronize()); }   // the fill must not trail work on the non-blocking streams
-    return 0;
-}
-
-}  // namespace smk
-
-using namespace smk;
-
-struct smk_matrix {
-    i64 m = 0, n_global = 0, c0 = 0, n = 0;
-    int storage = SMK_STORE_F32;
-    hipStream_t st = nullptr;                        // stream of the context that created it
-    smk::DeviceCtx* owner = nullptr;                 // the context whose registry lists it (nullptr once that context is gone)
-    mutable float ascale = 0.f;                      // fp16 two-term products: power of two with max|A| ascale in [2^13, 2^14); 0 = not yet measured
-    mutable int col_spread_log2 = -1;                // log2(largest / smallest non-zero column maximum of |A|); -1 = not yet measured
-    mutable double colnorm_max = -1.0, rownorm_max = -1.0;   // largest 2-norm of a column / a row of A (dense; NnlsPack's bound); < 0 = not yet measured
-    void* A = nullptr;  i64 ldA = 0, colsA = 0;      // m_pad x n_pad
-    void* At = nullptr; i64 ldAt = 0, colsAt = 0;    // n_pad x m_pad
-    // single copy (MU / HALS): no stored transpose -- the H*A' pass contracts down the strided direction of A itself
-    // (bigprod.hip: TRB for bf16, TAIL = 2 for fp32), as the reference's MU / HALS do (Gemm(NORMAL, TRANSPOSE) on A, nmf_solver_mu.hpp:121-164,
-    // nmf_solver_hals.hpp:166-199); half the footprint, no transpose pass at load time
-    bool single = false;
-    // sparse A: CSC of the local columns and CSC of its transpose (fp64 values, 64-bit offsets)
-    bool sparse = false;
-    i64 nnz = 0;
-    i64 *colptr = nullptr, *colptr_t = nullptr;
-    unsigned *rowidx = nullptr, *rowidx_t = nullptr;
-    double *val = nullptr, *val_t = nullptr;
-    // host copy of the CSC (column subsets for HierNMF2 nodes are cut on the host)
-    // RANK2 on a factor larger than an L2: the entries regrouped by row block (spmm_blocked.hip), built on first use
-    mutable BlockedCsc bA, bAt;
-    mutable bool blocked_tried = false;
-    // ranks 3 .. 128 on sparse A: the entry-balanced segments of CSC(A) / CSC(A') (spmm_seg.hip), built on first use
-    mutable SegPlan segA, segAt;
-    mutable bool seg_tried = false;
-    mutable std::vector<unsigned> h_colptr, h_rowidx;     // fetched on first use (ensure_host_csc)
-    mutable std::vector<double> h_val;
-};
-
-static const int MAX_CHUNKS = 8;
-static void repoint_matrices(hipStream_t st);
-
-// The registries of all contexts share one lock: a matrix may be destroyed from another thread than the one that created
-// it (Python's collector, the workers of smk_nmf_dense_sharded), and it leaves the registry of the context that OWNS it.
-static std::mutex g_mats_mu;
-static void repoint_matrices(hipStream_t st)
-{
-    std::lock_guard<std::mutex> lk(g_mats_mu);
-    for (smk_matrix* a : ctx().mats) a->st = st;
-}
-// the context goes away: its matrices stay alive without an owner (they take the next context's stream)
-static void orphan_matrices()
-{
-    std::lock_guard<std::mutex> lk(g_mats_mu);
-    for (smk_matrix* a : ctx().mats) { a->st = nullptr; a->owner = nullptr; }
-    ctx().mats.clear();
-}
-static void register_matrix(smk_matrix* a)
-{
-    std::lock_guard<std::mutex> lk(g_mats_mu);
-    a->owner = &ctx();
-    a->owner->mats.push_back(a);
-}
-static void unregister_matrix(smk_matrix* a)
-{
-    std::lock_guard<std::mutex> lk(g_mats_mu);
-    if (!a->owner) return;
-    auto& v = a->owner->mats;
-    v.erase(std::remove(v.begin(), v.end(), a), v.end());
-    a->owner = nullptr;
-}
-
-struct smk_solver {
-    smk_options o;
-    const smk_matrix* a = nullptr;
-    int k = 0, KP = 0, kpp = 0, nsplit = 3;
-    i64 m = 0, n = 0;
-    hipStream_t st = nullptr;
-    double *H = nullptr, *Wt = nullptr, *Gw = nullptr, *Gh = nullptr, *gram_scratch = nullptr;
-    double* seg_pieces[2] = {nullptr, nullptr};     // sparse A, spmm_seg.hip: partial sums of the long columns of pass 0 / 1
-    double *Wprev = nullptr, *hals_scratch = nullptr, *pg_partials = nullptr, *scal = nullptr, *tmpW = nullptr;
-    double* wide_tmp = nullptr;           // k > 128: max(m, n) x KP, the product X G of the MU rule and of the gradients
-    double* tmpH = nullptr;               // k x n compact copy of H for the host (get_factors)
-    // RANK2 (rank2.hip): scratch of the fused solve / progress kernels (ticket + partial sums), W'W of the W just solved
-    // (before its normalisation), and -- sparse A -- compact N x 2 copies of the factors for the gather products
-    double *r2_scratch = nullptr, *r2_prog = nullptr, *Graw = nullptr, *Hc = nullptr, *Wc = nullptr;
-    static constexpr int PROG_SLOTS = 4;         // progress checks in flight + 1 (solver_run_once / smk_solver_iterate_checked)
-    double* pin_r2[PROG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};      // pinned copies of the progress partials (the host sums them)
-    // the whole RANK2 factorisation as one resident launch (rank2_persist.hip): second H buffer, the rows of (AH')', partial
-    // sums, barrier words, result slots (device + pinned); latched off after an aborted launch
-    double *r2p_hc1 = nullptr, *r2p_r2c = nullptr, *r2p_part = nullptr, *r2p_out = nullptr, *r2p_pin = nullptr;
-    unsigned* r2p_sync = nullptr;
-    bool r2p_off = false;
-    // run-time guard of the product form (guard_step): a column sample of A, its accurate-form product, the comparison scalars
-    // + both Gram matrices on their way to the host
-    void* guard_As = nullptr;
-    unsigned* guard_cols = nullptr;
-    double *guard_P = nullptr, *guard_dev = nullptr, *guard_pin = nullptr;
-    hipEvent_t guard_ev = nullptr;
-    BigProdPlan guard_pl[MAX_GROUPS];
-    int guard_ncols = 0, guard_checks = 0, guard_fired = 0;
-    bool guard_pending = false, guard_off = false;
-    double guard_last = 0.0;               // cond * delta of the last check
-    bool wc_valid = false;
-    double* nnls_scratch = nullptr;       // BPP: inverses of W'W and HH' + path selectors (k > 32), two halves
-    unsigned* nnls_defer = nullptr;       // BPP, k in (32, 64]: work list between nnls_bpp_g16_kernel and the wave-per-column kernel
-    int hals_ep_blocks = 0;               // HALS, k <= 32: Gram partials the sweeps' epilogues may write into gram_scratch (0: epilogues off)
-    // deferred progress check (BPP, k <= 16; check_rides_in_nnls): the slot whose totals the NEXT H-side NNLS launch produces, the
-    // iteration tag up to which a failure counts for it, whether its snapshot is being written by this iteration's NNLS launches
-    int pg_defer_slot = -1, pg_defer_tag = 0, pg_defer_nblk = 0, iter_snap_slot = -1;
-    bool pg_defer_snap = false;
-    unsigned check_routes[4] = {0, 0, 0, 0}; // progress checks formed so far by route (smk_solver_kernel_name(2)): 1 own launches, 2 NNLS riders + totals launch, 3 riders + pass tail
-    int pg_totals_slot = -1;                 // >= 0: the H-side launch has left the partial sums of this slot's check; its totals are due
-    hipStream_t st_inv = nullptr;         // the 0.1 ms single-workgroup inversions run here, beside the streaming products
-    hipEvent_t ev_g[2] = {nullptr, nullptr}, ev_inv[2] = {nullptr, nullptr};
-    bool inv_pending[2] = {false, false};
-    bool gram_ride[2] = {false, false};   // sparse, k in (8, 32]: this factor's Gram matrix is due and rides in the two launches of the gather product that follows (gram_factor, timed_spmm)
-    bool inv_ride[2] = {false, false};    // sparse BPP, k in (16, 64]: this side's Gram matrix is new, its inverse is to ride in the product launch that follows (timed_spmm)
-    double *xscale[2] = {nullptr, nullptr}, *oscale[2] = {nullptr, nullptr};   // fp16 two-term products: row scales of W / H (from the Gram diagonal) and their inverses
-    bool packed_fresh[2] = {false, false};   // the fused Gram kernel has already written packW / packH for the next product
-    int nnls_gram_nblk[2] = {0, 0};          // > 0: the NNLS launch of this side left that many Gram partials in gram_scratch (k <= 16)
-    // k in (8, 16], BPP, fp16 form, one GPU (C2): the NNLS launch also PACKS the factor it solves (row scales from an a-priori
-    // bound, NnlsPack) and the reduction of its Gram partials rides in the streaming pass that follows (BigProdPlan::tail_*),
-    // so nothing stands between the solve and the product.  Indexed by factor: 0 = W, 1 = H.
-    bool pack_in_solve = false;              // the shape qualifies (decided with the plans)
-    bool pack_in_solve_off = false;          // latched by pack_fail_soft
-    bool from_nnls[2] = {false, false};      // the factor is the output of an NNLS launch of this run (hence >= 0)
-    bool nnls_packed[2] = {false, false};    // the last NNLS launch packed this factor
-    int tail_nblk[2] = {0, 0};               // > 0: the next product of this factor carries the reduction of that many partials
-    // HALS: the fused W sweep needs every workgroup resident; if its bounded polls ever expire (flag -3) the run is
-    // repeated from the initial factors on the one-launch-per-column path, latched for the life of the handle
-    double *W0c = nullptr, *H0c = nullptr;
-    bool hals_multi = false;
-    int hals_calls = 0;
-    double *Gh_own = nullptr, *scal_own = nullptr, *Wt_own = nullptr;
-    void *packW = nullptr, *packH = nullptr;
-    double *P1 = nullptr, *P2 = nullptr;
-    float* R2red = nullptr;
-    BigProdPlan pl1, pl2;                 // first group of each pass (row splits, P layout)
-    BigProdPlan pg1[MAX_GROUPS], pg2[MAX_GROUPS];   // all groups: k > 64 streams the big matrix once per 64 factor rows
-    int ng = 1;
-    int* fail_flag = nullptr;
-    int iter = 0;
-    bool have_factors = false, inited = false, normalized = false;
-    double pg0 = 1.0, last_metric = 1.0;
-    size_t pg_half = 2048;
-    // comm: a native communicator (RCCL or the in-process stand-in, comm.cpp) or -- test hook -- a host callback
-    int rank = 0, world = 1;
-    smk_allreduce_fn ar = nullptr;
-    void* ar_user = nullptr;
-    smk_comm* comm = nullptr;
-    void* comm_ws = nullptr;              // owned workspace when a native communicator is attached
-    // Native communicator: EVERY collective is issued on st2 (one stream per communicator), tied to the main stream by
-    // events.  The rows of A (= columns of A', rows of W) are cut into `nchunk` chunks of world * blk rows; block r of a
-    // chunk belongs to rank r (block-cyclic), so a chunk is at once a contiguous range of the H*At pass, the send buffer
-    // of one reduce-scatter / all-reduce and the receive buffer of one all-gather: the exchange of chunk j runs on st2
-    // while the streaming product works on chunk j + 1.
-    int nchunk = 1;
-    i64 blk = 0, rows_cap = 0;            // rows per (chunk, rank) block (multiple of 256); world * nchunk * blk >= m_pad
-    bool r2_alias = false;                // the H*At pass writes ONE slab of fp64 partial products: the collectives work on it directly (no copy)
-    bool red_f64 = false;                 // element type of the summed (AH')' on the wire (native communicator: fp64 unless SMK_COMM_F64=0)
-    bool w_sharded = false;               // BPP: every rank solves (and holds current) only its own blocks of W
-    bool w_full = true;                   // all rows of the fp64 W on this rank are current
-    // a row-sharded W: this rank's blocks back to back (KP x nchunk*blk; the n_own valid rows are a prefix because only the
-    // last non-empty block of a rank can be short) and, in the same order, its rows of the summed (AH')'
-    double* Wown = nullptr;
-    void* R2own = nullptr;
-    i64 n_own = 0;
-    hipStream_t st2 = nullptr;
-    hipEvent_t ev_gram = nullptr, ev_gh = nullptr, ev_x = nullptr, ev_y = nullptr;
-    hipEvent_t ev_c[MAX_CHUNKS] = {}, ev_r[MAX_CHUNKS] = {}, ev_a[MAX_CHUNKS] = {};
-    bool gh_pending = false;
-    bool r2_pending = false;              // the chunk exchanges of the last H*At pass have not been joined by the main stream yet
-    bool inv_done[2] = {false, false};    // the inverse of this side's current Gram matrix is in place (ordered before the main stream)
-    // stopping rule evaluated one iteration late (smk_solver_run): pinned result slots, events, and a
-    // snapshot of (W, H, W'W) per checked iteration so that a speculative iteration can be undone
-    struct ProgSlot { double h[8]; int flag; int fused; };     // fused: the flag travels in h[5]
-    ProgSlot* pin = nullptr;
-    hipEvent_t pev[PROG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
-    double poll_tag[PROG_SLOTS] = {0, 0, 0, 0};      // != 0: the kernel stores this into h[7] behind the result; progress_end polls the slot (no event)
-    double* snap[PROG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
-    // timing
-    bool timing = false;
-    // a pair of event records around a launch costs ~11 us of idle time (5.7 us in front of the kernel, 5.8 behind it: measured
-    // on C2, where that was 23 of 119 us per iteration): passes shorter than ~0.2 ms are timed one launch in `timing_stride`
-    // and the totals scaled back up, so that measuring does not change what is measured
-    int timing_stride = 1;
-    unsigned pass_counter[2] = {0, 0}, pass_sampled[2] = {0, 0};     // passes seen / passes that carried events since enable_timing
-    bool pass_timed[2] = {false, false};     // this W'A / H*At pass (all of its launches, and the collectives behind it) is a timed sample
-    struct TimedSpan { hipEvent_t e0, e1; int counts; };     // counts: this span completes one launch (a pass cut into chunks is ONE launch)
-    // 0: W'A passes, 1: H*At passes, 2: the big collectives of a sharded run (on st2), 3: what the MAIN stream spends waiting
-    // for events of the collective stream (the exposed part of the exchange: the bracket holds nothing but the wait)
-    // 4: the same bracket around a wait for an event that completed long ago -- what a bracket costs by itself (three packets
-    // through the command processor, ~15 us): exposure = slot 3 - brackets x the average of slot 4
-    std::vector<TimedSpan> ev[6];       // 0 / 1: the passes, 2 - 4: collectives, waits, calibration, 5: the block-pivoting launches
-    double acc_ms[6] = {0, 0, 0, 0, 0, 0};
-    int launches[6] = {0, 0, 0, 0, 0, 0};
-    hipEvent_t ev_cal = nullptr;          // recorded once on the collective stream
-    unsigned cal_counter = 0;
-};
-
-static const int GRAM_BLOCKS = 256;
-
 
 extern "C" {
 
-int smk_initialize(int device_ordinal)
-{
-    if (device_ordinal >= 0) SMK_HIP(hipSetDevice(device_ordinal));
-    int dev = 0;
-    SMK_HIP(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    SMK_HIP(hipGetDeviceProperties(&prop, dev));
-    g_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (!g_stream) {
-        SMK_HIP(hipStreamCreateWithFlags(&g_stream, hipStreamNonBlocking));
-        g_own_stream = true;
-    }
-    g_init = true;
-    return SMK_OK;
-}
-
-int smk_is_initialized(void) { return g_init ? SMK_INITIALIZED : SMK_NOTINITIALIZED; }
-
-void smk_finalize(void)
-{
-    if (g_stream) (void)hipStreamSynchronize(g_stream);
-    if (g_own_stream && g_stream) (void)hipStreamDestroy(g_stream);
-    orphan_matrices();                    // a matrix that outlives the context takes the next context's stream
-    dev_trim();                           // cached device blocks of this device go back to the runtime
-    g_stream = nullptr;
-    g_own_stream = false;
-    g_init = false;
-}
-
-// A host thread that drives a device of its own (the second device of a two-device HierNMF2 run, hierclust.cpp): its
-// library state -- stream, CU count, live handles -- is separate from the process-wide context from here to _end().
-int smk_thread_context_begin(int device_ordinal)
-{
-    if (t_ctx) { set_error("this thread already has a context of its own"); return SMK_BAD_PARAM; }
-    t_ctx = new DeviceCtx;
-    const int rc = smk_initialize(device_ordinal);
-    if (rc != SMK_OK) { delete t_ctx; t_ctx = nullptr; }
-    return rc;
-}
-void smk_thread_context_end(void)
-{
-    if (!t_ctx) return;
-    smk_finalize();
-    delete t_ctx;
-    t_ctx = nullptr;
-}
-int smk_device_count(void)
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
-}
-int smk_current_device(void)
-{
-    int d = 0;
-    return hipGetDevice(&d) == hipSuccess ? d : -1;
-}
-
-size_t smk_device_trim(void)
-{
-    size_t cached = 0;
-    smk::dev_cache_stats(nullptr, nullptr, &cached);
-    smk::dev_trim();
-    return cached;
-}
-
-int smk_device_synchronize(void)
-{
-    SMK_HIP(hipDeviceSynchronize());
-    return SMK_OK;
-}
-
-const char* smk_last_error(void) { return g_err.c_str(); }
-int smk_device_cu_count(void) { return g_cus; }
-
-int smk_set_stream(void* hip_stream)
-{
-    if (g_live_solvers > 0) { set_error("smk_set_stream: destroy every solver handle first"); return SMK_BAD_PARAM; }
-    if (g_stream) (void)hipStreamSynchronize(g_stream);     // resident-matrix work queued on the old stream
-    if (g_own_stream && g_stream) (void)hipStreamDestroy(g_stream);
-    g_stream = (hipStream_t)hip_stream;
-    g_own_stream = false;
-    repoint_matrices(g_stream);           // resident matrices were created under the old stream
-    return SMK_OK;
-}
-
-// IsValid, common/src/nmf_options.cpp:23-112 (same checks, same messages)
-int smk_is_valid(const smk_options* o, int validate_matrix)
-{
-    if (!o) return 0;
-    if (o->k <= 0) { fprintf(stderr, "nmflib error: k-value must be a positive integer\n"); return 0; }
-    if (validate_matrix) {
-        if (o->height <= 0) { fprintf(stderr, "nmflib error: matrix height must be a positive integer\n"); return 0; }
-        if (o->width <= 0) { fprintf(stderr, "nmflib error: matrix width must be a positive integer\n"); return 0; }
-        if (o->k > o->width) { fprintf(stderr, "nmflib error: k value cannot exceed the number of columns\n"); return 0; }
-    }
-    if (o->tol <= 0.0 || o->tol >= 1.0) { fprintf(stderr, "nmflib error: tolerance must be in the interval (0.0, 1.0)\n"); return 0; }
-    if (o->min_iter <= 0) { fprintf(stderr, "nmflib error: miniter must be a positive integer\n"); return 0; }
-    if (o->max_iter <= 0) { fprintf(stderr, "nmflib error: maxiter must be a positive integer\n"); return 0; }
-    if (o->tolcount <= 0) { fprintf(stderr, "nmflib error: tolcount must be a positive integer\n"); return 0; }
-    if (o->algorithm != SMK_ALG_MU && o->algorithm != SMK_ALG_HALS && o->algorithm != SMK_ALG_RANK2 &&
-        o->algorithm != SMK_ALG_BPP) {
-        fprintf(stderr, "nmflib error: unknown NMF algorithm specified\n");
-        return 0;
-    }
-    if (o->algorithm == SMK_ALG_RANK2 && o->k != 2) { fprintf(stderr, "nmflib error: RANK2 algorithm requires k == 2\n"); return 0; }
-    if (o->prog_est_algorithm != SMK_PROG_PG_RATIO && o->prog_est_algorithm != SMK_PROG_DELTA_FNORM) {
-        fprintf(stderr, "nmflib error: unknown stopping criterion specified\n");
-        return 0;
-    }
-    return 1;
-}
-
-// same generator as the device fill (kernels.hip) and the oracle, on the host
-static inline uint64_t h_mix64(uint64_t z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-void smk_uniform_fill_host(double* buf, int64_t ld, int64_t rows, int64_t cols, int64_t r0, int64_t c0,
-                           int64_t gheight, uint64_t seed, int quant)
-{
-    for (int64_t c = 0; c < cols; ++c)
-        for (int64_t r = 0; r < rows; ++r) {
-            uint64_t h = h_mix64(seed * 0xD1342543DE82EF95ull + (uint64_t)((c0 + c) * gheight + (r0 + r)));
-            float f = (float)(h >> 40) * (1.0f / 16777216.0f);
-            if (quant == 1) {
-                uint32_t b;
-                memcpy(&b, &f, 4);
-                b += 0x7FFFu + ((b >> 16) & 1u);
-                b &= 0xFFFF0000u;
-                memcpy(&f, &b, 4);
-            }
-            buf[c * ld + r] = (double)f;
-        }
-}
-
-// ------------------------------------------------------------------------------------------
-// matrix
-// ------------------------------------------------------------------------------------------
-static thread_local bool g_create_single = false;
-int smk_matrix_create(smk_matrix** out, int64_t height, int64_t width_global, int64_t col0, int64_t ncols_local,
-                      int storage)
-{
-    if (!out) return SMK_BAD_PARAM;
-    *out = nullptr;
-    if (!g_init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
-    if (height <= 0 || width_global <= 0 || ncols_local <= 0 || col0 < 0 || col0 + ncols_local > width_global ||
-        (storage != SMK_STORE_F32 && storage != SMK_STORE_BF16))
-        return SMK_BAD_PARAM;
-    smk_matrix* a = new smk_matrix;
-    a->m = height; a->n_global = width_global; a->c0 = col0; a->n = ncols_local; a->storage = storage;
-    a->st = g_stream;
-    register_matrix(a);
-    // rows of A padded to COL_PAD, not ROW_PAD: a single-copy matrix is also read through the transposed source, whose tiles are
-    // 128 ROWS of A and whose chunked passes (sharded runs, chunk_rows) run to round_up(m, COL_PAD) -- with 128-row padding a
-    // height with 0 < m mod 256 <= 128 let the last tile read 128 rows past the column (the next column's data; past the
-    // allocation in the last column).  The pad rows are zero like every other pad.
-    a->ldA = round_up(height, COL_PAD);      a->colsA = round_up(ncols_local, COL_PAD);
-    a->ldAt = round_up(ncols_local, ROW_PAD); a->colsAt = round_up(height, COL_PAD);
-    const size_t es = (size_t)elem_size(storage);
-    // A column stride that is a multiple of 1 MiB gets ROW_PAD more (zero) rows: with the 128 columns of a workgroup's stage
-    // exactly 2^20 bytes apart the W'A pass of C4 runs 3 % slower (11.3 -> 10.95 ms) and that of a C4 shard 8 % (1.60 ->
-    // 1.47 ms; bench.py --emulate-world 8: 3.28 -> 3.15 ms per rank).  Smaller power-of-two strides are best left alone
-    // (C3: 128 KiB and 32 KiB strides, skewed: 1200 -> 1130 / 980 it/s); 256 and 384 rows more gain less than 128.
-    // SMK_LD_SKEW=0 turns it off, =n asks for n rows.  (profiles/r04_leading_dimension_skew.txt)
-    {
-        static const i64 skew = [] { const char* e = getenv("SMK_LD_SKEW"); return e ? (i64)atoll(e) / ROW_PAD * ROW_PAD : ROW_PAD; }();
-        if (skew > 0 && ((size_t)a->ldA * es) % ((size_t)1 << 20) == 0) a->ldA += skew;
-        if (skew > 0 && ((size_t)a->ldAt * es) % ((size_t)1 << 20) == 0) a->ldAt += skew;
-    }
-    {   // SMK_SINGLE_COPY=1: dense matrices are created without the stored transpose (smk_matrix_create_single_copy asks for it explicitly)
-        const char* esc = getenv("SMK_SINGLE_COPY");
-        a->single = g_create_single || (esc && esc[0] == '1');
-    }
-    hipError_t e1 = smk::dev_malloc(&a->A, (size_t)a->ldA * a->colsA * es);
-    hipError_t e2 = (e1 == hipSuccess && !a->single) ? smk::dev_malloc(&a->At, (size_t)a->ldAt * a->colsAt * es) : e1;
-    if (e1 == hipSuccess && e2 != hipSuccess && !a->single) {
-        // A fits, A and A' together do not: the matrix becomes a single copy (MU, HALS and BPP with the 16-bit product forms run
-        // on it as they are; RANK2 and the accurate form will ask for the transpose and report the allocation failure then)
-        (void)hipGetLastError();
-        a->At = nullptr;
-        a->single = true;
-        e2 = hipSuccess;
-    }
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        set_error(std::string("smk::dev_malloc(A): ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-        if (a->A) (void)smk::dev_free(a->A);
-        delete a;
-        return SMK_DEVICE_ERROR;
-    }
-    e1 = hipMemsetAsync(a->A, 0, (size_t)a->ldA * a->colsA * es, g_stream);
-    if (e1 == hipSuccess && a->At) e1 = hipMemsetAsync(a->At, 0, (size_t)a->ldAt * a->colsAt * es, g_stream);
-    if (e1 != hipSuccess) {
-        set_error(std::string("hipMemsetAsync(A): ") + hipGetErrorString(e1));
-        smk_matrix_destroy(a);
-        return SMK_DEVICE_ERROR;
-    }
-    *out = a;
-    return SMK_OK;
-}
-
-int smk_matrix_create_single_copy(smk_matrix** out, int64_t height, int64_t width_global, int64_t col0, int64_t ncols_local,
-                                  int storage)
-{
-    g_create_single = true;
-    const int rc = smk_matrix_create(out, height, width_global, col0, ncols_local, storage);
-    g_create_single = false;
-    return rc;
-}
-int smk_matrix_is_single_copy(const smk_matrix* a) { return a && a->single ? 1 : 0; }
-// bytes of HBM the resident matrix occupies (A, the stored transpose when there is one, the CSC arrays of a sparse matrix)
-int64_t smk_matrix_device_bytes(const smk_matrix* a)
-{
-    if (!a) return 0;
-    if (a->sparse) return (int64_t)((size_t)(a->n + 1 + a->m + 1) * sizeof(i64) + 2 * (size_t)a->nnz * (sizeof(unsigned) + sizeof(double)));
-    const size_t es = (size_t)elem_size(a->storage);
-    return (int64_t)((size_t)a->ldA * a->colsA * es + (a->At ? (size_t)a->ldAt * a->colsAt * es : 0));
-}
-
-// a single-copy matrix meets a consumer of the stored transpose (BPP, RANK2, the accurate form, column subsets): allocate and fill
-// it now; solvers already planned on the transposed source keep reading A (their plans say so)
-static int matrix_materialize_transpose(const smk_matrix* ca)
-{
-    smk_matrix* a = const_cast<smk_matrix*>(ca);       // the lazily built parts of a matrix (scales, blocked CSC, segment plans) are filled the same way
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!a->single || a->At) return 0;
-    const size_t es = (size_t)elem_size(a->storage);
-    hipStream_t st = a->st ? a->st : g_stream;
-    if (smk::dev_malloc(&a->At, (size_t)a->ldAt * a->colsAt * es) != hipSuccess) { a->At = nullptr; set_error("no memory for the stored transpose of a single-copy matrix"); return SMK_DEVICE_ERROR; }
-    SMK_HIP(hipMemsetAsync(a->At, 0, (size_t)a->ldAt * a->colsAt * es, st));
-    const int rc = launch_transpose_store(a->A, a->ldA, a->At, a->ldAt, a->storage, a->m, a->n, st);
-    if (rc) return rc;
-    SMK_HIP(hipStreamSynchronize(st));
-    a->single = false;
-    return 0;
-}
-
-static int matrix_make_transpose(smk_matrix* a)
-{
-    if (a->single) return 0;
-    return launch_transpose_store(a->A, a->ldA, a->At, a->ldAt, a->storage, a->m, a->n, g_stream);
-}
-
-// ---- host fp64 -> resident matrix ---------------------------------------------------------------------------------------
-// The reference wraps the caller's buffer as a view, no copy (common/src/nmf.cpp:224-226); here A has to cross PCIe once, and this
-// is the path every reference caller takes (nmf/src/main.cpp:218-233, smallk.cpp:604-619, smallk_lib.pyx:769).  The loop is plain:
-// hipMemcpy2DAsync straight from the caller's pageable buffer into one 64 MB device staging buffer, conversion to the stored type,
-// synchronise, next chunk; the stored transpose in one device pass at the end.  Round 6 MEASURED it before replacing it
-// (profiles/r06_upload_rates.txt, bench.py --api-path): 50 - 55 GB/s on C3's 8.6 GB, on a C4 shard's 17 GB and on C2's 0.27 GB -- the
-// runtime pins the pageable pages in place piece by piece and the per-chunk synchronisation costs nothing measurable.  Two
-// pipelined variants were built and timed against it on the same box: pinned staging buffers filled by 2 - 16 host threads with the
-// transfer and the conversion overlapped (41 GB/s whatever the thread count, 10 - 19 GB/s on C2's matrix: the pinned allocations)
-// and hipHostRegister of each chunk of the caller's buffer (52 GB/s).  Both slower, both removed.
-int smk_matrix_upload_f64(smk_matrix* a, const double* host, int64_t ld)
-{
-    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; }     // new contents: scale, column spread and norms are measured again on first use
-    if (!a || !host || ld < a->m || a->sparse) return SMK_BAD_PARAM;
-    const size_t budget = (size_t)64 << 20;   // staging bytes
-    i64 chunk = (i64)(budget / ((size_t)a->m * sizeof(double)));
-    if (chunk < 1) chunk = 1;
-    if (chunk > a->n) chunk = a->n;
-    double* stage = nullptr;
-    int rc = dev_alloc(&stage, (size_t)a->m * chunk);
-    if (rc) return rc;
-    struct Free { void* p; ~Free() { if (p) (void)smk::dev_free(p); } } stage_guard{stage};   // also on the error returns
-    const size_t es = (size_t)elem_size(a->storage);
-    for (i64 c = 0; c < a->n; c += chunk) {
-        const i64 nc = (a->n - c < chunk) ? (a->n - c) : chunk;
-        SMK_HIP(hipMemcpy2DAsync(stage, (size_t)a->m * sizeof(double), host + c * ld, (size_t)ld * sizeof(double),
-                                 (size_t)a->m * sizeof(double), (size_t)nc, hipMemcpyHostToDevice, g_stream));
-        rc = launch_convert_f64(stage, a->m, (unsigned char*)a->A + (size_t)c * a->ldA * es, a->storage, a->ldA,
-                                a->m, nc, g_stream);
-        if (rc) return rc;
-        SMK_HIP(hipStreamSynchronize(g_stream));
-    }
-    rc = matrix_make_transpose(a);
-    if (rc) return rc;
-    SMK_HIP(hipStreamSynchronize(g_stream));
-    return SMK_OK;
-}
-
-int smk_matrix_fill_uniform(smk_matrix* a, uint64_t seed)
-{
-    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; }
-    if (!a || a->sparse) return SMK_BAD_PARAM;
-    int rc = launch_fill_uniform(a->A, a->storage, a->ldA, a->m, a->n, a->ldA, a->colsA, 0, a->c0, a->m, seed,
-                                 a->storage == SMK_STORE_BF16 ? 1 : 0, g_stream);
-    if (rc) return rc;
-    rc = matrix_make_transpose(a);
-    if (rc) return rc;
-    SMK_HIP(hipStreamSynchronize(g_stream));
-    return SMK_OK;
-}
-
-int smk_matrix_fill_planted(smk_matrix* a, uint64_t seed, int kstar, double threshold, double noise)
-{
-    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; }
-    if (!a || a->sparse || kstar < 1 || kstar > 4096 || !(threshold >= 0.0 && threshold < 1.0) || !(noise >= 0.0)) return SMK_BAD_PARAM;
-    int rc = launch_fill_planted(a->A, a->storage, a->ldA, a->m, a->n, a->ldA, a->colsA, a->c0, a->m, seed, kstar, threshold,
-                                 noise, a->storage == SMK_STORE_BF16 ? 1 : 0, g_stream);
-    if (rc) return rc;
-    rc = matrix_make_transpose(a);
-    if (rc) return rc;
-    SMK_HIP(hipStreamSynchronize(g_stream));
-    return SMK_OK;
-}
-
-int smk_matrix_download_f64(const smk_matrix* a, double* host, int64_t ld)
-{
-    if (!a || !host || ld < a->m || a->sparse) return SMK_BAD_PARAM;
-    const size_t es = (size_t)elem_size(a->storage);
-    std::vector<unsigned char> col((size_t)a->m * es);
-    SMK_HIP(hipStreamSynchronize(g_stream));
-    for (i64 c = 0; c < a->n; ++c) {
-        SMK_HIP(hipMemcpy(col.data(), (const unsigned char*)a->A + (size_t)c * a->ldA * es, (size_t)a->m * es,
-                          hipMemcpyDeviceToHost));
-        if (a->storage == SMK_STORE_BF16) {
-            const uint16_t* p = (const uint16_t*)col.data();
-            for (i64 r = 0; r < a->m; ++r) {
-                uint32_t b = ((uint32_t)p[r]) << 16;
-                float f;
-                memcpy(&f, &b, 4);
-                host[c * ld + r] = (double)f;
-            }
-        } else {
-            const float* p = (const float*)col.data();
-            for (i64 r = 0; r < a->m; ++r) host[c * ld + r] = (double)p[r];
-        }
-    }
-    return SMK_OK;
-}
-
-void smk_matrix_destroy(smk_matrix* a)
-{
-    if (!a) return;
-    unregister_matrix(a);
-    free_blocked_csc(&a->bA);
-    free_blocked_csc(&a->bAt);
-    free_seg_plan(&a->segA);
-    free_seg_plan(&a->segAt);
-    void* ptrs[] = {a->A, a->At, a->colptr, a->colptr_t, a->rowidx, a->rowidx_t, a->val, a->val_t};
-    for (void* p : ptrs)
-        if (p) (void)smk::dev_free(p);
-    delete a;
-}
-
-// A copy of a resident matrix in the CALLING thread's context (its current device and stream): the second device of a
-// two-device HierNMF2 run holds one (hierclust.cpp).  Device-to-device copies; works across devices and on one.
-int smk_matrix_clone(const smk_matrix* src, smk_matrix** out)
-{
-    if (!src || !out) return SMK_BAD_PARAM;
-    *out = nullptr;
-    if (!g_init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
-    smk_matrix* a = new smk_matrix;
-    a->m = src->m; a->n_global = src->n_global; a->c0 = src->c0; a->n = src->n; a->storage = src->storage;
-    a->ascale = src->ascale; a->col_spread_log2 = src->col_spread_log2;
-    a->colnorm_max = src->colnorm_max; a->rownorm_max = src->rownorm_max;
-    a->ldA = src->ldA; a->colsA = src->colsA; a->ldAt = src->ldAt; a->colsAt = src->colsAt;
-    a->sparse = src->sparse; a->nnz = src->nnz; a->single = src->single;
-    a->st = g_stream;
-    register_matrix(a);
-    bool ok = true;
-    auto dup = [&](void** dst, const void* from, size_t bytes) {
-        if (!ok || !from) return;
-        if (bytes == 0) bytes = 8;
-        if (smk::dev_malloc(dst, bytes) != hipSuccess || hipMemcpy(*dst, from, bytes, hipMemcpyDefault) != hipSuccess) ok = false;
-    };
-    if (src->sparse) {
-        dup((void**)&a->colptr, src->colptr, (size_t)(src->n + 1) * sizeof(i64));
-        dup((void**)&a->colptr_t, src->colptr_t, (size_t)(src->m + 1) * sizeof(i64));
-        dup((void**)&a->rowidx, src->rowidx, (size_t)src->nnz * sizeof(unsigned));
-        dup((void**)&a->rowidx_t, src->rowidx_t, (size_t)src->nnz * sizeof(unsigned));
-        dup((void**)&a->val, src->val, (size_t)src->nnz * sizeof(double));
-        dup((void**)&a->val_t, src->val_t, (size_t)src->nnz * sizeof(double));
-    } else {
-        const size_t es = (size_t)elem_size(src->storage);
-        dup(&a->A, src->A, (size_t)src->ldA * src->colsA * es);
-        dup(&a->At, src->At, (size_t)src->ldAt * src->colsAt * es);
-    }
-    if (!ok) { set_error("smk_matrix_clone: device allocation or copy failed"); smk_matrix_destroy(a); return SMK_DEVICE_ERROR; }
-    *out = a;
-    return SMK_OK;
-}
-
-// ---- host-side CSC bookkeeping (no device involved; pinned against the reference's own SparseMatrix code
-// compiled in place, oracle/_ref/libref_sparse.so, by tests/test_ref_sparse.py) -------------------------
-// Transpose(SparseMatrix), common/include/sparse_matrix_ops.hpp:36-127: counting sort by row; inside a
-// row of the result the entries keep the source's column order.
-int smk_csc_transpose(int64_t height, int64_t width, const unsigned* col_offsets, const unsigned* row_indices,
-                      const double* data, unsigned* out_col_offsets /* height+1 */, unsigned* out_row_indices,
-                      double* out_data)
-{
-    if (height < 0 || width < 0 || !col_offsets || !out_col_offsets) return SMK_BAD_PARAM;
-    const unsigned base = col_offsets[0];
-    const int64_t nnz = (int64_t)col_offsets[width] - base;
-    if (nnz > 0 && (!row_indices || !data || !out_row_indices || !out_data)) return SMK_BAD_PARAM;
-    std::vector<i64> cnt((size_t)height + 1, 0);
-    for (int64_t p = 0; p < nnz; ++p) {
-        if ((int64_t)row_indices[base + p] >= height) { set_error("row index out of range"); return SMK_BAD_PARAM; }
-        cnt[(size_t)row_indices[base + p] + 1] += 1;
-    }
-    for (int64_t r = 0; r < height; ++r) cnt[(size_t)r + 1] += cnt[(size_t)r];
-    for (int64_t r = 0; r <= height; ++r) out_col_offsets[r] = (unsigned)cnt[(size_t)r];
-    std::vector<i64> fill(cnt.begin(), cnt.end() - 1);
-    for (int64_t c = 0; c < width; ++c)
-        for (i64 p = (i64)col_offsets[c] - base; p < (i64)col_offsets[c + 1] - base; ++p) {
-            const i64 q = fill[row_indices[base + p]]++;
-            out_row_indices[q] = (unsigned)c;
-            out_data[q] = data[base + p];
-        }
-    return SMK_OK;
-}
-
-// SparseMatrix::SubMatrixColsCompact, common/include/sparse_matrix_impl.hpp:478-592: the listed columns in
-// the listed order, rows without a stored entry dropped and the rest renumbered in increasing order.
-// Call once with out_* NULL for the sizes (*out_nnz, *new_height), then with arrays of that capacity.
-// old_to_new (height entries, 0xFFFFFFFF = dropped) and new_to_old may be NULL.
-int smk_csc_subset_cols_compact(int64_t height, int64_t width, const unsigned* col_offsets, const unsigned* row_indices,
-                                const double* data, const unsigned* cols, int64_t ncols, unsigned* out_col_offsets,
-                                unsigned* out_row_indices, double* out_data, unsigned* old_to_new, unsigned* new_to_old,
-                                int64_t* new_height, int64_t* out_nnz)
-{
-    if (height <= 0 || width <= 0 || !col_offsets || !cols || ncols <= 0) { set_error("SubMatrixColsCompact: empty column set"); return SMK_BAD_PARAM; }
-    const unsigned UNUSED = 0xFFFFFFFFu;
-    std::vector<unsigned> o2n((size_t)height, UNUSED);
-    int64_t total = 0;
-    for (int64_t j = 0; j < ncols; ++j) {
-        if ((int64_t)cols[j] >= width) { set_error("SubMatrixColsCompact: column index out of range"); return SMK_BAD_PARAM; }
-        for (unsigned p = col_offsets[cols[j]]; p < col_offsets[cols[j] + 1]; ++p) o2n[row_indices[p]] = 0;
-        total += col_offsets[cols[j] + 1] - col_offsets[cols[j]];
-    }
-    if (total == 0) { set_error("SparseMatrix::SubMatrixColsCompact: submatrix is the zero matrix"); return SMK_BAD_PARAM; }
-    int64_t nh = 0;
-    for (int64_t r = 0; r < height; ++r)
-        if (o2n[(size_t)r] != UNUSED) {
-            o2n[(size_t)r] = (unsigned)nh;
-            if (new_to_old) new_to_old[nh] = (unsigned)r;
-            ++nh;
-        }
-    if (old_to_new) std::copy(o2n.begin(), o2n.end(), old_to_new);
-    if (new_height) *new_height = nh;
-    if (out_nnz) *out_nnz = total;
-    if (!out_col_offsets) return SMK_OK;
-    if (!out_row_indices || !out_data) return SMK_BAD_PARAM;
-    unsigned q = 0;
-    for (int64_t j = 0; j < ncols; ++j) {
-        out_col_offsets[j] = q;
-        for (unsigned p = col_offsets[cols[j]]; p < col_offsets[cols[j] + 1]; ++p, ++q) {
-            out_row_indices[q] = o2n[row_indices[p]];
-            out_data[q] = data[p];
-        }
-    }
-    out_col_offsets[ncols] = q;
-    return SMK_OK;
-}
-
-// read a resident sparse matrix (or the stored CSC of its transpose) back to the host (tests)
-int smk_matrix_download_csc(const smk_matrix* a, int transposed, unsigned* col_offsets, unsigned* row_indices, double* data)
-{
-    if (!a || !a->sparse || !col_offsets) return SMK_BAD_PARAM;
-    const i64 nc = transposed ? a->m : a->n;
-    std::vector<i64> cp((size_t)nc + 1);
-    SMK_HIP(hipStreamSynchronize(g_stream));
-    SMK_HIP(hipMemcpy(cp.data(), transposed ? a->colptr_t : a->colptr, cp.size() * sizeof(i64), hipMemcpyDeviceToHost));
-    for (i64 c = 0; c <= nc; ++c) col_offsets[c] = (unsigned)cp[(size_t)c];
-    if (a->nnz > 0 && row_indices && data) {
-        SMK_HIP(hipMemcpy(row_indices, transposed ? a->rowidx_t : a->rowidx, (size_t)a->nnz * sizeof(unsigned), hipMemcpyDeviceToHost));
-        SMK_HIP(hipMemcpy(data, transposed ? a->val_t : a->val, (size_t)a->nnz * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return SMK_OK;
-}
-static int ensure_seg_plans(const smk_matrix* a)
-{
-    // lazily built part of a shared, nominally const matrix: same lock discipline as matrix_materialize_transpose
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    if (a->seg_tried) return 0;
-    a->seg_tried = true;
-    static const bool seg_on = [] { const char* e = getenv("SMK_SPMM_SEG"); return !(e && e[0] == '0'); }();
-    hipStream_t bst = a->st ? a->st : g_stream;
-    if (seg_on && (build_seg_plan(a->n, a->nnz, a->colptr, a->rowidx, &a->segA, bst) ||
-                   build_seg_plan(a->m, a->nnz, a->colptr_t, a->rowidx_t, &a->segAt, bst))) {
-        free_seg_plan(&a->segA);
-        free_seg_plan(&a->segAt);
-    }
-    return 0;
-}
-
-// The sparse Gemm of the reference by itself (common/include/sparse_gemm_ab_impl.hpp / sparse_gemm_ba_impl.hpp in gather
-// form): out (k x ncols(B)) = X (k x rows(B)) * B with B = A (transposed == 0: W'A from X = W') or B = A' (transposed != 0:
-// (AH')' from X = H), on the kernel the solver would take at rank k.  `reps` launches are timed with HIP events (avg_ms, may be NULL).
-int smk_matrix_sparse_product(const smk_matrix* a, int transposed, int k, const double* X, int64_t ldx, double* out,
-                              int64_t ldo, int reps, double* avg_ms)
-{
-    if (!a || !a->sparse || k < 1 || k > MAX_K || !X || !out || ldx < k || ldo < k) return SMK_BAD_PARAM;
-    const i64 rows = transposed ? a->n : a->m, ncols = transposed ? a->m : a->n;
-    const int KP = kp_of(k);
-    const int kpp = (k <= 2) ? 2 : KP;
-    const int ldx_dev = (k <= 2) ? 2 : KP;
-    hipStream_t st = a->st ? a->st : g_stream;
-    if (k > 2 && !is_wide(k)) ensure_seg_plans(a);
-    std::vector<double> xp((size_t)rows * ldx_dev, 0.0), pp((size_t)ncols * kpp);
-    for (i64 r = 0; r < rows; ++r)
-        for (int c = 0; c < k; ++c) xp[(size_t)r * ldx_dev + c] = X[r * ldx + c];
-    double *dX = nullptr, *dP = nullptr;
-    int rc = dev_alloc(&dX, xp.size());
-    if (!rc) rc = dev_alloc(&dP, pp.size());
-    struct Free { double *&a, *&b; ~Free() { if (a) (void)smk::dev_free(a); if (b) (void)smk::dev_free(b); } } guard{dX, dP};
-    if (rc) return rc;
-    SMK_HIP(hipMemcpyAsync(dX, xp.data(), xp.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    const i64* cp = transposed ? a->colptr_t : a->colptr;
-    const unsigned* ri = transposed ? a->rowidx_t : a->rowidx;
-    const double* va = transposed ? a->val_t : a->val;
-    const SegPlan& seg = transposed ? a->segAt : a->segA;
-    auto once = [&]() -> int {
-        if (k > 2 && !is_wide(k) && seg.rowflag && seg.ncols == ncols && !seg.uniform) return launch_spmm_seg(seg, cp, va, dX, k, dP, kpp, st);
-        return launch_spmm_gather(cp, ri, va, ncols, a->nnz, dX, ldx_dev, k, dP, kpp, st);
-    };
-    rc = once();
-    if (rc) return rc;
-    if (reps > 0 && avg_ms) {
-        hipEvent_t e0, e1;
-        SMK_HIP(hipEventCreate(&e0));
-        SMK_HIP(hipEventCreate(&e1));
-        SMK_HIP(hipEventRecord(e0, st));
-        for (int i = 0; i < reps && !rc; ++i) rc = once();
-        SMK_HIP(hipEventRecord(e1, st));
-        SMK_HIP(hipEventSynchronize(e1));
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        *avg_ms = (double)ms / reps;
-        if (rc) return rc;
-    }
-    SMK_HIP(hipMemcpyAsync(pp.data(), dP, pp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    SMK_HIP(hipStreamSynchronize(st));
-    for (i64 j = 0; j < ncols; ++j)
-        for (int c = 0; c < k; ++c) out[j * ldo + c] = pp[(size_t)j * kpp + c];
-    return SMK_OK;
-}
-int64_t smk_matrix_nnz(const smk_matrix* a) { return a ? a->nnz : 0; }
-int64_t smk_matrix_height(const smk_matrix* a) { return a ? a->m : 0; }
-
-// CSC shard (columns [col0, col0+ncols_local) of a height x width_global matrix) -> HBM, plus the
-// CSC of its transpose built on the host by a counting sort (SparseMatrix::Transpose,
-// sparse_matrix_ops.hpp:37-127).  Duplicate entries are kept (they add up in every product, as in
-// the reference's Compress(), sparse_matrix_impl.hpp:184-260).
-int smk_matrix_create_sparse(smk_matrix** out, int64_t height, int64_t width_global, int64_t col0,
-                             int64_t ncols_local, int64_t nnz, const unsigned* col_offsets,
-                             const unsigned* row_indices, const double* data)
-{
-    if (!out) return SMK_BAD_PARAM;
-    *out = nullptr;
-    if (!g_init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
-    if (height <= 0 || width_global <= 0 || ncols_local <= 0 || col0 < 0 || col0 + ncols_local > width_global ||
-        nnz < 0 || !col_offsets || (nnz > 0 && (!row_indices || !data)))
-        return SMK_BAD_PARAM;
-    if ((int64_t)col_offsets[ncols_local] - (int64_t)col_offsets[0] != nnz) { set_error("col_offsets do not span nnz"); return SMK_BAD_PARAM; }
-    const unsigned base = col_offsets[0];
-    std::vector<i64> cp((size_t)ncols_local + 1);
-    for (int64_t c = 0; c <= ncols_local; ++c) {
-        if (c > 0 && col_offsets[c] < col_offsets[c - 1]) { set_error("col_offsets not monotone"); return SMK_BAD_PARAM; }
-        cp[(size_t)c] = (i64)col_offsets[c] - base;
-    }
-    for (int64_t p = 0; p < nnz; ++p)
-        if ((int64_t)row_indices[base + p] >= height) { set_error("row index out of range"); return SMK_BAD_PARAM; }
-    smk_matrix* a = new smk_matrix;
-    a->m = height; a->n_global = width_global; a->c0 = col0; a->n = ncols_local; a->storage = SMK_STORE_F32;
-    a->sparse = true; a->nnz = nnz;
-    a->st = g_stream;
-    register_matrix(a);
-    int rc = 0;
-    rc |= dev_alloc(&a->colptr, (size_t)ncols_local + 1);
-    rc |= dev_alloc(&a->colptr_t, (size_t)height + 1);
-    rc |= dev_alloc(&a->rowidx, (size_t)nnz);
-    rc |= dev_alloc(&a->rowidx_t, (size_t)nnz);
-    rc |= dev_alloc(&a->val, (size_t)nnz);
-    rc |= dev_alloc(&a->val_t, (size_t)nnz);
-    if (rc) { smk_matrix_destroy(a); return SMK_DEVICE_ERROR; }
-    hipError_t e = hipMemcpy(a->colptr, cp.data(), cp.size() * sizeof(i64), hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz > 0) e = hipMemcpy(a->rowidx, row_indices + base, (size_t)nnz * sizeof(unsigned), hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz > 0) e = hipMemcpy(a->val, data + base, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice);
-    // the transpose: a stable radix sort by row on the device (sort.hip) -- the entry order of the host counting sort --
-    // or, if that is not available (SMK_TRANSPOSE=host forces it), the host routine and a second upload
-    static const bool host_tr = [] { const char* ev = getenv("SMK_TRANSPOSE"); return ev && ev[0] == 'h'; }();
-    bool done = false;
-    if (e == hipSuccess && !host_tr)
-        done = device_csc_transpose(height, ncols_local, nnz, a->colptr, a->rowidx, a->val, a->colptr_t, a->rowidx_t, a->val_t, g_stream) == 0;
-    if (e == hipSuccess && !done) {
-        std::vector<unsigned> rit((size_t)(nnz > 0 ? nnz : 1)), cpt32((size_t)height + 1);
-        std::vector<double> vt((size_t)(nnz > 0 ? nnz : 1));
-        const int trc = smk_csc_transpose(height, ncols_local, col_offsets, row_indices, data, cpt32.data(), rit.data(), vt.data());
-        if (trc != SMK_OK) { smk_matrix_destroy(a); return trc; }
-        std::vector<i64> cpt((size_t)height + 1);
-        for (int64_t r = 0; r <= height; ++r) cpt[(size_t)r] = cpt32[(size_t)r];
-        e = hipMemcpy(a->colptr_t, cpt.data(), cpt.size() * sizeof(i64), hipMemcpyHostToDevice);
-        if (e == hipSuccess && nnz > 0) e = hipMemcpy(a->rowidx_t, rit.data(), (size_t)nnz * sizeof(unsigned), hipMemcpyHostToDevice);
-        if (e == hipSuccess && nnz > 0) e = hipMemcpy(a->val_t, vt.data(), (size_t)nnz * sizeof(double), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        set_error(std::string("hipMemcpy(CSC): ") + hipGetErrorString(e));
-        smk_matrix_destroy(a);
-        return SMK_DEVICE_ERROR;
-    }
-    *out = a;
-    return SMK_OK;
-}
-
-// preprocess.cpp: the resident matrix of a preprocessing result, filled on the device by `fill` (CSC with 64-bit offsets, on the
-// context stream) and its transpose built as smk_matrix_create_sparse builds it -- the same matrix as one created from the
-// downloaded arrays
-extern "C++" {
-namespace smk {
-int matrix_create_sparse_device(smk_matrix** out, i64 height, i64 width, i64 nnz,
-                                const std::function<int(i64* colptr, unsigned* rowidx, double* val, hipStream_t st)>& fill)
-{
-    if (!out) return SMK_BAD_PARAM;
-    *out = nullptr;
-    if (!g_init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
-    if (height <= 0 || width <= 0 || nnz < 0) { set_error("empty matrix"); return SMK_BAD_PARAM; }
-    smk_matrix* a = new smk_matrix;
-    a->m = height; a->n_global = width; a->c0 = 0; a->n = width; a->storage = SMK_STORE_F32;
-    a->sparse = true; a->nnz = nnz;
-    a->st = g_stream;
-    register_matrix(a);
-    int rc = 0;
-    rc |= dev_alloc(&a->colptr, (size_t)width + 1);
-    rc |= dev_alloc(&a->colptr_t, (size_t)height + 1);
-    rc |= dev_alloc(&a->rowidx, (size_t)nnz);
-    rc |= dev_alloc(&a->rowidx_t, (size_t)nnz);
-    rc |= dev_alloc(&a->val, (size_t)nnz);
-    rc |= dev_alloc(&a->val_t, (size_t)nnz);
-    if (rc) { smk_matrix_destroy(a); return SMK_DEVICE_ERROR; }
-    if (fill(a->colptr, a->rowidx, a->val, g_stream) != 0 ||
-        device_csc_transpose(height, width, nnz, a->colptr, a->rowidx, a->val, a->colptr_t, a->rowidx_t, a->val_t, g_stream) != 0) {
-        smk_matrix_destroy(a);
-        return SMK_DEVICE_ERROR;
-    }
-    const hipError_t e = hipStreamSynchronize(g_stream);
-    if (e != hipSuccess) {
-        set_error(std::string("resident CSC: ") + hipGetErrorString(e));
-        smk_matrix_destroy(a);
-        return SMK_DEVICE_ERROR;
-    }
-    *out = a;
-    return SMK_OK;
-}
-
-hipStream_t context_stream(bool* initialized)
-{
-    if (initialized) *initialized = g_init;
-    return g_stream;
-}
-}  // namespace smk
-}  // extern "C++"
-
-// host copy of a resident CSC (32-bit offsets), fetched on first use: only column subsets whose list is not strictly
-// increasing are cut on the host
-static int ensure_host_csc(const smk_matrix* a)
-{
-    if (!a->h_colptr.empty()) return SMK_OK;
-    a->h_colptr.resize((size_t)a->n + 1);
-    a->h_rowidx.resize((size_t)(a->nnz > 0 ? a->nnz : 1));
-    a->h_val.resize((size_t)(a->nnz > 0 ? a->nnz : 1));
-    const int rc = smk_matrix_download_csc(a, 0, a->h_colptr.data(), a->h_rowidx.data(), a->h_val.data());
-    if (rc != SMK_OK) { a->h_colptr.clear(); return rc; }
-    return SMK_OK;
-}
-
-// Column subset of a resident matrix as a new matrix (HierNMF2 node, SubMatrixColsCompact).
-// Dense (dense_matrix_impl.hpp:224-281): all rows kept, columns gathered HBM -> HBM, transpose rebuilt
-// on the device.  Sparse (sparse_matrix_impl.hpp:479-590): rows without a stored entry in the selected
-// columns are dropped; the cut is made on the host copy of the CSC and uploaded.
-int smk_matrix_gather_cols(const smk_matrix* src, const unsigned* cols, int64_t ncols, smk_matrix** out,
-                           unsigned* new_to_old_rows, int64_t* new_height)
-{
-    if (!out) return SMK_BAD_PARAM;
-    *out = nullptr;
-    if (!src || !cols || ncols <= 0) { set_error("SubMatrixColsCompact: empty column set"); return SMK_BAD_PARAM; }
-    for (int64_t j = 0; j < ncols; ++j)
-        if ((i64)cols[j] >= src->n) { set_error("SubMatrixColsCompact: column index out of range"); return SMK_BAD_PARAM; }
-    if (!src->sparse) {
-        smk_matrix* a = nullptr;
-        int rc = smk_matrix_create(&a, src->m, ncols, 0, ncols, src->storage);
-        if (rc) return rc;
-        unsigned* dcols = nullptr;
-        rc = dev_alloc(&dcols, (size_t)ncols);
-        if (rc) { smk_matrix_destroy(a); return rc; }
-        const i64 es = elem_size(src->storage);
-        hipError_t e = hipMemcpyAsync(dcols, cols, (size_t)ncols * sizeof(unsigned), hipMemcpyHostToDevice, g_stream);
-        if (e == hipSuccess) {
-            rc = launch_gather_cols(src->A, src->ldA * es, dcols, ncols, a->A, a->ldA * es, src->ldA * es, g_stream);
-            if (!rc) rc = matrix_make_transpose(a);
-            if (!rc) e = hipStreamSynchronize(g_stream);
-        }
-        (void)smk::dev_free(dcols);
-        if (e != hipSuccess) { set_error(std::string("gather_cols: ") + hipGetErrorString(e)); rc = SMK_DEVICE_ERROR; }
-        if (rc) { smk_matrix_destroy(a); return rc; }
-        if (new_to_old_rows) for (i64 r = 0; r < src->m; ++r) new_to_old_rows[r] = (unsigned)r;
-        if (new_height) *new_height = src->m;
-        *out = a;
-        return SMK_OK;
-    }
-    // strictly increasing column lists (every HierNMF2 document list): cut on the device, nothing but
-    // the row map crosses PCIe (sparse_subset.hip).  SMK_SPARSE_SUBSET=host forces the host cut below.
-    bool increasing = true;
-    for (int64_t j = 1; j < ncols && increasing; ++j) increasing = cols[j] > cols[j - 1];
-    static const bool force_host = [] { const char* e = getenv("SMK_SPARSE_SUBSET"); return e && e[0] == 'h'; }();
-    if (increasing && !force_host) {
-        SparseDev sd, od;
-        sd.m = src->m; sd.n = src->n; sd.nnz = src->nnz;
-        sd.colptr = src->colptr; sd.rowidx = src->rowidx; sd.val = src->val;
-        sd.colptr_t = src->colptr_t; sd.rowidx_t = src->rowidx_t; sd.val_t = src->val_t;
-        std::vector<unsigned> n2o_tmp;
-        unsigned* n2o = new_to_old_rows;
-        if (!n2o) { n2o_tmp.resize((size_t)src->m); n2o = n2o_tmp.data(); }
-        const int rc = device_sparse_subset(sd, cols, ncols, &od, n2o, g_stream);
-        if (rc) return rc == -3 ? SMK_BAD_PARAM : SMK_DEVICE_ERROR;
-        smk_matrix* a = new smk_matrix;
-        a->m = od.m; a->n_global = ncols; a->c0 = 0; a->n = ncols; a->storage = SMK_STORE_F32;
-        a->sparse = true; a->nnz = od.nnz;
-        a->st = g_stream;
-        register_matrix(a);
-        a->colptr = od.colptr; a->rowidx = od.rowidx; a->val = od.val;
-        a->colptr_t = od.colptr_t; a->rowidx_t = od.rowidx_t; a->val_t = od.val_t;
-        if (new_height) *new_height = od.m;
-        *out = a;
-        return SMK_OK;
-    }
-    int64_t nh = 0, nz = 0;
-    int rc = ensure_host_csc(src);
-    if (rc != SMK_OK) return rc;
-    rc = smk_csc_subset_cols_compact(src->m, src->n, src->h_colptr.data(), src->h_rowidx.data(), src->h_val.data(), cols,
-                                         ncols, nullptr, nullptr, nullptr, nullptr, nullptr, &nh, &nz);
-    if (rc != SMK_OK) return rc;
-    std::vector<unsigned> cp((size_t)ncols + 1), ri((size_t)nz);
-    std::vector<double> va((size_t)nz);
-    rc = smk_csc_subset_cols_compact(src->m, src->n, src->h_colptr.data(), src->h_rowidx.data(), src->h_val.data(), cols,
-                                     ncols, cp.data(), ri.data(), va.data(), nullptr, new_to_old_rows, &nh, &nz);
-    if (rc != SMK_OK) return rc;
-    if (new_height) *new_height = nh;
-    return smk_matrix_create_sparse(out, nh, ncols, 0, ncols, nz, cp.data(), ri.data(), va.data());
-}
-
-// ------------------------------------------------------------------------------------------
-// solver
-// ------------------------------------------------------------------------------------------
 static PartialView view1(const smk_solver* s)
 {
     return PartialView{s->P1, s->pl1.S, (i64)s->pl1.ncols_pad * s->kpp, s->kpp, 1};
@@ -1075,53 +73,6 @@ static size_t comm_bytes(const smk_solver* s)
     return b;
 }
 
-// One pass over a dense A at HBM rate, once per matrix contents: the column maxima of |A| give
-//   ascale          power of two with max |A| ascale in [2^13, 2^14) (fp16 two-term products; 1 for an all-zero matrix)
-//   col_spread_log2 log2 of (largest / smallest non-zero column maximum): how far apart the column scales are
-static int matrix_measure_scale(const smk_matrix* a, hipStream_t st)
-{
-    unsigned* d = nullptr;
-    SMK_HIP(smk::dev_malloc((void**)&d, 2 * sizeof(unsigned)));
-    unsigned bits[2] = {0, 0};
-    int rc = launch_colrange(a->A, a->storage, a->ldA, a->m, a->n, d, st);
-    if (!rc && hipMemcpyAsync(bits, d, sizeof(bits), hipMemcpyDeviceToHost, st) != hipSuccess) rc = SMK_DEVICE_ERROR;
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = SMK_DEVICE_ERROR;
-    (void)smk::dev_free(d);
-    if (rc) { set_error("could not measure max |A|"); return rc; }
-    float mx, mn;
-    memcpy(&mx, &bits[0], sizeof(mx));
-    memcpy(&mn, &bits[1], sizeof(mn));
-    float sc = 1.f;
-    int spread = 0;
-    if (mx > 0.f && std::isfinite(mx)) {
-        int ex = 0;
-        (void)frexpf(mx, &ex);                     // mx = f 2^ex, f in [0.5, 1)
-        sc = ldexpf(1.f, 14 - ex);
-        if (bits[1] != 0xFFFFFFFFu && mn > 0.f) { int en = 0; (void)frexpf(mn, &en); spread = ex - en; }
-    }
-    a->ascale = sc;
-    a->col_spread_log2 = spread;
-    return 0;
-}
-
-// One pass over A and one over A' at HBM rate, once per matrix contents: the largest 2-norm of a column and of a row
-// (what bounds the NNLS solutions from above, NnlsPack)
-static int matrix_measure_norms(const smk_matrix* a, hipStream_t st)
-{
-    double* d = nullptr;
-    SMK_HIP(smk::dev_malloc((void**)&d, 2 * sizeof(double)));
-    double v[2] = {0.0, 0.0};
-    int rc = launch_colnorm2_max(a->A, a->storage, a->ldA, a->m, a->n, d, st);
-    if (!rc) rc = launch_colnorm2_max(a->At, a->storage, a->ldAt, a->n, a->m, d + 1, st);
-    if (!rc && hipMemcpyAsync(v, d, sizeof(v), hipMemcpyDeviceToHost, st) != hipSuccess) rc = SMK_DEVICE_ERROR;
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = SMK_DEVICE_ERROR;
-    (void)smk::dev_free(d);
-    if (rc) { set_error("could not measure the column / row norms of A"); return rc; }
-    a->colnorm_max = std::sqrt(v[0]);
-    a->rownorm_max = std::sqrt(v[1]);
-    return 0;
-}
-
 // What the transposed-source kernels cover: MU, HALS and BPP with the 16-bit product forms (the reference's BPP keeps a transpose
 // itself, nmf_solver_bpp.hpp:319 -- its W-side right-hand side H A' is the same product as MU's and HALS's, so it does not have
 // to; RANK2 and the accurate form contract down the contiguous direction of A' on the vector ALUs / fp64 matrix cores).
@@ -1148,13 +99,13 @@ static int plan_products(smk_solver* s)
         const int trc = matrix_materialize_transpose(a);
         if (trc) return trc;
     }
-    s->ng = plan_bigprod_groups(a->storage, s->k, s->m, s->n, s->nsplit, g_cus, s->pg1);
+    s->ng = plan_bigprod_groups(a->storage, s->k, s->m, s->n, s->nsplit, ctx().cus, s->pg1);
     if (a->single) {                                                                                        // H*A' from A itself
-        if (plan_bigprod_groups_tr(a->storage, s->k, s->n, s->m, s->nsplit, g_cus, s->pg2) < 0) {
+        if (plan_bigprod_groups_tr(a->storage, s->k, s->n, s->m, s->nsplit, ctx().cus, s->pg2) < 0) {
             set_error("no transposed-source kernel for this product form");
             return SMK_UNSUPPORTED;
         }
-    } else (void)plan_bigprod_groups(a->storage, s->k, s->n, s->m, s->nsplit, g_cus, s->pg2);
+    } else (void)plan_bigprod_groups(a->storage, s->k, s->n, s->m, s->nsplit, ctx().cus, s->pg2);
     if (s->nsplit == NSPLIT_F64)
         for (int g = 0; g < s->ng; ++g) { s->pg1[g].ldx = s->KP; s->pg2[g].ldx = s->KP; }
     {
@@ -1212,7 +163,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
 {
     if (!out) return SMK_BAD_PARAM;
     *out = nullptr;
-    if (!g_init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
     if (!opts || !a) return SMK_BAD_PARAM;
     if (!smk_is_valid(opts, 1)) return SMK_BAD_PARAM;
     if (opts->height != a->m || opts->width != a->n_global) { set_error("options/matrix dimension mismatch"); return SMK_BAD_PARAM; }
@@ -1222,7 +173,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
     if ((uint64_t)a->n_global * (uint64_t)opts->k > 0x7FFFFFFFull) { fprintf(stderr, "H matrix size too large\n"); return SMK_SIZE_TOO_LARGE; }
 
     smk_solver* s = new smk_solver;
-    ++g_live_solvers;
+    ++ctx().live_solvers;
     s->o = *opts;
     s->a = a;
     s->k = opts->k;
@@ -1230,7 +181,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
     s->kpp = kpp_of(s->k);
     s->m = a->m;
     s->n = a->n;
-    s->st = a->st ? a->st : g_stream;
+    s->st = a->st ? a->st : ctx().stream;
     const char* env = getenv("SMK_NSPLIT");
     // fp32 A: the fp16 two-term form (3 MFMAs per product, 2^-22 operand error) unless SMK_NSPLIT picks the bf16 forms
     // (3 = bf16x3, 6 MFMAs, power-bound; 2 = two bf16 terms, 2^-16); bf16 A: three bf16 terms of the factor
@@ -1272,7 +223,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
     // Column scales of A more than 2^28 apart: the small columns fall below what fp32-class products resolve next to the
     // large ones (HALS / BPP leave the bar at 2^+-20, tests/test_gpu_parity.py) -- the accurate form as well.
     if (!env && !a->sparse && opts->algorithm != SMK_ALG_RANK2) {
-        if (a->col_spread_log2 < 0) { const int rc0 = matrix_measure_scale(a, a->st ? a->st : g_stream); if (rc0) { --g_live_solvers; delete s; return rc0; } }
+        if (a->col_spread_log2 < 0) { const int rc0 = matrix_measure_scale(a, a->st ? a->st : ctx().stream); if (rc0) { --ctx().live_solvers; delete s; return rc0; } }
         if (a->col_spread_log2 > 28) nsplit_default = NSPLIT_F64;
     }
     s->nsplit = env ? atoi(env) : nsplit_default;
@@ -1291,7 +242,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
             if (!a->blocked_tried) {
                 a->blocked_tried = true;
                 const int b1 = blocked_csc_blocks(a->m), b2 = blocked_csc_blocks(a->n);
-                hipStream_t bst = a->st ? a->st : g_stream;
+                hipStream_t bst = a->st ? a->st : ctx().stream;
                 if (b1 > 1) (void)build_blocked_csc(a->m, a->n, a->nnz, a->colptr, a->rowidx, a->val, b1, &a->bA, bst);
                 if (b2 > 1) (void)build_blocked_csc(a->n, a->m, a->nnz, a->colptr_t, a->rowidx_t, a->val_t, b2, &a->bAt, bst);
             }
@@ -1352,7 +303,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
     }
     if (opts->algorithm == SMK_ALG_BPP) {
         // k <= 128: two (inverse + selector) halves; above: one Cholesky panel per resident workgroup (wide.hip)
-        rc |= dev_alloc(&s->nnls_scratch, nnls_uses_tiles(s->k) ? nnls_wide_scratch_elems(s->k, g_cus, std::max(s->m, s->n)) : 2 * nnls_scratch_elems(s->k));
+        rc |= dev_alloc(&s->nnls_scratch, nnls_uses_tiles(s->k) ? nnls_wide_scratch_elems(s->k, ctx().cus, std::max(s->m, s->n)) : 2 * nnls_scratch_elems(s->k));
         if (s->KP == 64 && !nnls_uses_tiles(s->k)) rc |= dev_alloc(&s->nnls_defer, nnls_defer_elems(std::max(s->m, s->n)));
         // (above k = 128 the inverse stays in stream order: beside the product it gained 1-2 % -- measured -- and the two sides
         // share one scratch there)
@@ -1421,7 +372,7 @@ void smk_solver_destroy(smk_solver* s)
         if (s->ev_r[j]) (void)hipEventDestroy(s->ev_r[j]);
         if (s->ev_a[j]) (void)hipEventDestroy(s->ev_a[j]);
     }
-    --g_live_solvers;
+    --ctx().live_solvers;
     delete s;
 }
 
@@ -1901,7 +852,7 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
             riders = true;
         }
     }
-    const int rc = launch_nnls_bpp(X, nullptr, s->k, c0, c1, R, G, s->fail_flag, s->iter, inv_scratch(s, side), s->inv_done[side] ? 1 : 0, g_cus, s->st,
+    const int rc = launch_nnls_bpp(X, nullptr, s->k, c0, c1, R, G, s->fail_flag, s->iter, inv_scratch(s, side), s->inv_done[side] ? 1 : 0, ctx().cus, s->st,
                                    want ? s->gram_scratch : nullptr, want ? &s->nnls_gram_nblk[side] : nullptr, pack ? &pk : nullptr, s->nnls_defer,
                                    riders ? &rd : nullptr);
     if (!rc && rd.pg_part) {
@@ -2392,7 +1343,7 @@ static int solver_iteration(smk_solver* s)
                 eph.pack_out = (unsigned char*)s->packH; eph.nq = round_up(s->n, 128) / 16;
             }
             rc = wait_r2(s);  if (rc) return rc;
-            rc = launch_hals_w_update(s->Wt, s->k, s->m, r2, s->Gh, s->hals_scratch, g_cus, s->fail_flag, s->hals_calls++, s->hals_multi ? 1 : 0, s->st,
+            rc = launch_hals_w_update(s->Wt, s->k, s->m, r2, s->Gh, s->hals_scratch, ctx().cus, s->fail_flag, s->hals_calls++, s->hals_multi ? 1 : 0, s->st,
                                       ep_ok ? &epw : nullptr); if (rc) return rc;
             if (epw.done) { rc = launch_gram_reduce(s->gram_scratch, epw.nblk, s->k, s->Gw, s->st, nullptr, nullptr, 1.0); s->packed_fresh[0] = true; }
             else rc = gram_w(s);
@@ -2897,7 +1848,7 @@ static int guard_enqueue(smk_solver* s)
         rc = launch_gather_cols(s->a->A, s->a->ldA * es, s->guard_cols, nc, s->guard_As, s->a->ldA * es, s->a->ldA * es, s->st);
         if (rc) return rc;
         SMK_HIP(hipStreamSynchronize(s->st));              // `cols` leaves scope
-        const int ng = plan_bigprod_groups(s->a->storage, s->k, s->m, nc, NSPLIT_F64, g_cus, s->guard_pl);
+        const int ng = plan_bigprod_groups(s->a->storage, s->k, s->m, nc, NSPLIT_F64, ctx().cus, s->guard_pl);
         for (int g = 0; g < ng; ++g) s->guard_pl[g].ldx = s->KP;
         if (dev_alloc(&s->guard_P, s->guard_pl[0].p_elems)) return SMK_DEVICE_ERROR;
         SMK_HIP(hipHostMalloc((void**)&s->guard_pin, (2 + 2 * kk) * sizeof(double)));
@@ -3053,7 +2004,7 @@ static bool rank2_persist_eligible(const smk_solver* s)
     if (g_r2p_off_devices.load(std::memory_order_relaxed) & (1ull << (smk_current_device() & 63))) return false;
     if (s->o.algorithm != SMK_ALG_RANK2 || !s->a->sparse || s->o.prog_est_algorithm != SMK_PROG_PG_RATIO) return false;
     if (is_dist(s) || s->comm || s->o.verbose || s->timing || !s->Hc || !s->Wc) return false;
-    if (rank2_persist_workgroups(s->m, s->n, s->a->nnz, g_cus) < 1) return false;      // more than 4096 rows per workgroup
+    if (rank2_persist_workgroups(s->m, s->n, s->a->nnz, ctx().cus) < 1) return false;      // more than 4096 rows per workgroup
     return s->a->nnz <= max_nnz || mode == 2;
 }
 
@@ -3061,7 +2012,7 @@ static bool rank2_persist_eligible(const smk_solver* s)
 // failure flag is set as the launch-per-kernel loop sets it), ABORTED (nothing was touched: the caller runs the classic loop)
 static int rank2_persist_run(smk_solver* s, int* status, int* count)
 {
-    const int nwg = rank2_persist_workgroups(s->m, s->n, s->a->nnz, g_cus);
+    const int nwg = rank2_persist_workgroups(s->m, s->n, s->a->nnz, ctx().cus);
     if (nwg < 1 || nwg > 1024) { *status = R2P_ABORTED; return 0; }
     // TEST HOOK: behave as if the kernel's workgroups had not all become resident (the caller must then finish the run on the
     // launch-per-kernel loop from the state solver.Init left)
@@ -3324,7 +2275,7 @@ int smk_solver_nnls_hals(smk_solver* s, double tol, int verbose, int max_iter, i
 int smk_nnls_blockpivot(int k, int64_t ncols, const double* LHS, int64_t ldL, const double* RHS, int64_t ldR, double* X,
                         int64_t ldX, double* Y, int64_t ldY)
 {
-    if (!g_init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
     if (k <= 0 || ncols <= 0 || !LHS || !RHS || !X || ldL < k || ldR < k || ldX < k || (Y && ldY < k)) return SMK_BAD_PARAM;
     if (k > MAX_K_BPP) { set_error("device path supports k <= 2048"); return SMK_UNSUPPORTED; }
     const int KP = kp_of(k);
@@ -3343,26 +2294,26 @@ int smk_nnls_blockpivot(int k, int64_t ncols, const double* LHS, int64_t ldL, co
     rc |= dev_alloc(&dr, hr.size());
     rc |= dev_alloc(&dx, hx.size());
     rc |= dev_alloc(&dy, hx.size());
-    rc |= dev_alloc(&dscratch, nnls_uses_tiles(k) ? nnls_wide_scratch_elems(k, g_cus, ncols) : nnls_scratch_elems(k));
+    rc |= dev_alloc(&dscratch, nnls_uses_tiles(k) ? nnls_wide_scratch_elems(k, ctx().cus, ncols) : nnls_scratch_elems(k));
     rc |= dev_alloc(&dflag, (size_t)1);
     unsigned* ddefer = nullptr;
     if (KP == 64 && !nnls_uses_tiles(k)) rc |= dev_alloc(&ddefer, nnls_defer_elems(ncols));
     struct Free { std::vector<void*> p; ~Free() { for (void* q : p) if (q) (void)smk::dev_free(q); } } guard{{dg, dr, dx, dy, dscratch, dflag, ddefer}};
     if (rc) return SMK_DEVICE_ERROR;
     const int big = INT_MAX;
-    SMK_HIP(hipMemcpyAsync(dg, hg.data(), hg.size() * sizeof(double), hipMemcpyHostToDevice, g_stream));
-    SMK_HIP(hipMemcpyAsync(dr, hr.data(), hr.size() * sizeof(double), hipMemcpyHostToDevice, g_stream));
-    SMK_HIP(hipMemcpyAsync(dx, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice, g_stream));
-    SMK_HIP(hipMemsetAsync(dy, 0, hx.size() * sizeof(double), g_stream));
-    SMK_HIP(hipMemcpyAsync(dflag, &big, sizeof(int), hipMemcpyHostToDevice, g_stream));
+    SMK_HIP(hipMemcpyAsync(dg, hg.data(), hg.size() * sizeof(double), hipMemcpyHostToDevice, ctx().stream));
+    SMK_HIP(hipMemcpyAsync(dr, hr.data(), hr.size() * sizeof(double), hipMemcpyHostToDevice, ctx().stream));
+    SMK_HIP(hipMemcpyAsync(dx, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice, ctx().stream));
+    SMK_HIP(hipMemsetAsync(dy, 0, hx.size() * sizeof(double), ctx().stream));
+    SMK_HIP(hipMemcpyAsync(dflag, &big, sizeof(int), hipMemcpyHostToDevice, ctx().stream));
     const PartialView pv{dr, 1, 0, KP, 1};
-    rc = launch_nnls_bpp(dx, dy, k, 0, ncols, pv, dg, dflag, 0, dscratch, 0, g_cus, g_stream, nullptr, nullptr, nullptr, ddefer);
+    rc = launch_nnls_bpp(dx, dy, k, 0, ncols, pv, dg, dflag, 0, dscratch, 0, ctx().cus, ctx().stream, nullptr, nullptr, nullptr, ddefer);
     if (rc) return rc;
     int flag = INT_MAX;
-    SMK_HIP(hipMemcpyAsync(hx.data(), dx, hx.size() * sizeof(double), hipMemcpyDeviceToHost, g_stream));
-    SMK_HIP(hipMemcpyAsync(hr.data(), dy, hx.size() * sizeof(double), hipMemcpyDeviceToHost, g_stream));
-    SMK_HIP(hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-    SMK_HIP(hipStreamSynchronize(g_stream));
+    SMK_HIP(hipMemcpyAsync(hx.data(), dx, hx.size() * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
+    SMK_HIP(hipMemcpyAsync(hr.data(), dy, hx.size() * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
+    SMK_HIP(hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
+    SMK_HIP(hipStreamSynchronize(ctx().stream));
     for (int64_t c = 0; c < ncols; ++c)
         for (int r = 0; r < k; ++r) {
             X[(size_t)c * ldX + r] = hx[(size_t)c * KP + r];
@@ -3477,7 +2428,7 @@ int smk_solver_kernel_name(const smk_solver* s, int which, char* out, int cap)
 
 int smk_debug_nnls_stats(unsigned long long* out256, int reset)
 {
-    if (!g_init) return SMK_NOTINITIALIZED;
+    if (!ctx().init) return SMK_NOTINITIALIZED;
     const int rc = nnls_stats_read(out256, reset);
     return rc == 0 ? SMK_OK : rc == -1 ? SMK_UNSUPPORTED : SMK_DEVICE_ERROR;
 }
@@ -3494,37 +2445,6 @@ int smk_solver_kernel_work(const smk_solver* s, int which, double* bytes, double
     if (bytes) *bytes = mn * elem_size(s->a->storage);
     if (flops) *flops = 2.0 * mn * s->k / s->ng;      // per launch: k > 64 streams the matrix once per group of 64 rows
     return SMK_OK;
-}
-
-// Result Nmf(...), common/src/nmf.cpp:173-229
-int smk_nmf_dense(const smk_options* opts, const double* A, int64_t ldA, double* W, int64_t ldW, double* H,
-                  int64_t ldH, smk_stats* stats, int storage)
-{
-    if (!g_init) {
-        fprintf(stderr, "nmflib error: nmf_initialize() must be called prior to any factorization routine\n\n");
-        return SMK_NOTINITIALIZED;
-    }
-    if (!opts || !smk_is_valid(opts, 1)) return SMK_BAD_PARAM;
-    if (!A || !W || !H) return SMK_BAD_PARAM;
-    if (opts->k > MAX_K || (opts->algorithm == SMK_ALG_BPP && opts->k > MAX_K_BPP)) { set_error("device path supports k <= 2048"); return SMK_UNSUPPORTED; }     // before anything is uploaded
-    const int64_t m = opts->height, n = opts->width;
-    if (ldA < m || ldW < m || ldH < opts->k) { set_error("leading dimension too small"); return SMK_BAD_PARAM; }
-    smk_matrix* a = nullptr;
-    smk_solver* s = nullptr;
-    int rc = smk_matrix_create(&a, m, n, 0, n, storage);
-    if (rc == SMK_OK) rc = smk_matrix_upload_f64(a, A, ldA);
-    if (rc == SMK_OK) rc = smk_solver_create(&s, opts, a);
-    if (rc == SMK_OK) rc = smk_solver_set_factors(s, W, ldW, H, ldH);
-    int run_rc = SMK_OK;
-    if (rc == SMK_OK) {
-        run_rc = smk_solver_run(s, stats);
-        // like the reference, W/H hold the last iterate even when the solver reports failure
-        if (run_rc == SMK_OK || run_rc == SMK_FAILURE) (void)smk_solver_get_factors(s, 0, W, ldW, H, ldH);
-        rc = run_rc;
-    }
-    smk_solver_destroy(s);
-    smk_matrix_destroy(a);
-    return rc;
 }
 
 // Result Nmf(...) on `nshards` column shards of A, one host thread + one HIP device per shard: A and H
@@ -3601,7 +2521,7 @@ int smk_nmf_dense_sharded(const smk_options* opts, const double* A, int64_t ldA,
                 (void)smk_solver_get_factors(s, 0, r == 0 ? W : Wl.data(), r == 0 ? ldW : m, H + (size_t)c0 * ldH, ldH);
             }
         }
-        errs[(size_t)r] = g_err;
+        errs[(size_t)r] = smk_last_error();
         smk_solver_destroy(s);
         smk_matrix_destroy(a);
         smk_finalize();
@@ -3618,34 +2538,6 @@ int smk_nmf_dense_sharded(const smk_options* opts, const double* A, int64_t ldA,
         if (rcs[(size_t)r] != SMK_OK && result == SMK_OK) { result = rcs[(size_t)r]; set_error(errs[(size_t)r]); }
     if (stats) *stats = sts[0];
     return result;
-}
-
-// Result NmfSparse(...), common/src/nmf.cpp:232-300 (CSC input, 32-bit indices as in the reference)
-int smk_nmf_sparse(const smk_options* opts, unsigned height, unsigned width, unsigned nz, const unsigned* col_offsets,
-                   const unsigned* row_indices, const double* data, double* W, int64_t ldW, double* H, int64_t ldH,
-                   smk_stats* stats)
-{
-    if (!g_init) {
-        fprintf(stderr, "nmflib error: nmf_initialize() must be called prior to any factorization routine\n\n");
-        return SMK_NOTINITIALIZED;
-    }
-    if (!opts || !smk_is_valid(opts, 1)) return SMK_BAD_PARAM;
-    if (!col_offsets || !row_indices || !data || !W || !H) return SMK_BAD_PARAM;
-    if (opts->k > MAX_K || (opts->algorithm == SMK_ALG_BPP && opts->k > MAX_K_BPP)) { set_error("device path supports k <= 2048"); return SMK_UNSUPPORTED; }
-    if ((int64_t)height != opts->height || (int64_t)width != opts->width) return SMK_BAD_PARAM;
-    if (ldW < opts->height || ldH < opts->k) { set_error("leading dimension too small"); return SMK_BAD_PARAM; }
-    smk_matrix* a = nullptr;
-    smk_solver* s = nullptr;
-    int rc = smk_matrix_create_sparse(&a, height, width, 0, width, nz, col_offsets, row_indices, data);
-    if (rc == SMK_OK) rc = smk_solver_create(&s, opts, a);
-    if (rc == SMK_OK) rc = smk_solver_set_factors(s, W, ldW, H, ldH);
-    if (rc == SMK_OK) {
-        rc = smk_solver_run(s, stats);
-        if (rc == SMK_OK || rc == SMK_FAILURE) (void)smk_solver_get_factors(s, 0, W, ldW, H, ldH);
-    }
-    smk_solver_destroy(s);
-    smk_matrix_destroy(a);
-    return rc;
 }
 
 }  // extern "C"

@@ -1,9 +1,11 @@
 // tests/asan/stub_device.cpp -- TEST INFRASTRUCTURE ONLY.
-// A host-only stand-in for the device half of libsmallk_amd (solver.cpp + the .hip files) so that the ~4000 lines of
-// host C++ above it -- facade.cpp (namespace smallk, ::Nmf, CSV / MatrixMarket I/O, flat API), hierclust.cpp (tree
-// search, priority scores, writers), flatclust.cpp and the three command line tools -- can be compiled with
-// -fsanitize=address,undefined and run on a machine without a GPU (tests/asan/Makefile, tests/test_asan_host.py).
-// Every factorisation is delegated to the CPU oracle (oracle/nmf_oracle.c); nothing here ships in the product.
+// A host-only stand-in for the device half of libsmallk_amd (context.cpp, matrix.cpp, solver.cpp + the .hip files) so
+// that the ~4000 lines of host C++ above it -- facade.cpp (namespace smallk, ::Nmf, CSV / MatrixMarket I/O, flat API),
+// hierclust.cpp (tree search, priority scores, writers), flatclust.cpp, the three command line tools -- and the host-only
+// part of the C ABI beside it (host_abi.cpp: validation, generator, CSC bookkeeping, one-call drivers, error string) can
+// be compiled with -fsanitize=address,undefined and run on a machine without a GPU (tests/asan/Makefile,
+// tests/test_asan_host.py).  Every factorisation is delegated to the CPU oracle (oracle/nmf_oracle.c); nothing here
+// ships in the product.
 #include "../../include/smallk_amd.h"
 #include "../../smallk_amd/csrc/common.h"
 
@@ -24,10 +26,8 @@ void orc_fill_uniform(double* buf, int64_t ld, int64_t rows, int64_t cols, int64
 int orc_normalize_and_scale(int64_t m, int64_t n, int k, double* W, int64_t ldw, double* H, int64_t ldh);
 }
 
-static thread_local std::string g_err;
 static bool g_init = false;
 namespace smk {
-void set_error(const std::string& m) { g_err = m; }
 int device_sort_desc(const double* const*, int* const*, double* const*, int, i64, hipStream_t) { return -1; }   // host sorts
 int device_priority_score(const double*, const double*, i64, i64, double*, hipStream_t) { return -1; }          // host arithmetic
 void device_priority_release() {}
@@ -57,7 +57,6 @@ extern "C" {
 int smk_initialize(int) { g_init = true; return SMK_OK; }
 int smk_is_initialized(void) { return g_init ? SMK_INITIALIZED : SMK_NOTINITIALIZED; }
 void smk_finalize(void) { g_init = false; }
-const char* smk_last_error(void) { return g_err.c_str(); }
 int smk_device_cu_count(void) { return 1; }
 int smk_set_stream(void*) { return SMK_OK; }
 // a second "device" is just a second host thread here: the two-device HierNMF2 step runs under the sanitizers too
@@ -71,28 +70,6 @@ int smk_matrix_clone(const smk_matrix* src, smk_matrix** out)
     if (!src || !out) return SMK_BAD_PARAM;
     *out = new smk_matrix(*src);
     return SMK_OK;
-}
-
-int smk_is_valid(const smk_options* o, int vm)
-{   // same checks and messages as solver.cpp / nmf_options.cpp:23-112
-    if (!o) return 0;
-    if (o->k <= 0) { fprintf(stderr, "nmflib error: k-value must be a positive integer\n"); return 0; }
-    if (vm) {
-        if (o->height <= 0) { fprintf(stderr, "nmflib error: matrix height must be a positive integer\n"); return 0; }
-        if (o->width <= 0) { fprintf(stderr, "nmflib error: matrix width must be a positive integer\n"); return 0; }
-        if (o->k > o->width) { fprintf(stderr, "nmflib error: k value cannot exceed the number of columns\n"); return 0; }
-    }
-    if (o->tol <= 0.0 || o->tol >= 1.0) { fprintf(stderr, "nmflib error: tolerance must be in the interval (0.0, 1.0)\n"); return 0; }
-    if (o->min_iter <= 0 || o->max_iter <= 0 || o->tolcount <= 0) { fprintf(stderr, "nmflib error: iteration counts must be positive\n"); return 0; }
-    if (o->algorithm < 0 || o->algorithm > 3) { fprintf(stderr, "nmflib error: unknown NMF algorithm specified\n"); return 0; }
-    if (o->algorithm == SMK_ALG_RANK2 && o->k != 2) { fprintf(stderr, "nmflib error: RANK2 algorithm requires k == 2\n"); return 0; }
-    if (o->prog_est_algorithm != 0 && o->prog_est_algorithm != 1) { fprintf(stderr, "nmflib error: unknown stopping criterion specified\n"); return 0; }
-    return 1;
-}
-
-void smk_uniform_fill_host(double* buf, int64_t ld, int64_t rows, int64_t cols, int64_t r0, int64_t c0, int64_t gh, uint64_t seed, int quant)
-{
-    orc_fill_uniform(buf, ld, rows, cols, r0, c0, gh, seed, quant);
 }
 
 int smk_matrix_create(smk_matrix** out, int64_t h, int64_t wg, int64_t c0, int64_t nc, int)
@@ -121,7 +98,7 @@ int smk_matrix_create_sparse(smk_matrix** out, int64_t h, int64_t wg, int64_t c0
     a->ri.assign(ri, ri + nnz);
     a->va.assign(va, va + nnz);
     for (unsigned r : a->ri)
-        if ((int64_t)r >= h) { delete a; g_err = "row index out of range"; return SMK_BAD_PARAM; }
+        if ((int64_t)r >= h) { delete a; smk::set_error("row index out of range"); return SMK_BAD_PARAM; }
     *out = a;
     return SMK_OK;
 }
@@ -132,9 +109,9 @@ int smk_matrix_gather_cols(const smk_matrix* src, const unsigned* cols, int64_t 
 {
     if (!out) return SMK_BAD_PARAM;
     *out = nullptr;
-    if (!src || !cols || ncols <= 0) { g_err = "SubMatrixColsCompact: empty column set"; return SMK_BAD_PARAM; }
+    if (!src || !cols || ncols <= 0) { smk::set_error("SubMatrixColsCompact: empty column set"); return SMK_BAD_PARAM; }
     for (int64_t j = 0; j < ncols; ++j)
-        if ((int64_t)cols[j] >= src->n) { g_err = "SubMatrixColsCompact: column index out of range"; return SMK_BAD_PARAM; }
+        if ((int64_t)cols[j] >= src->n) { smk::set_error("SubMatrixColsCompact: column index out of range"); return SMK_BAD_PARAM; }
     smk_matrix* a = new smk_matrix;
     a->n = ncols;
     if (!src->sparse) {
@@ -148,22 +125,16 @@ int smk_matrix_gather_cols(const smk_matrix* src, const unsigned* cols, int64_t 
         *out = a;
         return SMK_OK;
     }
-    const unsigned UNUSED = 0xFFFFFFFFu;
-    std::vector<unsigned> o2n((size_t)src->m, UNUSED);
-    size_t total = 0;
-    for (int64_t j = 0; j < ncols; ++j)
-        for (unsigned p = src->cp[cols[j]]; p < src->cp[cols[j] + 1]; ++p, ++total) o2n[src->ri[p]] = 0;
-    if (total == 0) { delete a; g_err = "SparseMatrix::SubMatrixColsCompact: submatrix is the zero matrix"; return SMK_BAD_PARAM; }
-    int64_t h = 0;
-    for (int64_t r = 0; r < src->m; ++r)
-        if (o2n[(size_t)r] != UNUSED) { o2n[(size_t)r] = (unsigned)h; if (n2o) n2o[h] = (unsigned)r; ++h; }
-    a->sparse = true; a->m = h;
-    a->cp.resize((size_t)ncols + 1);
-    for (int64_t j = 0; j < ncols; ++j) {
-        a->cp[(size_t)j] = (unsigned)a->ri.size();
-        for (unsigned p = src->cp[cols[j]]; p < src->cp[cols[j] + 1]; ++p) { a->ri.push_back(o2n[src->ri[p]]); a->va.push_back(src->va[p]); }
+    int64_t h = 0, nz = 0;
+    int rc = smk_csc_subset_cols_compact(src->m, src->n, src->cp.data(), src->ri.data(), src->va.data(), cols, ncols, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr, &h, &nz);
+    if (rc == SMK_OK) {
+        a->sparse = true; a->m = h;
+        a->cp.resize((size_t)ncols + 1); a->ri.resize((size_t)nz); a->va.resize((size_t)nz);
+        rc = smk_csc_subset_cols_compact(src->m, src->n, src->cp.data(), src->ri.data(), src->va.data(), cols, ncols, a->cp.data(),
+                                         a->ri.data(), a->va.data(), nullptr, n2o, &h, &nz);
     }
-    a->cp[(size_t)ncols] = (unsigned)a->ri.size();
+    if (rc != SMK_OK) { delete a; return rc; }
     if (nh) *nh = h;
     *out = a;
     return SMK_OK;
@@ -175,7 +146,7 @@ int smk_solver_create(smk_solver** out, const smk_options* o, const smk_matrix* 
     *out = nullptr;
     if (!g_init) return SMK_NOTINITIALIZED;
     if (!smk_is_valid(o, 1)) return SMK_BAD_PARAM;
-    if (o->height != a->m || o->width != a->n) { g_err = "options/matrix dimension mismatch"; return SMK_BAD_PARAM; }
+    if (o->height != a->m || o->width != a->n) { smk::set_error("options/matrix dimension mismatch"); return SMK_BAD_PARAM; }
     smk_solver* s = new smk_solver;
     s->o = *o; s->a = a;
     *out = s;
@@ -259,40 +230,10 @@ int smk_solver_nnls_hals(smk_solver* s, double tol, int, int max_iter, int* iter
     return ok ? SMK_OK : SMK_FAILURE;
 }
 
-int smk_nmf_dense(const smk_options* o, const double* A, int64_t ldA, double* W, int64_t ldW, double* H, int64_t ldH, smk_stats* st, int)
-{
-    if (!g_init) return SMK_NOTINITIALIZED;
-    if (!o || !smk_is_valid(o, 1) || !A || !W || !H) return SMK_BAD_PARAM;
-    smk_matrix* a = nullptr;
-    smk_solver* s = nullptr;
-    int rc = smk_matrix_create(&a, o->height, o->width, 0, o->width, 0);
-    if (rc == SMK_OK) rc = smk_matrix_upload_f64(a, A, ldA);
-    if (rc == SMK_OK) rc = smk_solver_create(&s, o, a);
-    if (rc == SMK_OK) rc = smk_solver_set_factors(s, W, ldW, H, ldH);
-    if (rc == SMK_OK) { rc = smk_solver_run(s, st); if (rc == SMK_OK || rc == SMK_FAILURE) smk_solver_get_factors(s, 0, W, ldW, H, ldH); }
-    smk_solver_destroy(s);
-    smk_matrix_destroy(a);
-    return rc;
-}
 int smk_nmf_dense_sharded(const smk_options* o, const double* A, int64_t ldA, double* W, int64_t ldW, double* H, int64_t ldH,
                           smk_stats* st, int storage, int, const int*, int)
 {
     return smk_nmf_dense(o, A, ldA, W, ldW, H, ldH, st, storage);
-}
-int smk_nmf_sparse(const smk_options* o, unsigned h, unsigned w, unsigned nz, const unsigned* cp, const unsigned* ri, const double* va,
-                   double* W, int64_t ldW, double* H, int64_t ldH, smk_stats* st)
-{
-    if (!g_init) return SMK_NOTINITIALIZED;
-    if (!o || !smk_is_valid(o, 1)) return SMK_BAD_PARAM;
-    smk_matrix* a = nullptr;
-    smk_solver* s = nullptr;
-    int rc = smk_matrix_create_sparse(&a, h, w, 0, w, nz, cp, ri, va);
-    if (rc == SMK_OK) rc = smk_solver_create(&s, o, a);
-    if (rc == SMK_OK) rc = smk_solver_set_factors(s, W, ldW, H, ldH);
-    if (rc == SMK_OK) { rc = smk_solver_run(s, st); if (rc == SMK_OK || rc == SMK_FAILURE) smk_solver_get_factors(s, 0, W, ldW, H, ldH); }
-    smk_solver_destroy(s);
-    smk_matrix_destroy(a);
-    return rc;
 }
 
 }  // extern "C"

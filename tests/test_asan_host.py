@@ -1,7 +1,8 @@
-"""Host C++ of the product (facade.cpp, hierclust.cpp, flatclust.cpp, the three command line tools: ~4000 lines)
-under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  tests/asan/stub_device.cpp replaces the device
-half (solver.cpp + kernels) and delegates every factorisation to the CPU oracle, so what runs here is exactly the
-host logic: option handling, file parsing, buffer management, the HierNMF2 tree search, the result writers.
+"""Host C++ of the product (facade.cpp, hierclust.cpp, flatclust.cpp, host_abi.cpp, the three command line tools:
+~4000 lines) under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU.  tests/asan/stub_device.cpp replaces the
+device half (context.cpp, matrix.cpp, solver.cpp + kernels) and delegates every factorisation to the CPU oracle, so what
+runs here is exactly the host logic: option handling and validation, file parsing, buffer management, the CSC column
+subsets, the HierNMF2 tree search, the result writers.
 (GPU sanitizers are not available on the pool; SURVEY section 5 asks for this CPU target.)"""
 import os
 import subprocess
