@@ -2,6 +2,7 @@
 // packing of their skinny operand.  See kernels.hip for the kernel map.
 #include "devutil.h"
 #include "gram_inverse.h"
+#include "switches.h"
 #include <type_traits>
 
 namespace smk {
@@ -1876,6 +1877,17 @@ int plan_bigprod_groups(int storage, int k, i64 len, i64 ncols, int nsplit, int 
     return ng;
 }
 
+// row splits of a streaming pass: enough workgroups for >= 4 rounds over the CUs, but keep >= 8 stages per split;
+// SMK_BP_SPLITS=n asks for n instead (rounded up to a power of two, at most 64)
+static int bigprod_row_splits(i64 tiles, i64 stages, int num_cus)
+{
+    int S = 1;
+    while (tiles * S < 2 * (i64)num_cus && S < 64 && stages / (2 * S) >= 8) S *= 2;
+    const int want = sw::bp_splits();
+    if (want > 0) { S = 1; while (S < want && S < 64) S *= 2; }
+    return S;
+}
+
 // the H*A' pass of a single-copy (bf16) matrix: same geometry as the stored-transpose pass -- 128 rows of A per tile, 64 columns
 // of A per stage -- on the two kernel shapes that exist for the transposed source (k <= 32: 4 waves, 2-deep ring, two workgroups
 // per CU; k in (32, 64]: 8 compute + 4 loader waves, 3-deep)
@@ -1911,10 +1923,7 @@ int plan_bigprod_groups_tr(int storage, int k, i64 len, i64 ncols, int nsplit, i
         pl.stages = (len + pl.mb - 1) / pl.mb;
         pl.tiles = (ncols + 127) / 128;
         pl.ncols_pad = round_up(ncols, COL_PAD);
-        int S = 1;
-        while (pl.tiles * S < 2 * (i64)num_cus && S < 64 && pl.stages / (2 * S) >= 8) S *= 2;
-        const char* envS = getenv("SMK_BP_SPLITS");
-        if (envS && atoi(envS) > 0) { S = 1; while (S < atoi(envS) && S < 64) S *= 2; }
+        int S = bigprod_row_splits(pl.tiles, pl.stages, num_cus);
         if (ng > 0) S = out[0].S;
         pl.S = S;
         pl.nst = (pl.stages + S - 1) / S;
@@ -1964,10 +1973,8 @@ BigProdPlan plan_bigprod(int storage, int k, i64 len, i64 ncols, int nsplit, int
     // Short contractions are latency-bound, the extra folds cost nothing there; at C4 (len >= 65536) folding every 8 stages
     // instead of 4 is worth 0 .. 2 %.
     if (storage == STORE_F32 && pl.nsplit == NSPLIT_F16X2) v = len >= 65536 ? 125 : len >= 16384 ? 108 : len >= 4096 ? 128 : 129;
-    const char* env = getenv("SMK_BP_VARIANT");
-    if (env) v = atoi(env);
-    const char* env2 = getenv("SMK_BP_VARIANT_K64");       // only for k in (32, 64]
-    if (env2 && pl.kt == 2) v = atoi(env2);
+    if (const auto env = sw::bp_variant(); env.set) v = env.v;
+    if (const auto env2 = sw::bp_variant_k64(); env2.set && pl.kt == 2) v = env2.v;       // only for k in (32, 64]
     if (storage == STORE_F32 && pl.nsplit == 2 && v < 100) v = (pl.kt == 2) ? 108 : 115;   // the 2-term forms exist only there
     if (pl.nsplit != NSPLIT_F16X2 && (v == 128 || v == 129)) v = 108;       // the short-chain variants exist for the fp16 form only
     if (pl.nsplit == NSPLIT_F16X2 && v != 108 && v != 110 && v != 111 && v != 115 && v != 125 && v != 126 && v != 127 && v != 128 && v != 129) v = 125;
@@ -1988,10 +1995,7 @@ BigProdPlan plan_bigprod(int storage, int k, i64 len, i64 ncols, int nsplit, int
         pl.stages = (len + MB - 1) / MB;
         pl.tiles = (ncols + 127) / 128;
         pl.ncols_pad = round_up(ncols, COL_PAD);
-        int S = 1;
-        while (pl.tiles * S < 2 * (i64)num_cus && S < 64 && pl.stages / (2 * S) >= 8) S *= 2;
-        const char* envS = getenv("SMK_BP_SPLITS");
-        if (envS && atoi(envS) > 0) { S = 1; while (S < atoi(envS) && S < 64) S *= 2; }
+        const int S = bigprod_row_splits(pl.tiles, pl.stages, num_cus);
         pl.S = S;
         pl.nst = (pl.stages + S - 1) / S;
         pl.p_elems = (size_t)S * pl.ncols_pad * pl.pstride;
@@ -2014,11 +2018,7 @@ BigProdPlan plan_bigprod(int storage, int k, i64 len, i64 ncols, int nsplit, int
     pl.stages = (len + MB - 1) / MB;
     pl.tiles = (ncols + NB - 1) / NB;
     pl.ncols_pad = round_up(ncols, COL_PAD);
-    // enough workgroups for >= 4 rounds over the CUs, but keep >= 8 stages per split
-    int S = 1;
-    while (pl.tiles * S < 2 * (i64)num_cus && S < 64 && pl.stages / (2 * S) >= 8) S *= 2;
-    const char* envS = getenv("SMK_BP_SPLITS");
-    if (envS && atoi(envS) > 0) { S = 1; while (S < atoi(envS) && S < 64) S *= 2; }
+    const int S = bigprod_row_splits(pl.tiles, pl.stages, num_cus);
     pl.S = S;
     pl.nst = (pl.stages + S - 1) / S;
     pl.p_elems = (size_t)S * pl.ncols_pad * pl.pstride;   // doubles
@@ -2127,7 +2127,7 @@ template <int KT, int NSPLIT>
 static int launch_bigprod_tr_v(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
 {
     // the kernel shapes built for the transposed source (numbers = the variants of kVariants; SMK_BP_TR_VARIANT picks one)
-    static const int v = [] { const char* e = getenv("SMK_BP_TR_VARIANT"); return e ? atoi(e) : -1; }();
+    const int v = sw::bp_tr_variant();
     if constexpr (KT == 1) {
         switch (v) {
             case 0: return launch_bigprod_t<2, 1, NSPLIT, 64, 3, 1, 1, 0, true>(pl, B, ldb, Xp, P, st);

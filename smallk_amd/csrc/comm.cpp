@@ -8,6 +8,7 @@
 // (the fp64 rows only when results are read), and one 3-element all-reduce when the stopping rule is evaluated.
 #include "common.h"
 #include "comm.h"
+#include "switches.h"
 #include "../../include/smallk_amd.h"
 
 #include <rccl/rccl.h>
@@ -81,8 +82,7 @@ static int local_collective(smk_comm* c, const void* send, void* recv, i64 count
 
 bool comm_forced()
 {
-    const char* e = getenv("SMK_COMM_FORCE");       // read per call: tests switch it inside one process
-    return e && atoi(e) != 0;
+    return sw::comm_force();        // read per call: tests switch it inside one process
 }
 static inline bool skip_collective(const smk_comm* c) { return !c || (c->world == 1 && !comm_forced()); }
 

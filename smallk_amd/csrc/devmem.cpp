@@ -13,6 +13,7 @@
 //     caller receives (dev_alloc in state.h), reused or fresh;
 //   * smk_finalize / smk_thread_context_end / smk_device_trim return the cached blocks of their device (dev_trim).
 #include "common.h"
+#include "switches.h"
 
 #include <map>
 #include <mutex>
@@ -28,8 +29,7 @@ constexpr size_t MAX_CACHED_BLOCK = (size_t)512 << 20;
 // everything back before a caller creates communicators or large torch tensors
 size_t max_cached_total()
 {
-    static const size_t cap = [] { const char* e = getenv("SMK_DEVMEM_CACHE_MB"); return e ? (size_t)atoll(e) << 20 : (size_t)4 << 30; }();
-    return cap;
+    return (size_t)sw::devmem_cache_mb() << 20;
 }
 constexpr int MAX_DEVICES = 64;
 
@@ -42,8 +42,7 @@ unsigned long long g_hits = 0, g_misses = 0;
 
 bool cache_on()
 {
-    static const bool on = [] { const char* e = getenv("SMK_DEVMEM_CACHE"); return !(e && atoi(e) == 0); }();
-    return on;
+    return sw::devmem_cache() != 0;
 }
 
 size_t round_size(size_t b)

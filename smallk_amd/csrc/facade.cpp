@@ -8,6 +8,7 @@
 #include "../../include/nmf.hpp"
 #include "../../include/smallk.hpp"
 #include "../../include/smallk_amd.h"
+#include "switches.h"
 
 #include <sys/stat.h>
 #include <unistd.h>
@@ -258,11 +259,10 @@ static void requested_shards(int* shards, int* stub)
 {
     *shards = 1;
     *stub = 0;
-    const char* e = getenv("SMK_NUM_GPUS");
-    if (!e || atoi(e) <= 1) return;
-    *shards = atoi(e) > 16 ? 16 : atoi(e);
-    const char* s1 = getenv("SMK_SHARDS_ON_ONE_GPU");
-    *stub = (s1 && atoi(s1) != 0) ? 1 : 0;
+    const int want = smk::sw::num_gpus();
+    if (want <= 1) return;
+    *shards = want > 16 ? 16 : want;
+    *stub = smk::sw::shards_on_one_gpu() ? 1 : 0;
 }
 
 Result Nmf(const NmfOptions& options, double* buf_a, int ldim_a, double* buf_w, int ldim_w, double* buf_h,
@@ -400,7 +400,7 @@ void Initialize(int& /*argc*/, char**& /*argv*/)
     rng_seed = (uint64_t)std::chrono::high_resolution_clock::now().time_since_epoch().count();
     // SMALLK_SEED pins the seed for callers that cannot be changed to call SeedRNG() (the reference's own example
     // programs draw their initial factors right after Initialize)
-    if (const char* e = getenv("SMALLK_SEED")) rng_seed = (uint64_t)strtoull(e, nullptr, 10);
+    if (const auto fixed = smk::sw::seed(); fixed.set) rng_seed = fixed.v;
     rng_draws = 0;
     if (smk_initialize(-1) != SMK_OK) throw std::runtime_error(std::string("smallk error (Initialize): ") + smk_last_error());
 }

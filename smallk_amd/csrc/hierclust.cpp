@@ -14,6 +14,7 @@
 // (sort.hip).
 #include "common.h"
 #include "../../include/smallk_amd.h"
+#include "switches.h"
 
 #include <algorithm>
 #include <chrono>
@@ -215,7 +216,7 @@ double ndcg_cum(const std::vector<int>& seq, const std::vector<int>& test, const
 
 double priority_score(const double* wp, const double* wc, i64 n)
 {
-    static const bool timing = [] { const char* e = getenv("SMK_CLUST_TIMING"); return e && atoi(e) > 1; }();
+    const bool timing = smk::sw::clust_timing() > 1;
     const auto T0 = std::chrono::high_resolution_clock::now();
     auto lap = [&](const char* what) {
         if (timing) fprintf(stderr, "[priority] %s at %.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - T0).count());
@@ -230,7 +231,7 @@ double priority_score(const double* wp, const double* wc, i64 n)
     const bool on_device = n >= DEVICE_SORT_MIN && smk_is_initialized() == SMK_INITIALIZED;
     // the whole score on the device (sort.hip): three doubles come back.  SMK_PRIORITY_HOST=1 keeps the host arithmetic
     // around the device sorts (bit-identical to the reference's sequential sums; the device sums differ by rounding).
-    static const bool host_arith = [] { const char* e = getenv("SMK_PRIORITY_HOST"); return e && atoi(e) != 0; }();
+    const bool host_arith = smk::sw::priority_host();
     if (on_device && !host_arith) {
         double sc = 0.0;
         if (smk::device_priority_score(wp, wc, n, n_part, &sc, nullptr) == 0) { lap("device score done"); return sc; }
@@ -388,8 +389,7 @@ int factor_node(Run& r, const smk_matrix* a, i64 h, i64 w, const unsigned* rows,
         smk_solver_destroy(s);
         r.iterations += st.iteration_count;
         {
-            static const bool timing = [] { const char* e = getenv("SMK_CLUST_TIMING"); return e && atoi(e) != 0; }();
-            if (timing)
+            if (smk::sw::clust_timing() != 0)
                 fprintf(stderr, "[smk_clust] %s %ld x %ld nnz %ld: %d iterations in %.1f ms (%.1f us each)\n", what, (long)h, (long)w,
                         (long)smk_matrix_nnz(a), st.iteration_count, st.elapsed_us * 1e-3,
                         st.iteration_count ? (double)st.elapsed_us / st.iteration_count : 0.0);
@@ -512,8 +512,7 @@ int trial_split(Run& r, std::vector<unsigned>& subset, double min_priority, cons
 std::mutex g_serialize_mu;
 inline bool serialize_trials()
 {
-    static const bool on = [] { const char* e = getenv("SMK_CLUST_SERIALIZE"); return e && atoi(e) != 0; }();
-    return on;
+    return smk::sw::clust_serialize();
 }
 
 struct SplitTask {
@@ -605,13 +604,11 @@ struct Worker {
 std::vector<Worker*> start_workers(const Run& r)
 {
     std::vector<Worker*> out;
-    const char* e = getenv("SMK_CLUST_DEVICES");
-    if (!e || atoi(e) < 2) return out;
-    const int want = std::min(atoi(e), 8);
+    if (smk::sw::clust_devices() < 2) return out;
+    const int want = std::min(smk::sw::clust_devices(), 8);
     const int cur = smk_current_device(), ndev = smk_device_count();
     if (cur < 0 || ndev < 1) return out;
-    const char* one = getenv("SMK_SHARDS_ON_ONE_GPU");
-    const bool same = one && atoi(one) != 0;
+    const bool same = smk::sw::shards_on_one_gpu();
     const int devices = same ? want : std::min(want, ndev);
     for (int j = 0; j + 1 < devices; ++j) {
         Worker* w = new Worker;
@@ -912,13 +909,12 @@ int run_clust(const smk_clust_options* opts, smk_matrix* full, uint64_t seed, ui
     if (draws) *draws = r.draws;
     if (stats) *stats = r.stats;
     smk::device_priority_release();        // workspace of the device-side priority score (kept between the calls of a run)
-    if (const char* e = getenv("SMK_CLUST_TIMING"))
-        if (atoi(e))
-            fprintf(stderr, "[smk_clust] subset %.3fs  factor %.3fs (%ld RANK2 iterations)  priority %.3fs  init %.3fs  |  tree search %.3fs in all "
-                    "(host bookkeeping %.3fs: device frees %.3f, tree edits %.3f, labels + scatter of W %.3f, top terms + assignments %.3f, zero-filled W buffers %.3f)  flat step %.3fs  speculative steps accepted %ld of %ld; trial splits kept %.3fs, sum over rounds of the longest one %.3fs (= their time on "
-                    "SMK_CLUST_DEVICES real devices)\n",
-                    r.t_subset, r.t_factor, r.iterations, r.t_priority, r.t_init, t_search,
-                    t_search - r.t_subset - r.t_factor - r.t_priority - r.t_init, r.t_free, r.t_tree, r.t_scatter, r.t_terms, r.t_alloc, t_flat, r.lanes_accepted, r.lanes_tried, r.t_tasks, r.t_round_max);
+    if (smk::sw::clust_timing_live() != 0)
+        fprintf(stderr, "[smk_clust] subset %.3fs  factor %.3fs (%ld RANK2 iterations)  priority %.3fs  init %.3fs  |  tree search %.3fs in all "
+                "(host bookkeeping %.3fs: device frees %.3f, tree edits %.3f, labels + scatter of W %.3f, top terms + assignments %.3f, zero-filled W buffers %.3f)  flat step %.3fs  speculative steps accepted %ld of %ld; trial splits kept %.3fs, sum over rounds of the longest one %.3fs (= their time on "
+                "SMK_CLUST_DEVICES real devices)\n",
+                r.t_subset, r.t_factor, r.iterations, r.t_priority, r.t_init, t_search,
+                t_search - r.t_subset - r.t_factor - r.t_priority - r.t_init, r.t_free, r.t_tree, r.t_scatter, r.t_terms, r.t_alloc, t_flat, r.lanes_accepted, r.lanes_tried, r.t_tasks, r.t_round_max);
     // a failed flat step still returns the tree (RunClust, clust.cpp:53-61: the caller writes it)
     if (rc != SMK_OK && rc != SMK_FLATCLUST_FAILURE) { delete t; return rc; }
     *tree_out = t;
@@ -994,8 +990,8 @@ int smk_clust_sparse(const smk_clust_options* opts, int64_t nnz, const unsigned*
         rc = smk_matrix_create_sparse(&a, opts->nmf.height, opts->nmf.width, 0, opts->nmf.width, nnz, col_offsets,
                                       row_indices, data);
     }
-    if (const char* e = getenv("SMK_CLUST_TIMING"))
-        if (atoi(e)) fprintf(stderr, "[smk_clust] matrix to the device (CSC upload + transpose): %.3fs\n", t_create);
+    if (smk::sw::clust_timing_live() != 0)
+        fprintf(stderr, "[smk_clust] matrix to the device (CSC upload + transpose): %.3fs\n", t_create);
     if (rc == SMK_OK) rc = run_clust(opts, a, seed, draws, initdir, tree, stats);
     smk_matrix_destroy(a);
     return rc;

@@ -21,6 +21,7 @@
 #include "devutil.h"
 #include "gram_inverse.h"
 #include "gram_body.h"
+#include "switches.h"
 #include <climits>
 
 namespace smk {
@@ -969,8 +970,7 @@ int launch_gram_pack(const double* X, int k, i64 N, double* G, double* scratch, 
     const int KP = kp_of(k);
     const bool bf16_frag = storage == STORE_BF16 || nsplit >= 2;
     if (KP < 16 || KP > 64 || !bf16_frag || nsplit < 1 || nsplit > 3) return 1;     // (the fp16 form needs the finished Gram diagonal first)
-    static const bool enabled = [] { const char* e = getenv("SMK_FUSED_GRAM"); return !(e && e[0] == '0'); }();
-    if (!enabled) return 1;
+    if (!sw::fused_gram()) return 1;
     int nblk = (int)((N + 63) / 64);                     // one 16-column trip per wave while the partials stay within max_blocks, as launch_gram
     if (nblk > max_blocks) nblk = max_blocks;
     if (nblk < 1) nblk = 1;
@@ -1801,8 +1801,7 @@ __global__ __launch_bounds__(NT) void hals_w_fused_kernel(double* __restrict__ W
 
 static inline bool hals_w_use_blocked(int k)
 {
-    static const bool on = [] { const char* e = getenv("SMK_HALS_W_BLOCKED"); return !(e && e[0] == '0'); }();
-    return on && k > 64;
+    return sw::hals_w_blocked() && k > 64;
 }
 
 size_t hals_w_scratch_elems(int k, i64 M)
@@ -1829,23 +1828,17 @@ int launch_hals_w_update(double* Wt, int k, i64 M, PartialView R, const double* 
     if (hals_w_use_blocked(k)) return launch_hals_w_update_blocked(Wt, k, M, R, G, scratch, st);
     if (is_wide(k)) return launch_hals_w_update_wide(Wt, k, M, R, G, scratch, st);
     const int KPv = kp_of(k);
-    static int mode = -1;                            // SMK_HALS_W=multi forces the one-launch-per-column path
-    static unsigned spin_max = 1u << 22;             // SMK_HALS_SPIN=<n>: bound of the exchange polls (tests)
-    if (mode < 0) {
-        const char* env = getenv("SMK_HALS_W");
-        mode = (env && env[0] == 'm') ? 0 : 1;
-        const char* sp = getenv("SMK_HALS_SPIN");
-        if (sp && atoi(sp) > 0) spin_max = (unsigned)atoi(sp);
-    }
+    const bool env_multi = sw::hals_w_multi();                                                      // SMK_HALS_W=multi forces the one-launch-per-column path
+    const unsigned spin_max = sw::hals_spin() > 0 ? (unsigned)sw::hals_spin() : 1u << 22;           // SMK_HALS_SPIN=<n>: bound of the exchange polls (tests)
     // fused path: at most one workgroup per CU so that all of them are resident by construction.
     // Smallest workgroup (256 threads: cheapest in-block sync, measured best) that still covers M
     // rows with <= num_cus workgroups; the register budget caps it at 512 for KP = 32 and 256 for 64.
     int nt = 0;
     const int nt_max = (KPv == 64) ? 256 : 1024;
-    static const int nt_min = [] { const char* e = getenv("SMK_HALS_NT"); return e ? atoi(e) : 256; }();
+    const int nt_min = sw::hals_nt();
     for (int cand = 256; cand <= nt_max; cand *= 2)
         if (cand >= nt_min && (M + cand - 1) / cand <= (i64)num_cus) { nt = cand; break; }
-    if (mode == 1 && nt != 0 && !force_multi && KPv <= 64) {
+    if (!env_multi && nt != 0 && !force_multi && KPv <= 64) {
         const i64 nblk_f = (M + nt - 1) / nt;
         unsigned long long* slots = (unsigned long long*)scratch + (size_t)(parity & 1) * k * (1024 + 8);
         unsigned long long* other = (unsigned long long*)scratch + (size_t)((parity & 1) ^ 1) * k * (1024 + 8);
@@ -1854,7 +1847,7 @@ int launch_hals_w_update(double* Wt, int k, i64 M, PartialView R, const double* 
         // round 4 on the expectation that 40 polled slots instead of 256 would cut the 3.9 us per column -- measured on C3 it is
         // SLOWER, 155 us per sweep against 125 (4.8 us per column): the second dependent store -> poll hop costs more than the
         // all-to-all's contention.  Kept selectable as the record of that measurement (profiles/r04_hals_exchange_two_level.txt).
-        static const int mode = [] { const char* e = getenv("SMK_HALS_EXCHANGE"); return e ? atoi(e) : 1; }();
+        const int mode = sw::hals_exchange();
         const int two_level = (mode == 2 && nb >= 16 && nb <= 512 && k * 8 <= nt) ? 1 : 0;
         // the epilogue (packed operand + Gram partial per workgroup) rides along at KP = 16 / 32 with 256-thread workgroups
         const bool with_ep = ep && ep->pack_out && ep->Gp && (KPv == 16 || KPv == 32) && nt == 256 && nb <= ep->max_blocks;
@@ -1987,7 +1980,7 @@ int launch_spmm_gather(const i64* colptr, const unsigned* rowidx, const double* 
     if (k <= 2 && (ldx == 2 || ldx == KPv)) {
         if (ncols <= 0) return 0;
         // lanes per column by the average column length (nnz_hint <= 0: unknown -> 8)
-        static const int forced = [] { const char* e = getenv("SMK_SPMM2_LPC"); return e ? atoi(e) : 0; }();
+        const int forced = sw::spmm2_lpc();
         const double avg = nnz_hint > 0 ? (double)nnz_hint / (double)ncols : 12.0;
         int lpc = forced ? forced : (avg <= 3.0 ? 2 : avg <= 6.0 ? 4 : avg <= 12.0 ? 8 : 16);
         const i64 threads = ncols * lpc;

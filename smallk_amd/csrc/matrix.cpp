@@ -38,7 +38,7 @@ int ensure_seg_plans(const smk_matrix* a)
     std::lock_guard<std::mutex> lk(mu);
     if (a->seg_tried) return 0;
     a->seg_tried = true;
-    static const bool seg_on = [] { const char* e = getenv("SMK_SPMM_SEG"); return !(e && e[0] == '0'); }();
+    const bool seg_on = sw::spmm_seg();
     hipStream_t bst = a->st ? a->st : ctx().stream;
     if (seg_on && (build_seg_plan(a->n, a->nnz, a->colptr, a->rowidx, &a->segA, bst) ||
                    build_seg_plan(a->m, a->nnz, a->colptr_t, a->rowidx_t, &a->segAt, bst))) {
@@ -126,13 +126,12 @@ int smk_matrix_create(smk_matrix** out, int64_t height, int64_t width_global, in
     // (C3: 128 KiB and 32 KiB strides, skewed: 1200 -> 1130 / 980 it/s); 256 and 384 rows more gain less than 128.
     // SMK_LD_SKEW=0 turns it off, =n asks for n rows.  (profiles/r04_leading_dimension_skew.txt)
     {
-        static const i64 skew = [] { const char* e = getenv("SMK_LD_SKEW"); return e ? (i64)atoll(e) / ROW_PAD * ROW_PAD : ROW_PAD; }();
+        const i64 skew = sw::ld_skew().set ? sw::ld_skew().v / ROW_PAD * ROW_PAD : ROW_PAD;
         if (skew > 0 && ((size_t)a->ldA * es) % ((size_t)1 << 20) == 0) a->ldA += skew;
         if (skew > 0 && ((size_t)a->ldAt * es) % ((size_t)1 << 20) == 0) a->ldAt += skew;
     }
     {   // SMK_SINGLE_COPY=1: dense matrices are created without the stored transpose (smk_matrix_create_single_copy asks for it explicitly)
-        const char* esc = getenv("SMK_SINGLE_COPY");
-        a->single = g_create_single || (esc && esc[0] == '1');
+        a->single = g_create_single || sw::single_copy();
     }
     hipError_t e1 = smk::dev_malloc(&a->A, (size_t)a->ldA * a->colsA * es);
     hipError_t e2 = (e1 == hipSuccess && !a->single) ? smk::dev_malloc(&a->At, (size_t)a->ldAt * a->colsAt * es) : e1;
@@ -439,7 +438,7 @@ int smk_matrix_create_sparse(smk_matrix** out, int64_t height, int64_t width_glo
     if (e == hipSuccess && nnz > 0) e = hipMemcpy(a->val, data + base, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice);
     // the transpose: a stable radix sort by row on the device (sort.hip) -- the entry order of the host counting sort --
     // or, if that is not available (SMK_TRANSPOSE=host forces it), the host routine and a second upload
-    static const bool host_tr = [] { const char* ev = getenv("SMK_TRANSPOSE"); return ev && ev[0] == 'h'; }();
+    const bool host_tr = sw::transpose_host();
     bool done = false;
     if (e == hipSuccess && !host_tr)
         done = device_csc_transpose(height, ncols_local, nnz, a->colptr, a->rowidx, a->val, a->colptr_t, a->rowidx_t, a->val_t, ctx().stream) == 0;
@@ -556,7 +555,7 @@ int smk_matrix_gather_cols(const smk_matrix* src, const unsigned* cols, int64_t 
     // the row map crosses PCIe (sparse_subset.hip).  SMK_SPARSE_SUBSET=host forces the host cut below.
     bool increasing = true;
     for (int64_t j = 1; j < ncols && increasing; ++j) increasing = cols[j] > cols[j - 1];
-    static const bool force_host = [] { const char* e = getenv("SMK_SPARSE_SUBSET"); return e && e[0] == 'h'; }();
+    const bool force_host = sw::sparse_subset_host();
     if (increasing && !force_host) {
         SparseDev sd, od;
         sd.m = src->m; sd.n = src->n; sd.nnz = src->nnz;

@@ -4,6 +4,7 @@
 #include "devutil.h"
 #include "gram_inverse.h"
 #include "nnls_masked.h"
+#include "switches.h"
 
 namespace smk {
 
@@ -16,9 +17,8 @@ namespace smk {
 unsigned long long* nnls_stats_ptr()
 {
     static unsigned long long* buf = [] {
-        const char* e = getenv("SMK_NNLS_STATS");
         unsigned long long* p = nullptr;
-        if (e && atoi(e) != 0 && hipMalloc((void**)&p, 256 * sizeof(unsigned long long)) == hipSuccess) (void)hipMemset(p, 0, 256 * sizeof(unsigned long long));
+        if (sw::nnls_stats() && hipMalloc((void**)&p, 256 * sizeof(unsigned long long)) == hipSuccess) (void)hipMemset(p, 0, 256 * sizeof(unsigned long long));
         else p = nullptr;
         return p;
     }();
@@ -531,7 +531,7 @@ bool nnls_uses_tiles(int k)
 {
     // default: from k = 65 (measured on 16384 x 8192, 12 iterations: k = 80 / 100 / 128 3.96 / 4.53 / 5.27 -> 2.39 / 2.84 / 3.12 ms per
     // iteration against nnls_bpp_inv128_kernel); SMK_NNLS_TILE128=0 keeps that kernel, =2 also sends k in (32, 64] here (A/B)
-    static const int level = [] { const char* e = getenv("SMK_NNLS_TILE128"); return e ? atoi(e) : 1; }();
+    const int level = sw::nnls_tile128();
     return is_wide(k) || (level >= 1 && k > 64) || (level >= 2 && k > 32);
 }
 
@@ -543,14 +543,13 @@ size_t nnls_scratch_elems(int k) { return (size_t)kp_of(k) * kp_of(k) + 8; }    
 // columns: 3.39 against 3.56 ms per iteration; C4 whole: no difference).  SMK_NNLS_ROUNDS overrides.
 static inline int nnls_rounds(i64 ncols)
 {
-    static const int forced = [] { const char* e = getenv("SMK_NNLS_ROUNDS"); return e ? atoi(e) : 0; }();
+    const int forced = sw::nnls_rounds();
     return forced > 0 ? forced : (ncols <= 65536 ? 1 : 4);
 }
 
 bool nnls_inverse_at_32()
 {
-    static const bool on = [] { const char* e = getenv("SMK_NNLS_INV32"); return !(e && e[0] == '0'); }();
-    return on;
+    return sw::nnls_inv32();
 }
 
 // k > 32: Ginv and the path selector into `scratch` (nnls_scratch_elems(k) doubles).  One workgroup, ~0.1 ms: the
@@ -560,7 +559,7 @@ int launch_gram_inverse(const double* G, int k, double* scratch, hipStream_t st)
     const int KPv = kp_of(k);
     if (KPv < 32 || KPv > 128 || !scratch) return 0;
     if (KPv == 32 && !nnls_inverse_at_32()) return 0;
-    static const bool old64 = [] { const char* e = getenv("SMK_GRAM_INVERSE_OLD"); return e && atoi(e) != 0; }();
+    const bool old64 = sw::gram_inverse_old();
     if (KPv == 32) gram_inverse64_kernel<32><<<1, 256, 0, st>>>(G, k, scratch, (int*)(scratch + 32 * 32));
     else if (KPv == 64 && !old64) gram_inverse64_kernel<64><<<1, 256, 0, st>>>(G, k, scratch, (int*)(scratch + 64 * 64));
     else if (KPv == 64) gram_inverse_kernel<64><<<1, 256, 0, st>>>(G, k, scratch, (int*)(scratch + 64 * 64));
@@ -585,7 +584,7 @@ int launch_nnls_bpp(double* X, double* Y, int k, i64 col_begin, i64 col_end, Par
     if (ncols <= 0) return 0;
     const int grid = (int)((ncols + gpb - 1) / gpb);
     const i64 N = col_end;
-    static const int inv_mode = [] { const char* e = getenv("SMK_NNLS_INV"); return e ? atoi(e) : 1; }();
+    const int inv_mode = sw::nnls_inv();
     const int* skip_if = nullptr;
     if (KPv == 128) {
         if (!scratch) { set_error("nnls: k > 64 needs the scratch buffer"); return -100; }

@@ -19,6 +19,7 @@
 // Ginv r and of M[:, T] u): the results are bit-identical to that kernel's (tests/test_gpu_nnls.py compares them).
 #include "devutil.h"
 #include "nnls_masked.h"
+#include "switches.h"
 
 namespace smk {
 
@@ -399,8 +400,7 @@ __global__ __launch_bounds__(NT, WGS) void nnls_bpp_g16_kernel(double* __restric
 // launch-bound iteration).
 static int g16_level()
 {
-    static const int level = [] { const char* e = getenv("SMK_NNLS_G16"); return e ? atoi(e) : 1; }();
-    return level;
+    return sw::nnls_g16();
 }
 
 // the four-columns-per-wave launch; returns 1 when it was issued, 2 when it was issued AND carries the masked-elimination fallback
@@ -417,12 +417,12 @@ int launch_nnls_bpp_g16(double* X, double* Y, int k, i64 col_begin, i64 col_end,
     if (ncols <= 0) return 0;
     const bool s1 = R.S == 1 && R.f64;
     const i64 nquads = (ncols + 3) / 4;
-    static const int wgs = [] { const char* e = getenv("SMK_NNLS_G16_WGS"); return e ? atoi(e) : 0; }();
+    const int wgs = sw::nnls_g16_wgs();
     if (KPv == 32) {
         // shapes (SMK_NNLS_G16_SHAPE, A/B; s_1m it/s on one box): 3 = 256 threads, three workgroups per CU at <= 168 registers (no
         // spills), elimination bounds in steps of 2 (default: 441); 0 = the same with bounds in steps of 4 (428); 1 = 512 threads at
         // <= 128 registers (four waves per SIMD, 144 bytes of scratch per lane: 395); 2 = 512 threads, two waves per SIMD (408)
-        static const int shape = [] { const char* e = getenv("SMK_NNLS_G16_SHAPE"); return e ? atoi(e) : 3; }();
+        const int shape = sw::nnls_g16_shape();
         auto run = [&](auto kern, int NT, int wg_per_cu) -> int {
             const int lds = (2 * 32 * 32 + (NT / 64) * 4 * 48) * (int)sizeof(double);
             i64 g2 = (nquads + NT / 64 - 1) / (NT / 64);

@@ -27,6 +27,7 @@
 // leaves through the abort word and the host runs the launch-per-kernel loop instead (the solver state was not touched).
 #include "devutil.h"
 #include "rank2_math.h"
+#include "switches.h"
 
 #include <algorithm>
 
@@ -461,7 +462,7 @@ __global__ __launch_bounds__(1024) void rank2_persist_kernel(R2PersistArgs A)
 constexpr size_t R2P_LDS_BYTES = 150 * 1024;      // of the CU's 160 KB (static LDS: ~1.2 KB): 64 KB of products, the offsets, the row-index copies
 size_t rank2_persist_lds_bytes()
 {
-    static const int small = [] { const char* e = getenv("SMK_R2P_LDS"); return e && atoi(e) == 0 ? 1 : 0; }();
+    const bool small = sw::r2p_lds() == 0;
     // SMK_R2P_LDS=0: products and offsets only (no room for a row-index copy)
     return small ? (size_t)R2P_CHUNK * 16 + 2 * ((size_t)(R2P_MAX_ITEMS + 1) * 4 + 16) : R2P_LDS_BYTES;
 }
@@ -471,7 +472,7 @@ size_t rank2_persist_sync_bytes() { return (size_t)R2P_WORDS * 32 * sizeof(unsig
 // side, at most one workgroup per CU.  0: the matrix does not fit this geometry (the caller takes the other path).
 int rank2_persist_workgroups(i64 m, i64 n, i64 nnz, int num_cus)
 {
-    static const int cap = [] { const char* e = getenv("SMK_R2P_WGS"); return e ? atoi(e) : 0; }();
+    const int cap = sw::r2p_wgs();
     const i64 top = cap > 0 ? cap : num_cus;
     const i64 longer = m > n ? m : n;
     i64 wgs = std::max((nnz + 2047) / 2048, (longer + 1023) / 1024);

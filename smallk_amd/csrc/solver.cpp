@@ -14,6 +14,7 @@
 //   packW / packH : MFMA operand fragments of W' / H
 #include "state.h"
 #include "comm.h"
+#include "switches.h"
 
 #include <climits>
 #include <cmath>
@@ -113,7 +114,7 @@ static int plan_products(smk_solver* s)
         // single copy, A' -- either stays in the 256 MB Infinity Cache between the passes or it does not.  Measured crossover:
         // profiles/r05_cache_policy_ab.txt.  SMK_BP_TEMPORAL=0/1 forces a policy.
         const double streamed = (double)s->m * (double)s->n * elem_size(a->storage) * (a->single ? 1.0 : 2.0) * s->ng;
-        static const int forced = [] { const char* e = getenv("SMK_BP_TEMPORAL"); return e ? atoi(e) : -1; }();
+        const int forced = sw::bp_temporal();
         const int temporal = forced >= 0 ? (forced ? 1 : 0) : (streamed <= 300.0e6 ? 1 : 0);
         for (int g = 0; g < s->ng; ++g) { s->pg1[g].temporal = temporal; s->pg2[g].temporal = temporal; }
     }
@@ -133,8 +134,7 @@ static int plan_products(smk_solver* s)
         s->pl1 = s->pg1[0];
         s->pl2 = s->pg2[0];
     }
-    const char* epk = getenv("SMK_NNLS_PACK");                      // read per plan, like SMK_NSPLIT (0 = the separate reduce-and-pack launch)
-    const bool pack_env = !(epk && epk[0] == '0');
+    const bool pack_env = sw::nnls_pack();                          // read per plan, like SMK_NSPLIT (0 = the separate reduce-and-pack launch)
     s->pack_in_solve = pack_env && !s->pack_in_solve_off && s->o.algorithm == SMK_ALG_BPP && s->KP == 16 && s->nsplit == NSPLIT_F16X2 &&
                        !a->sparse && !a->single && s->ng == 1 && !is_dist(s) && !s->comm && bigprod_supports_tail(s->pl1) && bigprod_supports_tail(s->pl2);
     if (s->pack_in_solve && (a->colnorm_max < 0.0 || a->rownorm_max < 0.0)) {
@@ -182,7 +182,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
     s->m = a->m;
     s->n = a->n;
     s->st = a->st ? a->st : ctx().stream;
-    const char* env = getenv("SMK_NSPLIT");
+    const sw::Maybe<int> env = sw::nsplit();
     // fp32 A: the fp16 two-term form (3 MFMAs per product, 2^-22 operand error) unless SMK_NSPLIT picks the bf16 forms
     // (3 = bf16x3, 6 MFMAs, power-bound; 2 = two bf16 terms, 2^-16); bf16 A: three bf16 terms of the factor
     // HALS amplifies the product error several thousand times (its W update is a difference of nearly equal terms per
@@ -211,8 +211,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
     // (profiles/r04_long_runs_500_iterations.txt).  Larger matrices keep the fp16 form (C4: 3 x the pass time otherwise);
     // SMK_NSPLIT=8 / 3 select the other forms anywhere.
     // (SMK_BPP_SMALL_ACCURATE=0 keeps the fp16 form: the test suite sets it, its small cases stand in for C4's path.)
-    const char* esa = getenv("SMK_BPP_SMALL_ACCURATE");             // read per solver, like SMK_NSPLIT
-    const bool small_accurate = !(esa && esa[0] == '0');
+    const bool small_accurate = sw::bpp_small_accurate();           // read per solver, like SMK_NSPLIT
     if (small_accurate && opts->algorithm == SMK_ALG_BPP && opts->k > 32 && !a->sparse && a->m * a->n_global <= ((i64)1 << 24))
         nsplit_default = NSPLIT_F64;
     // Dense RANK2 (every node factorisation of HierNMF2 / flatclust on dense A runs 100 .. 1000 iterations to a tight
@@ -222,11 +221,11 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
     if (opts->algorithm == SMK_ALG_RANK2 && !a->sparse) nsplit_default = NSPLIT_F64;
     // Column scales of A more than 2^28 apart: the small columns fall below what fp32-class products resolve next to the
     // large ones (HALS / BPP leave the bar at 2^+-20, tests/test_gpu_parity.py) -- the accurate form as well.
-    if (!env && !a->sparse && opts->algorithm != SMK_ALG_RANK2) {
+    if (!env.set && !a->sparse && opts->algorithm != SMK_ALG_RANK2) {
         if (a->col_spread_log2 < 0) { const int rc0 = matrix_measure_scale(a, a->st ? a->st : ctx().stream); if (rc0) { --ctx().live_solvers; delete s; return rc0; } }
         if (a->col_spread_log2 > 28) nsplit_default = NSPLIT_F64;
     }
-    s->nsplit = env ? atoi(env) : nsplit_default;
+    s->nsplit = env.set ? env.v : nsplit_default;
     if (s->nsplit != NSPLIT_F64 && (s->nsplit < 1 || s->nsplit > NSPLIT_F16X2)) s->nsplit = nsplit_default;
     if (s->nsplit == NSPLIT_F64 && a->sparse) s->nsplit = 3;      // sparse A: gather products in fp64 already
     // the fp16 two-term form applies to fp32 storage; RANK2 keeps its Gram matrices inside its own solve kernel
@@ -311,7 +310,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
         // inversion of k in (32, 64] behind a dense pass; at k in (16, 32] (13 us) stream order is as fast or faster (4096 x 2048,
         // k = 32: 115 -> 92 us per iteration; 8192 x 4096: 131 -> 125; 32768 x 8192: equal), and with a sparse matrix the inverse
         // rides in the gather product's launch (start_inverse).  SMK_INV_STREAM=1: the second stream everywhere, =0: nowhere.
-        static const int inv_env = [] { const char* e = getenv("SMK_INV_STREAM"); return e ? atoi(e) : -1; }();
+        const int inv_env = sw::inv_stream();
         const bool inv_beside = inv_env >= 0 ? inv_env != 0 : (!a->sparse && s->KP >= 64);
         if (inv_beside && (s->KP >= 64 || (s->KP == 32 && nnls_inverse_at_32())) && !nnls_uses_tiles(s->k)) {
             if (hipStreamCreateWithFlags(&s->st_inv, hipStreamNonBlocking) != hipSuccess) rc |= 1;
@@ -430,8 +429,7 @@ int smk_solver_attach_comm(smk_solver* s, smk_comm* comm)
     // MEASUREMENT HOOK (bench.py --emulate-world N, one GPU): the geometry of rank 0 of N ranks -- row blocks, chunk
     // sizes, per-rank NNLS / Gram / packing work -- while the collectives run through the real one-rank communicator.
     // Times a rank's work without the transfers; the blocks of the other ranks never arrive, so the factors mean nothing.
-    if (const char* e = getenv("SMK_COMM_EMULATE_WORLD"))
-        if (comm->world == 1 && atoi(e) > 1 && atoi(e) <= 64) { s->world = atoi(e); s->rank = 0; }
+    if (const int emu = sw::comm_emulate_world(); comm->world == 1 && emu > 1 && emu <= 64) { s->world = emu; s->rank = 0; }
     // The ranks must run ONE exchange protocol.  The product form is chosen per solver, and one input of that choice -- the
     // spread of the column scales -- is measured on the rank's LOCAL column shard: a rank whose shard alone spans more than
     // 2^28 would take the accurate form (and with it other buffers and other collectives) while its peers do not.  So the
@@ -457,7 +455,7 @@ int smk_solver_attach_comm(smk_solver* s, smk_comm* comm)
         const i64 mpad = s->pl2.ncols_pad;
         i64 c = mpad / ((i64)s->world * 4096);
         c = std::max<i64>(1, std::min<i64>(c, 4));
-        if (const char* e = getenv("SMK_COMM_CHUNKS")) c = std::max(1, std::min(atoi(e), MAX_CHUNKS));
+        if (const auto ce = sw::comm_chunks(); ce.set) c = std::max(1, std::min(ce.v, MAX_CHUNKS));
         s->blk = round_up((mpad + (i64)s->world * c - 1) / ((i64)s->world * c), 256);
         s->nchunk = (int)((mpad + (i64)s->world * s->blk - 1) / ((i64)s->world * s->blk));      // chunks that hold rows
         s->rows_cap = (i64)s->nchunk * s->world * s->blk;
@@ -468,8 +466,7 @@ int smk_solver_attach_comm(smk_solver* s, smk_comm* comm)
         // iteration -- the sums over 65536 columns are ~500, their fp32 rounding 3e-5, and HH' of such data amplifies it a
         // thousand times -- against 6e-7 with fp64.  With the exchange pipelined behind the pass the extra bytes are hidden
         // except in the last chunk.
-        const char* e = getenv("SMK_COMM_F64");
-        s->red_f64 = !(e && atoi(e) == 0);
+        s->red_f64 = sw::comm_f64() != 0;
     }
     // BPP and MU update the rows of W independently of each other: every rank takes its own blocks (HALS normalises column by
     // column over ALL rows inside its sweep and keeps the replicated update)
@@ -762,7 +759,7 @@ static int start_inverse(smk_solver* s, int side, const double* G, hipEvent_t af
         // per solve, ~8 us each way on the main stream -- more than the 13 us inversion of k <= 32 they hide (the Reuters shape: 125
         // us per iteration beside the product, 118 in stream order, 91 riding; dense 4096 x 2048, k = 32: 115 / 92 / 70).  A launch
         // that cannot carry it leaves it to launch_nnls_bpp, in stream order, or to the second stream.  SMK_INV_RIDE=0: never rides.
-        static const bool ride = [] { const char* e = getenv("SMK_INV_RIDE"); return !(e && e[0] == '0'); }();
+        const bool ride = sw::inv_ride();
         const bool route = !nnls_uses_tiles(s->k) && (s->KP == 64 || (s->KP == 32 && nnls_inverse_at_32()));
         const bool carrier = s->a->sparse ? true : (s->ng == 1 && bigprod_supports_ride(side == 0 ? s->pg1[0] : s->pg2[0]));
         if (ride && route && carrier && !after && !is_dist(s) && !s->comm && !s->w_sharded) { s->inv_ride[side] = true; return 0; }
@@ -790,11 +787,7 @@ static int start_inverse(smk_solver* s, int side, const double* G, hipEvent_t af
 static bool guard_applies(const smk_solver* s);
 static bool check_rides_in_nnls(const smk_solver* s)
 {
-    static const bool on = [] { const char* e = getenv("SMK_PROGRESS_DEFER"); return !(e && e[0] == '0'); }();
-    static const bool fused = [] { const char* e = getenv("SMK_PROGRESS_FUSED"); return !(e && e[0] == '0'); }();
-    static const bool dual = [] { const char* e = getenv("SMK_BPP_GRADW"); return !(e && e[0] == '1'); }();
-    static const bool guard_env = [] { const char* e = getenv("SMK_GUARD_EVERY"); return e && atoi(e) > 0; }();
-    if (!on || !fused || !dual || guard_env) return false;
+    if (!sw::progress_defer() || !sw::progress_fused() || sw::bpp_gradw() || sw::guard_every() > 0) return false;
     if (s->o.algorithm != SMK_ALG_BPP || s->KP > 16 || s->o.prog_est_algorithm != SMK_PROG_PG_RATIO) return false;
     if (is_dist(s) || s->comm || s->w_sharded) return false;
     const i64 gpb = 256 / s->KP;
@@ -810,7 +803,7 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
     }
     // k in (8, 16], fp16 form, one GPU: the launch that solves ALL columns of a factor also leaves its Gram partials (the
     // gram_x that follows in every BPP schedule then only reduces them)
-    static const bool fuse = [] { const char* e = getenv("SMK_NNLS_GRAM"); return !(e && e[0] == '0'); }();
+    const bool fuse = sw::nnls_gram();
     const i64 N = side == 0 ? s->n : s->m;
     const bool want = fuse && s->KP == 16 && s->nsplit == NSPLIT_F16X2 && !is_dist(s) && c0 == 0 && c1 == N && (X == s->H || X == s->Wt);
     s->nnls_gram_nblk[side] = 0;
@@ -828,7 +821,7 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
         pk.nq = packed_chunk_pairs_f16x2(s->a->storage, N);
         // TEST HOOK: shrink the bound so that the scaled entries leave fp16's range (the launch must flag it, the run must be
         // repeated without the packing: pack_fail_soft)
-        if (const char* e = getenv("SMK_NNLS_PACK_TEST_ANORM")) pk.anorm *= atof(e);
+        pk.anorm *= sw::nnls_pack_test_anorm();
     }
     s->nnls_packed[fx] = false;
     // slot 5 of smk_solver_kernel_time: the block-pivoting launches (both kernels of a k > 16 solve), sampled with the pass that fed them
@@ -1038,14 +1031,13 @@ static inline void take_tail(smk_solver* s, int side, BigProdPlan* pl)
 // 12 650 -> 13 350 it/s).  SMK_PROGRESS_POLL=0: the event.
 static bool progress_polls()
 {
-    static const bool poll = [] { const char* e = getenv("SMK_PROGRESS_POLL"); return !(e && e[0] == '0'); }();
-    return poll;
+    return sw::progress_poll();
 }
 
 static int check_totals(smk_solver* s, BigProdPlan* pl)
 {
     if (s->pg_totals_slot < 0) return 0;
-    static const bool ride = [] { const char* e = getenv("SMK_PROGRESS_TAIL"); return !(e && e[0] == '0'); }();
+    const bool ride = sw::progress_tail();
     const bool poll = progress_polls();
     const int b = s->pg_totals_slot, k2 = (s->k + 1) / 2 * 2;
     double* snap_g = s->pg_defer_snap ? s->snap[b] + (size_t)(s->m + s->n) * k2 : nullptr;
@@ -1196,7 +1188,7 @@ static int gram_factor(smk_solver* s, int side)
         // the second (spmm_seg.hip, gram_body.h): four launches become two (the Reuters shape under HALS: 102 -> 84 us per iteration).
         // Not where block pivoting needs the inverse of this matrix in the SAME launch (k in (16, 32]: that one rides, start_inverse).
         // A product that takes another route forms the matrix first, as before (timed_spmm).  SMK_GRAM_RIDE=0: never rides.
-        static const bool ride = [] { const char* e = getenv("SMK_GRAM_RIDE"); return !(e && e[0] == '0'); }();
+        const bool ride = sw::gram_ride();
         const bool inverse_next = s->o.algorithm == SMK_ALG_BPP && (s->KP == 64 || (s->KP == 32 && nnls_inverse_at_32()));
         if (ride && s->a->sparse && !is_dist(s) && !s->comm && !s->w_sharded && (s->KP == 16 || s->KP == 32) && s->k > 2 && !inverse_next &&
             s->o.algorithm != SMK_ALG_RANK2) {
@@ -1227,7 +1219,7 @@ static int gram_factor(smk_solver* s, int side)
                 return 0;
             }
             // ... and packs it in the same launch (the packing workgroups add up the 16 diagonal entries themselves)
-            static const bool fuse_pack = [] { const char* e = getenv("SMK_REDUCE_PACK"); return !(e && e[0] == '0'); }();
+            const bool fuse_pack = sw::reduce_pack();
             if (fuse_pack && !s->a->sparse) {
                 const int rc = launch_reduce_pack_f16x2(s->gram_scratch, nb, s->k, G, s->xscale[side], s->oscale[side], (double)s->a->ascale, X, N,
                                                         s->a->storage, side == 0 ? s->packW : s->packH, s->st);
@@ -1331,7 +1323,7 @@ static int solver_iteration(smk_solver* s)
             // round 6: at k <= 32 on one GPU both sweeps also leave the packed operand of the product that follows and their Gram
             // partials (kernels.hip: tile_pack_gram) -- the separate gram_pack launches (11 us each at C3) go, only the 5 us
             // reductions stay.  SMK_HALS_EPILOGUE=0: the launches of before.
-            static const bool ep_on = [] { const char* e = getenv("SMK_HALS_EPILOGUE"); return !(e && e[0] == '0'); }();
+            const bool ep_on = sw::hals_epilogue();
             const bool bf16_frag = s->a->storage == SMK_STORE_BF16 || s->nsplit >= 2;
             const bool ep_ok = ep_on && !s->a->sparse && !is_dist(s) && !s->comm && (s->KP == 16 || s->KP == 32) && bf16_frag && s->nsplit >= 1 && s->nsplit <= 3 &&
                                s->ng == 1 && s->hals_ep_blocks > 0;
@@ -1554,10 +1546,10 @@ static int progress_begin(smk_solver* s, int b, bool snapshot, bool allow_defer 
         SMK_HIP(hipEventRecord(s->pev[b], s->st));
         return 0;
     }
-    static const bool fused_check = [] { const char* e = getenv("SMK_PROGRESS_FUSED"); return !(e && e[0] == '0'); }();
+    const bool fused_check = sw::progress_fused();
     // BPP: gradW is the dual of the W-side NNLS (nmf_solver_bpp.hpp:362-366), whose projected-gradient sum is exactly zero after a
     // solve that reached optimality (a solve that did not has raised the failure flag); SMK_BPP_GRADW=1 forms HH' W' - (AH')' anyway
-    static const bool bpp_dual_is_gradient = [] { const char* e = getenv("SMK_BPP_GRADW"); return !(e && e[0] == '1'); }();
+    const bool bpp_dual_is_gradient = !sw::bpp_gradw();
     if (fused_check && s->o.prog_est_algorithm == SMK_PROG_PG_RATIO && !is_dist(s) && !is_wide(s->k) && !s->w_sharded) {
         // round 6: gradients + snapshot in one launch, sums + failure flag written into the pinned slot by a second (kernels.hip:
         // grad_pg2_snap_kernel, sum_partials2_host_kernel); SMK_PROGRESS_FUSED=0: the four stream operations of before
@@ -1605,7 +1597,7 @@ static int progress_begin(smk_solver* s, int b, bool snapshot, bool allow_defer 
 // SMK_PROGRESS_DEPTH=2|3 keeps the deeper pipeline selectable; sharded runs always use one (their checks carry collectives).
 static int progress_depth(const smk_solver* s)
 {
-    static const int forced = [] { const char* e = getenv("SMK_PROGRESS_DEPTH"); return e ? atoi(e) : 0; }();
+    const int forced = sw::progress_depth();
     if (is_dist(s) || s->comm || forced <= 1) return 1;
     if (snapshot_elems(s->k, s->m, s->n) * sizeof(double) > ((size_t)1 << 30)) return 1;
     return std::min(forced, smk_solver::PROG_SLOTS - 1);
@@ -1758,7 +1750,7 @@ static int pack_fail_soft(smk_solver* s)
 // guard is offered for BPP runs on data outside the swept families, and the static rules of smk_solver_create stay the default.
 static bool guard_applies(const smk_solver* s)
 {
-    static const int every = [] { const char* e = getenv("SMK_GUARD_EVERY"); return e ? atoi(e) : 0; }();
+    const int every = sw::guard_every();
     if (every <= 0 || s->guard_off || s->a->sparse || s->nsplit == NSPLIT_F64 || is_dist(s) || s->comm) return false;
     if (s->o.algorithm != SMK_ALG_BPP) return false;
     return s->k <= 256 && s->n >= 64 && s->iter > 0 && s->iter % every == 0;
@@ -1807,15 +1799,14 @@ static int guard_resolve(smk_solver* s)
     if (!s->guard_pending) return 0;
     s->guard_pending = false;
     SMK_HIP(hipEventSynchronize(s->guard_ev));
-    static const double tau = [] { const char* e = getenv("SMK_GUARD_TAU"); return e ? atof(e) : 1e-4; }();
+    const double tau = sw::guard_tau();
     const double* p = s->guard_pin;
     const double delta = p[1] > 0.0 ? std::sqrt(p[0] / p[1]) : 0.0;
     const size_t kk = (size_t)s->KP * s->KP;
     const double cond = std::max(cond1_spd(p + 2, s->KP, s->k), cond1_spd(p + 2 + kk, s->KP, s->k));
     s->guard_checks += 1;
     s->guard_last = cond * delta;
-    static const bool verbose = [] { const char* e = getenv("SMK_GUARD_VERBOSE"); return e && atoi(e) != 0; }();
-    if (verbose) fprintf(stderr, "[smk guard] iteration %d: delta %.3e, cond %.3e, product %.3e (tau %.1e)\n", s->iter, delta, cond, cond * delta, tau);
+    if (sw::guard_verbose()) fprintf(stderr, "[smk guard] iteration %d: delta %.3e, cond %.3e, product %.3e (tau %.1e)\n", s->iter, delta, cond, cond * delta, tau);
     if (!(cond * delta > tau)) return 0;
     // change to the accurate form: new plans and buffers, then solver.Init on the current factors
     s->guard_fired += 1;
@@ -1998,8 +1989,8 @@ int smk_solver_run(smk_solver* s, smk_stats* stats)
 static std::atomic<unsigned long long> g_r2p_off_devices{0};
 static bool rank2_persist_eligible(const smk_solver* s)
 {
-    static const int mode = [] { const char* e = getenv("SMK_R2_PERSIST"); return e ? atoi(e) : 1; }();
-    static const i64 max_nnz = [] { const char* e = getenv("SMK_R2_PERSIST_NNZ"); return e ? (i64)atoll(e) : (i64)1 << 40; }();
+    const int mode = sw::r2_persist();
+    const i64 max_nnz = sw::r2_persist_nnz();
     if (!mode || s->r2p_off) return false;
     if (g_r2p_off_devices.load(std::memory_order_relaxed) & (1ull << (smk_current_device() & 63))) return false;
     if (s->o.algorithm != SMK_ALG_RANK2 || !s->a->sparse || s->o.prog_est_algorithm != SMK_PROG_PG_RATIO) return false;
@@ -2016,7 +2007,7 @@ static int rank2_persist_run(smk_solver* s, int* status, int* count)
     if (nwg < 1 || nwg > 1024) { *status = R2P_ABORTED; return 0; }
     // TEST HOOK: behave as if the kernel's workgroups had not all become resident (the caller must then finish the run on the
     // launch-per-kernel loop from the state solver.Init left)
-    if (const char* e = getenv("SMK_R2P_TEST_ABORT")) if (atoi(e) != 0) { *status = R2P_ABORTED; return 0; }
+    if (sw::r2p_test_abort()) { *status = R2P_ABORTED; return 0; }
     if (!s->r2p_sync) {
         int rc = dev_alloc(&s->r2p_hc1, (size_t)2 * s->n);
         rc |= dev_alloc(&s->r2p_r2c, (size_t)2 * s->m);
@@ -2048,8 +2039,7 @@ static int rank2_persist_run(smk_solver* s, int* status, int* count)
     *status = (int)s->r2p_pin[0];
     *count = (int)s->r2p_pin[1];
     {
-        static const bool prof = [] { const char* e = getenv("SMK_R2P_PROFILE"); return e && atoi(e) != 0; }();
-        if (prof) {
+        if (sw::r2p_profile()) {
             const double it = std::max(1.0, s->r2p_pin[2]);
             fprintf(stderr, "[r2p] %ld x %ld nnz %ld: %d workgroups, status %d, %.0f iterations; per iteration (workgroup 0): "
                     "B1 %.1f us, phase W %.1f, B2 %.1f, phase G %.1f\n", (long)s->m, (long)s->n, (long)s->a->nnz, nwg, *status, it,
@@ -2117,7 +2107,7 @@ static int solver_run_once(smk_solver* s, smk_stats* stats)
     // results and iteration counts are those of the check-every-iteration loop (SMK_SYNC_PROGRESS=1
     // runs that loop instead).
     {
-        static const bool sync_mode = [] { const char* e = getenv("SMK_SYNC_PROGRESS"); return e && atoi(e) != 0; }();
+        const bool sync_mode = sw::sync_progress();
         const int depth = progress_depth(s), NS = smk_solver::PROG_SLOTS;
         std::deque<int> pend;                          // iterations whose check is outstanding, oldest first (at most `depth`)
         auto resolve = [&](int p, bool speculated) -> int {      // 0: go on, 1: converged at p, < 0: error
@@ -2227,7 +2217,7 @@ int smk_solver_nnls_hals(smk_solver* s, double tol, int verbose, int max_iter, i
     int rc = 0;
     // W'A is formed ONCE and every sweep of the loop below reads it: the accurate product form (the fp64 product of the stored
     // data) for the price of one slower pass, so that the converged H differs from the reference's by summation order only
-    if (!s->a->sparse && s->nsplit != NSPLIT_F64 && !getenv("SMK_NSPLIT")) {
+    if (!s->a->sparse && s->nsplit != NSPLIT_F64 && !sw::nsplit().set) {
         s->nsplit = NSPLIT_F64;
         rc = plan_products(s);
         if (!rc && alloc_product_buffers(s)) rc = SMK_DEVICE_ERROR;
@@ -2369,7 +2359,7 @@ int smk_solver_enable_timing(smk_solver* s, int on)
         const double bytes = (double)s->m * (double)s->n * (s->a->sparse ? 12.0 : (double)elem_size(s->a->storage));
         s->timing_stride = bytes < (double)((i64)1 << 30) ? 16 : bytes < 32.0 * (double)((i64)1 << 30) ? 8 : 1;
     }
-    if (const char* e = getenv("SMK_TIMING_STRIDE")) s->timing_stride = std::max(1, atoi(e));
+    if (const auto ts = sw::timing_stride(); ts.set) s->timing_stride = std::max(1, ts.v);
     s->pass_counter[0] = s->pass_counter[1] = 0;
     s->pass_sampled[0] = s->pass_sampled[1] = 0;
     for (int w = 0; w < 6; ++w) { s->acc_ms[w] = 0.0; s->launches[w] = 0; }

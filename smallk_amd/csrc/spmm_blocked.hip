@@ -10,6 +10,7 @@
 // entries stream past.  Every (block, column) pair leaves a partial sum; the consumers of the product add the nb slabs
 // (they read the right-hand side through a PartialView with S slabs anyway).
 #include "devutil.h"
+#include "switches.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -141,7 +142,7 @@ void free_blocked_csc(BlockedCsc* b)
 // number of row blocks for a gathered factor of `rows` rows (16 bytes each): 1 while it fits an L2 beside the streams
 int blocked_csc_blocks(i64 rows)
 {
-    static const int forced = [] { const char* e = getenv("SMK_SPMM_BLOCKS"); return e ? atoi(e) : 0; }();
+    const int forced = sw::spmm_blocks();
     if (forced == 1 || forced == 2 || forced == 4 || forced == 8) return forced;
     // measured on a 1 M x 1 M, 16 M-entry matrix (tools/gpu_round3_e.sh): the product itself 244 us unblocked, 191 us with
     // 4 blocks, 215 us with 8 -- but every consumer of the result reads one slab per block (solve 26 -> 31 -> 54 us,
@@ -201,9 +202,9 @@ int launch_spmm_blocked2(const BlockedCsc& b, const double* X, double* P, i64 nc
 {
     if (b.nb < 2 || b.ncols <= 0) return -100;
     const double avg = (double)b.nnz / ((double)b.ncols * b.nb);
-    static const int forced = [] { const char* e = getenv("SMK_SPMM_BLOCKED_LPC"); return e ? atoi(e) : 0; }();
+    const int forced = sw::spmm_blocked_lpc();
     const int lpc = forced ? forced : (avg <= 1.5 ? 1 : avg <= 3.0 ? 2 : avg <= 6.0 ? 4 : 8);
-    static const int unroll = [] { const char* e = getenv("SMK_SPMM_UNROLL"); return e ? atoi(e) : 1; }();
+    const int unroll = sw::spmm_unroll();
     const int U = unroll >= 4 ? 4 : unroll >= 2 ? 2 : 1;
     const i64 cpw = (256 / lpc) * U;                            // columns per workgroup
     const i64 tiles = (b.ncols + cpw - 1) / cpw;

@@ -20,6 +20,7 @@
 #include "devutil.h"
 #include "gram_inverse.h"
 #include "gram_body.h"
+#include "switches.h"
 
 namespace smk {
 
@@ -191,8 +192,8 @@ static int upload_vec(T** dst, const std::vector<T>& v, hipStream_t st)
 
 int spmm_seg_len()
 {
-    static const int seg = [] { const char* e = getenv("SMK_SPMM_SEG_LEN"); const int v = e ? atoi(e) : 64; return v < 8 ? 8 : v > 4096 ? 4096 : v; }();
-    return seg;
+    const int v = sw::spmm_seg_len();
+    return v < 8 ? 8 : v > 4096 ? 4096 : v;
 }
 
 int build_seg_plan(i64 ncols, i64 nnz, const i64* colptr, const unsigned* rowidx, SegPlan* out, hipStream_t st)
@@ -291,7 +292,7 @@ int launch_spmm_seg(const SegPlan& sp, const i64* colptr, const double* val, con
     }
     const unsigned grid = (unsigned)((sp.nseg + gpb - 1) / gpb) + (ride.G ? 1u : 0u) + (unsigned)gnblk;
     const double* v = val;
-    static const int ufix = [] { const char* e = getenv("SMK_SPMM_SEG_U"); return e ? atoi(e) : 0; }();
+    const int ufix = sw::spmm_seg_u();
 #define SMK_SEG(U)                                                                                                                  \
     KP_DISPATCH128(KPv, (sp.has_empty ? spmm_seg_kernel<KP, U, true><<<grid, 256, 0, st>>>(sp.seg_p0, sp.seg_len, sp.seg_col, sp.seg_piece, sp.nseg, colptr, sp.rowflag, v, X, P, kpp, pieces, ride, gram.X, gram.N, gcpw, gnblk, gram.Gp) \
                                       : spmm_seg_kernel<KP, U, false><<<grid, 256, 0, st>>>(sp.seg_p0, sp.seg_len, sp.seg_col, sp.seg_piece, sp.nseg, colptr, sp.rowflag, v, X, P, kpp, pieces, ride, gram.X, gram.N, gcpw, gnblk, gram.Gp)))

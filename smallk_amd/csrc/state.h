@@ -3,6 +3,7 @@
 // few functions that cross those files.
 #pragma once
 #include "common.h"
+#include "switches.h"
 #include "../../include/smallk_amd.h"
 
 #include <chrono>
@@ -41,8 +42,7 @@ static int dev_alloc(T** p, size_t count)
     SMK_HIP(smk::dev_malloc((void**)p, count * sizeof(T)));
     // debugging aid: SMK_POISON=1 fills every fresh workspace with 0xFF bytes (NaN as fp64 / fp32, -1 as int), so that a
     // kernel reading memory nobody wrote shows up in every run instead of once in a hundred
-    static const bool poison = [] { const char* e = getenv("SMK_POISON"); return e && atoi(e) != 0; }();
-    if (poison) { SMK_HIP(hipMemset(*p, 0xFF, count * sizeof(T))); SMK_HIP(hipDeviceSynchronize()); }   // the fill must not trail work on the non-blocking streams
+    if (sw::poison()) { SMK_HIP(hipMemset(*p, 0xFF, count * sizeof(T))); SMK_HIP(hipDeviceSynchronize()); }   // the fill must not trail work on the non-blocking streams
     return 0;
 }
 

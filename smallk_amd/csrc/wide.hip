@@ -9,6 +9,7 @@
 // passive block in LDS or in a global scratch panel).  Same arithmetic as the narrow kernels (reference file:line cited
 // there); the streaming products are the same kernels at every k (one pass over A per 64 factor rows).
 #include "devutil.h"
+#include "switches.h"
 
 #include <cfloat>
 
@@ -1598,8 +1599,7 @@ size_t nnls_wide_scratch_elems(int k, int num_cus, i64 ncols)
 // SMK_NNLS_INV=0: the direct form only (nnls_wide_kernel: the reference's own computation on the passive block)
 static inline bool wide_use_inverse()
 {
-    static const int mode = [] { const char* e = getenv("SMK_NNLS_INV"); return e ? atoi(e) : 1; }();
-    return mode != 0;
+    return sw::nnls_inv() != 0;
 }
 
 int launch_gram_inverse_wide(const double* G, int k, double* scratch, int num_cus, hipStream_t st)
@@ -1647,7 +1647,7 @@ int launch_nnls_bpp_wide(double* X, double* Y, int k, i64 col_begin, i64 col_end
     // invertible (direct form only: the reference's own computation, including its "not SPD" failure).
     int took_wave = 0;
     if (use_inv) {
-        static const int nw_env = [] { const char* e = getenv("SMK_WIDE_NW"); return e ? atoi(e) : 0; }();
+        const int nw_env = sw::wide_nw();
         const int tp_full = ((k + 1) / 2 + 15) / 16;
         // measured, 12 iterations at 16384 x 8192: k = 160 4.4 ms per iteration with a wave per column (three columns per CU)
         // against 5.0 with the workgroup on one; k = 192 6.2 against 5.8; k = 256 13.7 against 11.0
