@@ -1,6 +1,7 @@
 // smallk_amd/csrc/devmem.cpp -- a caching allocator in front of hipMalloc / hipFree.
 //
-// HierNMF2, flat clustering and repeated Nmf() calls create and destroy a solver (~35 device buffers), a column subset
+// HierNMF2, flat clustering and repeated Nmf() calls create and destroy a solver (13 - 20 device blocks at creation by
+// algorithm, about 45 with everything built on first use; its Owned member, owned.h, keeps the list), a column subset
 // (6 - 12) and sort workspaces per node; hipMalloc maps fresh pages and hipFree synchronises the device and unmaps them,
 // ~0.1 - 0.3 ms each: on the C5-shaped run (15 node factorisations) that was ~0.1 s of a 0.9 s run.  Freed blocks of up to
 // 512 MB are kept per device (at most 4 GB of them; SMK_DEVMEM_CACHE_MB) and handed out again to requests that fit (the smallest cached block
@@ -10,7 +11,7 @@
 //     (no kernel that still uses the memory can be in flight), at the cost of a sync on an idle device (~10 us);
 //   * a failed hipMalloc empties the device's cache and tries once more;
 //   * SMK_DEVMEM_CACHE=0 turns the cache off (every call goes to the runtime), SMK_POISON=1 still poisons every block a
-//     caller receives (dev_alloc in state.h), reused or fresh;
+//     caller receives (dev_alloc in owned.h), reused or fresh;
 //   * smk_finalize / smk_thread_context_end / smk_device_trim return the cached blocks of their device (dev_trim).
 #include "common.h"
 #include "switches.h"
@@ -23,7 +24,7 @@ namespace smk {
 
 namespace {
 constexpr size_t MAX_CACHED_BLOCK = (size_t)512 << 20;
-// per device.  4 GB covers the per-node workspaces this cache exists for (a solver's ~35 buffers, a subset's 6 - 12, the
+// per device.  4 GB covers the per-node workspaces this cache exists for (a solver's 13 - 45 blocks, a subset's 6 - 12, the
 // sort workspaces: < 1 GB on the C5-shaped run); what is parked here is invisible to the other allocators of the process
 // (torch, RCCL's channel buffers), so the cap is modest and adjustable (SMK_DEVMEM_CACHE_MB), and smk_device_trim() hands
 // everything back before a caller creates communicators or large torch tensors

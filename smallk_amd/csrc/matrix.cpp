@@ -12,6 +12,16 @@
 
 namespace smk {
 
+// a matrix of the calling thread's context, registered with it; nothing allocated yet
+static smk_matrix* new_matrix(i64 m, i64 n_global, i64 c0, i64 n, int storage, bool sparse = false, i64 nnz = 0)
+{
+    smk_matrix* a = new smk_matrix;
+    a->m = m; a->n_global = n_global; a->c0 = c0; a->n = n; a->storage = storage; a->sparse = sparse; a->nnz = nnz;
+    a->st = ctx().stream;
+    register_matrix(a);
+    return a;
+}
+
 // a single-copy matrix meets a consumer of the stored transpose (BPP, RANK2, the accurate form, column subsets): allocate and fill
 // it now; solvers already planned on the transposed source keep reading A (their plans say so)
 int matrix_materialize_transpose(const smk_matrix* ca)
@@ -22,7 +32,7 @@ int matrix_materialize_transpose(const smk_matrix* ca)
     if (!a->single || a->At) return 0;
     const size_t es = (size_t)elem_size(a->storage);
     hipStream_t st = a->st ? a->st : ctx().stream;
-    if (smk::dev_malloc(&a->At, (size_t)a->ldAt * a->colsAt * es) != hipSuccess) { a->At = nullptr; set_error("no memory for the stored transpose of a single-copy matrix"); return SMK_DEVICE_ERROR; }
+    if (a->own.dev((unsigned char**)&a->At, (size_t)a->ldAt * a->colsAt * es)) { set_error("no memory for the stored transpose of a single-copy matrix"); return SMK_DEVICE_ERROR; }
     SMK_HIP(hipMemsetAsync(a->At, 0, (size_t)a->ldAt * a->colsAt * es, st));
     const int rc = launch_transpose_store(a->A, a->ldA, a->At, a->ldAt, a->storage, a->m, a->n, st);
     if (rc) return rc;
@@ -53,13 +63,12 @@ int ensure_seg_plans(const smk_matrix* a)
 //   col_spread_log2 log2 of (largest / smallest non-zero column maximum): how far apart the column scales are
 int matrix_measure_scale(const smk_matrix* a, hipStream_t st)
 {
-    unsigned* d = nullptr;
-    SMK_HIP(smk::dev_malloc((void**)&d, 2 * sizeof(unsigned)));
+    Scratch<unsigned> d;
+    SMK_HIP(smk::dev_malloc(d.put(), 2 * sizeof(unsigned)));
     unsigned bits[2] = {0, 0};
     int rc = launch_colrange(a->A, a->storage, a->ldA, a->m, a->n, d, st);
     if (!rc && hipMemcpyAsync(bits, d, sizeof(bits), hipMemcpyDeviceToHost, st) != hipSuccess) rc = SMK_DEVICE_ERROR;
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = SMK_DEVICE_ERROR;
-    (void)smk::dev_free(d);
     if (rc) { set_error("could not measure max |A|"); return rc; }
     float mx, mn;
     memcpy(&mx, &bits[0], sizeof(mx));
@@ -81,14 +90,13 @@ int matrix_measure_scale(const smk_matrix* a, hipStream_t st)
 // (what bounds the NNLS solutions from above, NnlsPack)
 int matrix_measure_norms(const smk_matrix* a, hipStream_t st)
 {
-    double* d = nullptr;
-    SMK_HIP(smk::dev_malloc((void**)&d, 2 * sizeof(double)));
+    Scratch<double> d;
+    SMK_HIP(smk::dev_malloc(d.put(), 2 * sizeof(double)));
     double v[2] = {0.0, 0.0};
     int rc = launch_colnorm2_max(a->A, a->storage, a->ldA, a->m, a->n, d, st);
     if (!rc) rc = launch_colnorm2_max(a->At, a->storage, a->ldAt, a->n, a->m, d + 1, st);
     if (!rc && hipMemcpyAsync(v, d, sizeof(v), hipMemcpyDeviceToHost, st) != hipSuccess) rc = SMK_DEVICE_ERROR;
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = SMK_DEVICE_ERROR;
-    (void)smk::dev_free(d);
     if (rc) { set_error("could not measure the column / row norms of A"); return rc; }
     a->colnorm_max = std::sqrt(v[0]);
     a->rownorm_max = std::sqrt(v[1]);
@@ -109,10 +117,7 @@ int smk_matrix_create(smk_matrix** out, int64_t height, int64_t width_global, in
     if (height <= 0 || width_global <= 0 || ncols_local <= 0 || col0 < 0 || col0 + ncols_local > width_global ||
         (storage != SMK_STORE_F32 && storage != SMK_STORE_BF16))
         return SMK_BAD_PARAM;
-    smk_matrix* a = new smk_matrix;
-    a->m = height; a->n_global = width_global; a->c0 = col0; a->n = ncols_local; a->storage = storage;
-    a->st = ctx().stream;
-    register_matrix(a);
+    smk_matrix* a = new_matrix(height, width_global, col0, ncols_local, storage);
     // rows of A padded to COL_PAD, not ROW_PAD: a single-copy matrix is also read through the transposed source, whose tiles are
     // 128 ROWS of A and whose chunked passes (sharded runs, chunk_rows) run to round_up(m, COL_PAD) -- with 128-row padding a
     // height with 0 < m mod 256 <= 128 let the last tile read 128 rows past the column (the next column's data; past the
@@ -133,23 +138,15 @@ int smk_matrix_create(smk_matrix** out, int64_t height, int64_t width_global, in
     {   // SMK_SINGLE_COPY=1: dense matrices are created without the stored transpose (smk_matrix_create_single_copy asks for it explicitly)
         a->single = g_create_single || sw::single_copy();
     }
-    hipError_t e1 = smk::dev_malloc(&a->A, (size_t)a->ldA * a->colsA * es);
-    hipError_t e2 = (e1 == hipSuccess && !a->single) ? smk::dev_malloc(&a->At, (size_t)a->ldAt * a->colsAt * es) : e1;
-    if (e1 == hipSuccess && e2 != hipSuccess && !a->single) {
+    if (a->own.dev((unsigned char**)&a->A, (size_t)a->ldA * a->colsA * es)) { smk_matrix_destroy(a); return SMK_DEVICE_ERROR; }
+    if (!a->single && a->own.dev((unsigned char**)&a->At, (size_t)a->ldAt * a->colsAt * es)) {
         // A fits, A and A' together do not: the matrix becomes a single copy (MU, HALS and BPP with the 16-bit product forms run
         // on it as they are; RANK2 and the accurate form will ask for the transpose and report the allocation failure then)
         (void)hipGetLastError();
-        a->At = nullptr;
+        a->own.drop(&a->At);
         a->single = true;
-        e2 = hipSuccess;
     }
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        set_error(std::string("smk::dev_malloc(A): ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-        if (a->A) (void)smk::dev_free(a->A);
-        delete a;
-        return SMK_DEVICE_ERROR;
-    }
-    e1 = hipMemsetAsync(a->A, 0, (size_t)a->ldA * a->colsA * es, ctx().stream);
+    hipError_t e1 = hipMemsetAsync(a->A, 0, (size_t)a->ldA * a->colsA * es, ctx().stream);
     if (e1 == hipSuccess && a->At) e1 = hipMemsetAsync(a->At, 0, (size_t)a->ldAt * a->colsAt * es, ctx().stream);
     if (e1 != hipSuccess) {
         set_error(std::string("hipMemsetAsync(A): ") + hipGetErrorString(e1));
@@ -202,10 +199,9 @@ int smk_matrix_upload_f64(smk_matrix* a, const double* host, int64_t ld)
     i64 chunk = (i64)(budget / ((size_t)a->m * sizeof(double)));
     if (chunk < 1) chunk = 1;
     if (chunk > a->n) chunk = a->n;
-    double* stage = nullptr;
-    int rc = dev_alloc(&stage, (size_t)a->m * chunk);
+    Scratch<double> stage;
+    int rc = stage.alloc((size_t)a->m * chunk);
     if (rc) return rc;
-    struct Free { void* p; ~Free() { if (p) (void)smk::dev_free(p); } } stage_guard{stage};   // also on the error returns
     const size_t es = (size_t)elem_size(a->storage);
     for (i64 c = 0; c < a->n; c += chunk) {
         const i64 nc = (a->n - c < chunk) ? (a->n - c) : chunk;
@@ -281,9 +277,7 @@ void smk_matrix_destroy(smk_matrix* a)
     free_blocked_csc(&a->bAt);
     free_seg_plan(&a->segA);
     free_seg_plan(&a->segAt);
-    void* ptrs[] = {a->A, a->At, a->colptr, a->colptr_t, a->rowidx, a->rowidx_t, a->val, a->val_t};
-    for (void* p : ptrs)
-        if (p) (void)smk::dev_free(p);
+    a->own.release();
     delete a;
 }
 
@@ -294,19 +288,15 @@ int smk_matrix_clone(const smk_matrix* src, smk_matrix** out)
     if (!src || !out) return SMK_BAD_PARAM;
     *out = nullptr;
     if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
-    smk_matrix* a = new smk_matrix;
-    a->m = src->m; a->n_global = src->n_global; a->c0 = src->c0; a->n = src->n; a->storage = src->storage;
+    smk_matrix* a = new_matrix(src->m, src->n_global, src->c0, src->n, src->storage, src->sparse, src->nnz);
     a->ascale = src->ascale; a->col_spread_log2 = src->col_spread_log2;
     a->colnorm_max = src->colnorm_max; a->rownorm_max = src->rownorm_max;
     a->ldA = src->ldA; a->colsA = src->colsA; a->ldAt = src->ldAt; a->colsAt = src->colsAt;
-    a->sparse = src->sparse; a->nnz = src->nnz; a->single = src->single;
-    a->st = ctx().stream;
-    register_matrix(a);
+    a->single = src->single;
     bool ok = true;
     auto dup = [&](void** dst, const void* from, size_t bytes) {
         if (!ok || !from) return;
-        if (bytes == 0) bytes = 8;
-        if (smk::dev_malloc(dst, bytes) != hipSuccess || hipMemcpy(*dst, from, bytes, hipMemcpyDefault) != hipSuccess) ok = false;
+        if (a->own.dev((unsigned char**)dst, bytes) || hipMemcpy(*dst, from, bytes, hipMemcpyDefault) != hipSuccess) ok = false;
     };
     if (src->sparse) {
         dup((void**)&a->colptr, src->colptr, (size_t)(src->n + 1) * sizeof(i64));
@@ -357,10 +347,9 @@ int smk_matrix_sparse_product(const smk_matrix* a, int transposed, int k, const 
     std::vector<double> xp((size_t)rows * ldx_dev, 0.0), pp((size_t)ncols * kpp);
     for (i64 r = 0; r < rows; ++r)
         for (int c = 0; c < k; ++c) xp[(size_t)r * ldx_dev + c] = X[r * ldx + c];
-    double *dX = nullptr, *dP = nullptr;
-    int rc = dev_alloc(&dX, xp.size());
-    if (!rc) rc = dev_alloc(&dP, pp.size());
-    struct Free { double *&a, *&b; ~Free() { if (a) (void)smk::dev_free(a); if (b) (void)smk::dev_free(b); } } guard{dX, dP};
+    Scratch<double> dX, dP;
+    int rc = dX.alloc(xp.size());
+    if (!rc) rc = dP.alloc(pp.size());
     if (rc) return rc;
     SMK_HIP(hipMemcpyAsync(dX, xp.data(), xp.size() * sizeof(double), hipMemcpyHostToDevice, st));
     const i64* cp = transposed ? a->colptr_t : a->colptr;
@@ -374,17 +363,15 @@ int smk_matrix_sparse_product(const smk_matrix* a, int transposed, int k, const 
     rc = once();
     if (rc) return rc;
     if (reps > 0 && avg_ms) {
+        Owned timer;                        // the two events of this measurement
         hipEvent_t e0, e1;
-        SMK_HIP(hipEventCreate(&e0));
-        SMK_HIP(hipEventCreate(&e1));
+        if (timer.event(&e0, hipEventDefault) || timer.event(&e1, hipEventDefault)) return SMK_DEVICE_ERROR;
         SMK_HIP(hipEventRecord(e0, st));
         for (int i = 0; i < reps && !rc; ++i) rc = once();
         SMK_HIP(hipEventRecord(e1, st));
         SMK_HIP(hipEventSynchronize(e1));
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         *avg_ms = (double)ms / reps;
         if (rc) return rc;
     }
@@ -396,6 +383,13 @@ int smk_matrix_sparse_product(const smk_matrix* a, int transposed, int k, const 
 }
 int64_t smk_matrix_nnz(const smk_matrix* a) { return a ? a->nnz : 0; }
 int64_t smk_matrix_height(const smk_matrix* a) { return a ? a->m : 0; }
+
+// the six arrays of CSC(A) and CSC(A') for a->n columns, a->m rows and a->nnz entries
+static int alloc_csc(smk_matrix* a)
+{
+    return a->own.dev(&a->colptr, (size_t)a->n + 1) || a->own.dev(&a->colptr_t, (size_t)a->m + 1) || a->own.dev(&a->rowidx, (size_t)a->nnz) ||
+           a->own.dev(&a->rowidx_t, (size_t)a->nnz) || a->own.dev(&a->val, (size_t)a->nnz) || a->own.dev(&a->val_t, (size_t)a->nnz);
+}
 
 // CSC shard (columns [col0, col0+ncols_local) of a height x width_global matrix) -> HBM, plus the
 // CSC of its transpose built on the host by a counting sort (SparseMatrix::Transpose,
@@ -420,19 +414,8 @@ int smk_matrix_create_sparse(smk_matrix** out, int64_t height, int64_t width_glo
     }
     for (int64_t p = 0; p < nnz; ++p)
         if ((int64_t)row_indices[base + p] >= height) { set_error("row index out of range"); return SMK_BAD_PARAM; }
-    smk_matrix* a = new smk_matrix;
-    a->m = height; a->n_global = width_global; a->c0 = col0; a->n = ncols_local; a->storage = SMK_STORE_F32;
-    a->sparse = true; a->nnz = nnz;
-    a->st = ctx().stream;
-    register_matrix(a);
-    int rc = 0;
-    rc |= dev_alloc(&a->colptr, (size_t)ncols_local + 1);
-    rc |= dev_alloc(&a->colptr_t, (size_t)height + 1);
-    rc |= dev_alloc(&a->rowidx, (size_t)nnz);
-    rc |= dev_alloc(&a->rowidx_t, (size_t)nnz);
-    rc |= dev_alloc(&a->val, (size_t)nnz);
-    rc |= dev_alloc(&a->val_t, (size_t)nnz);
-    if (rc) { smk_matrix_destroy(a); return SMK_DEVICE_ERROR; }
+    smk_matrix* a = new_matrix(height, width_global, col0, ncols_local, SMK_STORE_F32, true, nnz);
+    if (alloc_csc(a)) { smk_matrix_destroy(a); return SMK_DEVICE_ERROR; }
     hipError_t e = hipMemcpy(a->colptr, cp.data(), cp.size() * sizeof(i64), hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz > 0) e = hipMemcpy(a->rowidx, row_indices + base, (size_t)nnz * sizeof(unsigned), hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz > 0) e = hipMemcpy(a->val, data + base, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice);
@@ -474,19 +457,8 @@ int matrix_create_sparse_device(smk_matrix** out, i64 height, i64 width, i64 nnz
     *out = nullptr;
     if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
     if (height <= 0 || width <= 0 || nnz < 0) { set_error("empty matrix"); return SMK_BAD_PARAM; }
-    smk_matrix* a = new smk_matrix;
-    a->m = height; a->n_global = width; a->c0 = 0; a->n = width; a->storage = SMK_STORE_F32;
-    a->sparse = true; a->nnz = nnz;
-    a->st = ctx().stream;
-    register_matrix(a);
-    int rc = 0;
-    rc |= dev_alloc(&a->colptr, (size_t)width + 1);
-    rc |= dev_alloc(&a->colptr_t, (size_t)height + 1);
-    rc |= dev_alloc(&a->rowidx, (size_t)nnz);
-    rc |= dev_alloc(&a->rowidx_t, (size_t)nnz);
-    rc |= dev_alloc(&a->val, (size_t)nnz);
-    rc |= dev_alloc(&a->val_t, (size_t)nnz);
-    if (rc) { smk_matrix_destroy(a); return SMK_DEVICE_ERROR; }
+    smk_matrix* a = new_matrix(height, width, 0, width, SMK_STORE_F32, true, nnz);
+    if (alloc_csc(a)) { smk_matrix_destroy(a); return SMK_DEVICE_ERROR; }
     if (fill(a->colptr, a->rowidx, a->val, ctx().stream) != 0 ||
         device_csc_transpose(height, width, nnz, a->colptr, a->rowidx, a->val, a->colptr_t, a->rowidx_t, a->val_t, ctx().stream) != 0) {
         smk_matrix_destroy(a);
@@ -533,8 +505,8 @@ int smk_matrix_gather_cols(const smk_matrix* src, const unsigned* cols, int64_t 
         smk_matrix* a = nullptr;
         int rc = smk_matrix_create(&a, src->m, ncols, 0, ncols, src->storage);
         if (rc) return rc;
-        unsigned* dcols = nullptr;
-        rc = dev_alloc(&dcols, (size_t)ncols);
+        Scratch<unsigned> dcols;
+        rc = dcols.alloc((size_t)ncols);
         if (rc) { smk_matrix_destroy(a); return rc; }
         const i64 es = elem_size(src->storage);
         hipError_t e = hipMemcpyAsync(dcols, cols, (size_t)ncols * sizeof(unsigned), hipMemcpyHostToDevice, ctx().stream);
@@ -543,7 +515,6 @@ int smk_matrix_gather_cols(const smk_matrix* src, const unsigned* cols, int64_t 
             if (!rc) rc = matrix_make_transpose(a);
             if (!rc) e = hipStreamSynchronize(ctx().stream);
         }
-        (void)smk::dev_free(dcols);
         if (e != hipSuccess) { set_error(std::string("gather_cols: ") + hipGetErrorString(e)); rc = SMK_DEVICE_ERROR; }
         if (rc) { smk_matrix_destroy(a); return rc; }
         if (new_to_old_rows) for (i64 r = 0; r < src->m; ++r) new_to_old_rows[r] = (unsigned)r;
@@ -566,13 +537,10 @@ int smk_matrix_gather_cols(const smk_matrix* src, const unsigned* cols, int64_t 
         if (!n2o) { n2o_tmp.resize((size_t)src->m); n2o = n2o_tmp.data(); }
         const int rc = device_sparse_subset(sd, cols, ncols, &od, n2o, ctx().stream);
         if (rc) return rc == -3 ? SMK_BAD_PARAM : SMK_DEVICE_ERROR;
-        smk_matrix* a = new smk_matrix;
-        a->m = od.m; a->n_global = ncols; a->c0 = 0; a->n = ncols; a->storage = SMK_STORE_F32;
-        a->sparse = true; a->nnz = od.nnz;
-        a->st = ctx().stream;
-        register_matrix(a);
+        smk_matrix* a = new_matrix(od.m, ncols, 0, ncols, SMK_STORE_F32, true, od.nnz);
         a->colptr = od.colptr; a->rowidx = od.rowidx; a->val = od.val;
         a->colptr_t = od.colptr_t; a->rowidx_t = od.rowidx_t; a->val_t = od.val_t;
+        for (void* p : {(void*)od.colptr, (void*)od.rowidx, (void*)od.val, (void*)od.colptr_t, (void*)od.rowidx_t, (void*)od.val_t}) a->own.adopt(p);
         if (new_height) *new_height = od.m;
         *out = a;
         return SMK_OK;

@@ -16,6 +16,7 @@
 
 #include "../../include/smallk_amd.h"
 #include "common.h"
+#include "owned.h"
 #include "preprocess.h"
 
 struct smk_preprocess_result {
@@ -139,12 +140,8 @@ int run(const smk_preprocess_options& o, unsigned height, unsigned width, unsign
     std::vector<unsigned> cp_host((size_t)width + 1);
     for (size_t c = 0; c <= width; ++c) cp_host[c] = col_offsets[c] - base;
 
-    unsigned *d_rows = nullptr, *d_unsorted = nullptr;
-    double* d_data = nullptr;
-    struct Input {
-        unsigned*& r; double*& d; unsigned*& u;
-        ~Input() { if (r) (void)smk::dev_free(r); if (d) (void)smk::dev_free(d); if (u) (void)smk::dev_free(u); }
-    } input{d_rows, d_data, d_unsorted};
+    smk::Scratch<unsigned> d_rows, d_unsorted;          // the input as uploaded: gone when this function returns
+    smk::Scratch<double> d_data;
     for (int h = 0; h < 2; ++h) {
         PP_TRY(alloc(&w.cp[h], (size_t)width + 1));
         PP_TRY(alloc(&w.ent[h], nnz));
@@ -163,9 +160,9 @@ int run(const smk_preprocess_options& o, unsigned height, unsigned width, unsign
     PP_TRY(alloc(&w.idx, width));
     PP_TRY(alloc(&w.idx_sorted, width));
     PP_TRY(alloc(&w.differ, (size_t)width + 1));
-    PP_TRY(alloc(&d_rows, nnz));
-    PP_TRY(alloc(&d_data, nnz));
-    PP_TRY(alloc(&d_unsorted, 1));
+    PP_TRY(alloc(d_rows.put(), nnz));
+    PP_TRY(alloc(d_data.put(), nnz));
+    PP_TRY(alloc(d_unsorted.put(), 1));
     PP_HIP(hipHostMalloc((void**)&w.host, 64));
 
     // the input upload: the copies alone (the working set above is allocated before the timer starts)
@@ -244,13 +241,12 @@ int run(const smk_preprocess_options& o, unsigned height, unsigned width, unsign
     nnz = w.host[0];
 
     // scores on the final matrix; the result takes the current halves
-    double* idf = nullptr;
-    PP_TRY(alloc(&idf, (size_t)height + 1));
-    const int rc_alloc = alloc(&res->score, nnz);
-    if (rc_alloc) { (void)smk::dev_free(idf); return SMK_DEVICE_ERROR; }
+    smk::Scratch<double> idf;
+    PP_TRY(alloc(idf.put(), (size_t)height + 1));
+    PP_TRY(alloc(&res->score, nnz));
     const int rc_sc = smk::pp_scores(w.cp[w.a], w.ent[w.a], width, w.stat[w.a], height, idf, res->score, w.st);
     const hipError_t e = hipStreamSynchronize(w.st);
-    (void)smk::dev_free(idf);
+    idf.reset();
     if (rc_sc) return SMK_DEVICE_ERROR;
     if (e != hipSuccess) { smk::set_error(std::string("preprocess scores: ") + hipGetErrorString(e)); return SMK_DEVICE_ERROR; }
     res->device_ms = now_ms() - t1;
@@ -339,10 +335,10 @@ int smk_preprocess_result_download(const smk_preprocess_result* r, unsigned* ter
     if (!r) return SMK_BAD_PARAM;
     if (r->failed) { smk::set_error("preprocess: every column was pruned"); return SMK_FAILURE; }
     const hipStream_t st = smk::context_stream(nullptr);
-    unsigned* rows = nullptr;
+    smk::Scratch<unsigned> rows;
     if (row_indices && r->nnz > 0) {
-        if (smk::dev_malloc((void**)&rows, (size_t)r->nnz * 4) != hipSuccess) { smk::set_error("preprocess: hipMalloc"); return SMK_DEVICE_ERROR; }
-        if (smk::pp_export(r->cp, r->width, r->ent, r->nnz, nullptr, rows, st)) { (void)smk::dev_free(rows); return SMK_DEVICE_ERROR; }
+        if (smk::dev_malloc(rows.put(), (size_t)r->nnz * 4) != hipSuccess) { smk::set_error("preprocess: hipMalloc"); return SMK_DEVICE_ERROR; }
+        if (smk::pp_export(r->cp, r->width, r->ent, r->nnz, nullptr, rows, st)) return SMK_DEVICE_ERROR;
     }
     hipError_t e = hipSuccess;
     auto D2H = [&](void* dst, const void* src, size_t bytes) {
@@ -354,7 +350,6 @@ int smk_preprocess_result_download(const smk_preprocess_result* r, unsigned* ter
     D2H(row_indices, rows, (size_t)r->nnz * 4);
     D2H(scores, r->score, (size_t)r->nnz * 8);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (rows) (void)smk::dev_free(rows);
     if (e != hipSuccess) { smk::set_error(std::string("preprocess download: ") + hipGetErrorString(e)); return SMK_DEVICE_ERROR; }
     return SMK_OK;
 }

@@ -123,8 +123,8 @@ static int plan_products(smk_solver* s)
     if (s->nsplit == NSPLIT_F16X2) {
         int rc = 0;
         for (int side = 0; side < 2 && !rc; ++side) {
-            if (!s->xscale[side]) rc |= dev_alloc(&s->xscale[side], (size_t)MAX_K);
-            if (!s->oscale[side]) rc |= dev_alloc(&s->oscale[side], (size_t)MAX_K);
+            if (!s->xscale[side]) rc |= s->own.dev(&s->xscale[side], (size_t)MAX_K);
+            if (!s->oscale[side]) rc |= s->own.dev(&s->oscale[side], (size_t)MAX_K);
         }
         if (rc) return SMK_DEVICE_ERROR;
         for (int g = 0; g < s->ng; ++g) {
@@ -147,15 +147,13 @@ static int plan_products(smk_solver* s)
 static int alloc_product_buffers(smk_solver* s)
 {
     int rc = 0;
-    void** bufs[] = {&s->packW, &s->packH, (void**)&s->P1, (void**)&s->P2};
-    for (void** b : bufs)
-        if (*b) { (void)smk::dev_free(*b); *b = nullptr; }
+    s->own.drop(&s->packW); s->own.drop(&s->packH); s->own.drop(&s->P1); s->own.drop(&s->P2);      // a re-plan sizes them anew
     if (!s->a->sparse) {
-        rc |= dev_alloc((unsigned char**)&s->packW, packed_bytes(s->a->storage, s->k, s->m, s->nsplit));
-        rc |= dev_alloc((unsigned char**)&s->packH, packed_bytes(s->a->storage, s->k, s->n, s->nsplit));
+        rc |= s->own.dev((unsigned char**)&s->packW, packed_bytes(s->a->storage, s->k, s->m, s->nsplit));
+        rc |= s->own.dev((unsigned char**)&s->packH, packed_bytes(s->a->storage, s->k, s->n, s->nsplit));
     }
-    rc |= dev_alloc(&s->P1, s->pl1.p_elems);
-    rc |= dev_alloc(&s->P2, s->pl2.p_elems);
+    rc |= s->own.dev(&s->P1, s->pl1.p_elems);
+    rc |= s->own.dev(&s->P2, s->pl2.p_elems);
     return rc;
 }
 
@@ -257,10 +255,10 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
     }
 
     const size_t kk = (size_t)s->KP * s->KP;
-    rc |= dev_alloc(&s->H, (size_t)s->KP * s->n);
-    rc |= dev_alloc(&s->Wt_own, (size_t)s->KP * s->m);
-    rc |= dev_alloc(&s->Gw, kk);
-    rc |= dev_alloc(&s->Gh_own, kk);
+    rc |= s->own.dev(&s->H, (size_t)s->KP * s->n);
+    rc |= s->own.dev(&s->Wt, (size_t)s->KP * s->m);
+    rc |= s->own.dev(&s->Gw, kk);
+    rc |= s->own.dev(&s->Gh, kk);
     {
         size_t gs = gram_scratch_elems(s->k, GRAM_BLOCKS);
         if (opts->algorithm == SMK_ALG_HALS && !a->sparse && (s->KP == 16 || s->KP == 32)) {
@@ -269,41 +267,41 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
             if (need <= 4096) { s->hals_ep_blocks = (int)std::max<i64>(need, 1); gs = std::max(gs, gram_scratch_elems(s->k, s->hals_ep_blocks)); }
         }
         if (s->KP == 16 && opts->algorithm == SMK_ALG_BPP) gs = std::max(gs, (size_t)NNLS_GRAM_MAX * (256 + 16) + 8);   // partials from the NNLS launch
-        rc |= dev_alloc(&s->gram_scratch, gs);
+        rc |= s->own.dev(&s->gram_scratch, gs);
         if (s->o.algorithm == SMK_ALG_RANK2) {
             const size_t e1 = rank2_gram_scratch_elems(std::max(s->m, s->n)), e2 = rank2_progress_scratch_elems(s->m, s->n);
-            rc |= dev_alloc(&s->r2_scratch, e1);
-            rc |= dev_alloc(&s->r2_prog, e2);
-            rc |= dev_alloc(&s->Graw, (size_t)s->KP * s->KP);
-            if (a->sparse) { rc |= dev_alloc(&s->Hc, (size_t)2 * s->n); rc |= dev_alloc(&s->Wc, (size_t)2 * s->m); }
+            rc |= s->own.dev(&s->r2_scratch, e1);
+            rc |= s->own.dev(&s->r2_prog, e2);
+            rc |= s->own.dev(&s->Graw, (size_t)s->KP * s->KP);
+            if (a->sparse) { rc |= s->own.dev(&s->Hc, (size_t)2 * s->n); rc |= s->own.dev(&s->Wc, (size_t)2 * s->m); }
 
         }
         if (!rc && hipMemsetAsync(s->gram_scratch, 0, gs * sizeof(double), s->st) != hipSuccess) rc |= 1;   // incl. the ticket word
     }
-    rc |= dev_alloc(&s->tmpW, (size_t)s->KP * s->m);
-    if (is_wide(s->k)) rc |= dev_alloc(&s->wide_tmp, (size_t)s->KP * std::max(s->m, s->n));
+    rc |= s->own.dev(&s->tmpW, (size_t)s->KP * s->m);
+    if (is_wide(s->k)) rc |= s->own.dev(&s->wide_tmp, (size_t)s->KP * std::max(s->m, s->n));
     // one partial per workgroup of the column-tile kernels (grid = N*(KP/4)/256 blocks) and at most
     // 2 x 512 for delta_fnorm
     s->pg_half = (size_t)((std::max(s->m, s->n) * (s->KP / 4) + 255) / 256) + 1024;
     if (is_wide(s->k)) s->pg_half = std::max(s->pg_half, (size_t)((std::max(s->m, s->n) + 3) / 4) + 1024);   // one partial per 4 columns
-    rc |= dev_alloc(&s->pg_partials, 2 * s->pg_half);
-    rc |= dev_alloc(&s->scal_own, (size_t)8);
-    rc |= dev_alloc(&s->fail_flag, (size_t)1);
+    rc |= s->own.dev(&s->pg_partials, 2 * s->pg_half);
+    rc |= s->own.dev(&s->scal, (size_t)8);
+    rc |= s->own.dev(&s->fail_flag, (size_t)1);
     rc |= alloc_product_buffers(s);
     if (opts->algorithm == SMK_ALG_HALS) {
-        rc |= dev_alloc(&s->hals_scratch, hals_w_scratch_elems(s->k, s->m));
-        rc |= dev_alloc(&s->W0c, (size_t)s->KP * s->m);
-        rc |= dev_alloc(&s->H0c, (size_t)s->KP * s->n);
+        rc |= s->own.dev(&s->hals_scratch, hals_w_scratch_elems(s->k, s->m));
+        rc |= s->own.dev(&s->W0c, (size_t)s->KP * s->m);
+        rc |= s->own.dev(&s->H0c, (size_t)s->KP * s->n);
         if (!rc) rc = hals_w_scratch_init(s->hals_scratch, s->k, s->m, s->st);
     }
     if (s->pack_in_solve && !s->W0c) {      // pack_fail_soft goes back to the initial factors
-        rc |= dev_alloc(&s->W0c, (size_t)s->KP * s->m);
-        rc |= dev_alloc(&s->H0c, (size_t)s->KP * s->n);
+        rc |= s->own.dev(&s->W0c, (size_t)s->KP * s->m);
+        rc |= s->own.dev(&s->H0c, (size_t)s->KP * s->n);
     }
     if (opts->algorithm == SMK_ALG_BPP) {
         // k <= 128: two (inverse + selector) halves; above: one Cholesky panel per resident workgroup (wide.hip)
-        rc |= dev_alloc(&s->nnls_scratch, nnls_uses_tiles(s->k) ? nnls_wide_scratch_elems(s->k, ctx().cus, std::max(s->m, s->n)) : 2 * nnls_scratch_elems(s->k));
-        if (s->KP == 64 && !nnls_uses_tiles(s->k)) rc |= dev_alloc(&s->nnls_defer, nnls_defer_elems(std::max(s->m, s->n)));
+        rc |= s->own.dev(&s->nnls_scratch, nnls_uses_tiles(s->k) ? nnls_wide_scratch_elems(s->k, ctx().cus, std::max(s->m, s->n)) : 2 * nnls_scratch_elems(s->k));
+        if (s->KP == 64 && !nnls_uses_tiles(s->k)) rc |= s->own.dev(&s->nnls_defer, nnls_defer_elems(std::max(s->m, s->n)));
         // (above k = 128 the inverse stays in stream order: beside the product it gained 1-2 % -- measured -- and the two sides
         // share one scratch there)
         // The second stream pays two event hops per solve (~8 us each way on the main stream): worth it where it hides the 47 us
@@ -313,18 +311,15 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
         const int inv_env = sw::inv_stream();
         const bool inv_beside = inv_env >= 0 ? inv_env != 0 : (!a->sparse && s->KP >= 64);
         if (inv_beside && (s->KP >= 64 || (s->KP == 32 && nnls_inverse_at_32())) && !nnls_uses_tiles(s->k)) {
-            if (hipStreamCreateWithFlags(&s->st_inv, hipStreamNonBlocking) != hipSuccess) rc |= 1;
+            rc |= s->own.stream(&s->st_inv, hipStreamNonBlocking);
             for (int i = 0; i < 2 && !rc; ++i) {
-                if (hipEventCreateWithFlags(&s->ev_g[i], hipEventDisableTiming) != hipSuccess) rc |= 1;
-                if (hipEventCreateWithFlags(&s->ev_inv[i], hipEventDisableTiming) != hipSuccess) rc |= 1;
+                rc |= s->own.event(&s->ev_g[i], hipEventDisableTiming);
+                rc |= s->own.event(&s->ev_inv[i], hipEventDisableTiming);
             }
         }
     }
-    if (opts->prog_est_algorithm == SMK_PROG_DELTA_FNORM) rc |= dev_alloc(&s->Wprev, (size_t)s->KP * s->m);
+    if (opts->prog_est_algorithm == SMK_PROG_DELTA_FNORM) rc |= s->own.dev(&s->Wprev, (size_t)s->KP * s->m);
     if (rc) { smk_solver_destroy(s); return SMK_DEVICE_ERROR; }
-    s->Gh = s->Gh_own;
-    s->scal = s->scal_own;
-    s->Wt = s->Wt_own;
     *out = s;
     return SMK_OK;
 }
@@ -332,45 +327,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
 void smk_solver_destroy(smk_solver* s)
 {
     if (!s) return;
-    if (s->st2) (void)hipStreamSynchronize(s->st2);
-    if (s->st_inv) (void)hipStreamSynchronize(s->st_inv);
-    void* ptrs[] = {s->H, s->Wt_own, s->Gw, s->Gh_own, s->gram_scratch, s->tmpW, s->pg_partials, s->scal_own,
-                    s->fail_flag, s->packW, s->packH, s->P1, s->P2, s->hals_scratch, s->Wprev, s->tmpH, s->nnls_scratch, s->W0c, s->H0c,
-                    s->xscale[0], s->xscale[1], s->oscale[0], s->oscale[1], s->r2_scratch, s->r2_prog, s->Graw, s->Hc, s->Wc, s->wide_tmp};
-    for (void* p : ptrs)
-        if (p) (void)smk::dev_free(p);
-    for (int w = 0; w < 6; ++w)
-        for (auto& e : s->ev[w]) { (void)hipEventDestroy(e.e0); (void)hipEventDestroy(e.e1); }
-    if (s->ev_cal) (void)hipEventDestroy(s->ev_cal);
-    for (int b = 0; b < smk_solver::PROG_SLOTS; ++b) {
-        if (s->snap[b]) (void)smk::dev_free(s->snap[b]);
-        if (s->pev[b]) (void)hipEventDestroy(s->pev[b]);
-    }
-    if (s->pin) (void)hipHostFree(s->pin);
-    { void* gq[] = {s->guard_As, s->guard_cols, s->guard_P, s->guard_dev}; for (void* q : gq) if (q) (void)smk::dev_free(q); }
-    if (s->guard_pin) (void)hipHostFree(s->guard_pin);
-    if (s->guard_ev) (void)hipEventDestroy(s->guard_ev);
-    { void* r2p[] = {s->r2p_hc1, s->r2p_r2c, s->r2p_part, s->r2p_out, s->r2p_sync}; for (void* q : r2p) if (q) (void)smk::dev_free(q); }
-    if (s->r2p_pin) (void)hipHostFree(s->r2p_pin);
-    for (int b = 0; b < smk_solver::PROG_SLOTS; ++b) if (s->pin_r2[b]) (void)hipHostFree(s->pin_r2[b]);
-    for (int b = 0; b < 2; ++b) if (s->seg_pieces[b]) (void)smk::dev_free(s->seg_pieces[b]);
-    if (s->nnls_defer) (void)smk::dev_free(s->nnls_defer);
-    if (s->comm_ws) (void)smk::dev_free(s->comm_ws);
-    if (s->Wown) (void)smk::dev_free(s->Wown);
-    if (s->R2own) (void)smk::dev_free(s->R2own);
-    if (s->st2) (void)hipStreamDestroy(s->st2);
-    if (s->st_inv) (void)hipStreamDestroy(s->st_inv);
-    for (int i = 0; i < 2; ++i) {
-        if (s->ev_g[i]) (void)hipEventDestroy(s->ev_g[i]);
-        if (s->ev_inv[i]) (void)hipEventDestroy(s->ev_inv[i]);
-    }
-    hipEvent_t single[] = {s->ev_gram, s->ev_gh, s->ev_x, s->ev_y};
-    for (hipEvent_t e : single) if (e) (void)hipEventDestroy(e);
-    for (int j = 0; j < MAX_CHUNKS; ++j) {
-        if (s->ev_c[j]) (void)hipEventDestroy(s->ev_c[j]);
-        if (s->ev_r[j]) (void)hipEventDestroy(s->ev_r[j]);
-        if (s->ev_a[j]) (void)hipEventDestroy(s->ev_a[j]);
-    }
+    s->own.release();
     --ctx().live_solvers;
     delete s;
 }
@@ -405,14 +362,13 @@ int smk_solver_set_comm(smk_solver* s, int rank, int world, smk_allreduce_fn fn,
     if (s->comm) { set_error("a native communicator is attached"); return SMK_BAD_PARAM; }
     s->rank = rank; s->world = world;
     if (fn && (!workspace || workspace_bytes < comm_bytes(s))) return SMK_BAD_PARAM;
-    s->ar = fn; s->ar_user = user;
     if (fn) {
+        if (!s->ar) { s->home[0] = s->Gh; s->home[1] = s->scal; s->home[2] = s->Wt; }      // still in the handle's own blocks: remember the way back
         carve_workspace(s, workspace);
-    } else {
-        s->Gh = s->Gh_own;
-        s->scal = s->scal_own;
-        s->Wt = s->Wt_own;
+    } else if (s->ar) {
+        s->Gh = s->home[0]; s->scal = s->home[1]; s->Wt = s->home[2];
     }
+    s->ar = fn; s->ar_user = user;
     return SMK_OK;
 }
 
@@ -437,11 +393,11 @@ int smk_solver_attach_comm(smk_solver* s, smk_comm* comm)
     // Every rank of the communicator calls attach, so this is a collective like the ones that follow.
     if (comm->world > 1) {
         double want = s->nsplit == NSPLIT_F64 ? 1.0 : 0.0;
-        SMK_HIP(hipMemcpy(s->scal_own, &want, sizeof(double), hipMemcpyHostToDevice));
-        int arc = comm_allreduce(comm, s->scal_own, 1, 1, s->st);
+        SMK_HIP(hipMemcpy(s->scal, &want, sizeof(double), hipMemcpyHostToDevice));
+        int arc = comm_allreduce(comm, s->scal, 1, 1, s->st);
         if (arc) { s->comm = nullptr; return arc; }
         SMK_HIP(hipStreamSynchronize(s->st));
-        SMK_HIP(hipMemcpy(&want, s->scal_own, sizeof(double), hipMemcpyDeviceToHost));
+        SMK_HIP(hipMemcpy(&want, s->scal, sizeof(double), hipMemcpyDeviceToHost));
         if (want > 0.0 && s->nsplit != NSPLIT_F64 && !s->a->sparse) {
             s->nsplit = NSPLIT_F64;
             arc = plan_products(s);
@@ -474,26 +430,24 @@ int smk_solver_attach_comm(smk_solver* s, smk_comm* comm)
     // chunk in place of the packed operand -- prod1_sharded)
     s->w_sharded = (s->o.algorithm == SMK_ALG_BPP || s->o.algorithm == SMK_ALG_MU) && !s->a->sparse && (s->world > 1 || comm_forced());
     const size_t bytes = comm_bytes(s);
-    if (smk::dev_malloc(&s->comm_ws, bytes) != hipSuccess) { s->comm = nullptr; s->w_sharded = false; set_error("smk::dev_malloc(comm workspace)"); return SMK_DEVICE_ERROR; }
+    if (s->own.dev((unsigned char**)&s->comm_ws, bytes)) { s->comm = nullptr; s->w_sharded = false; set_error("no memory for the communicator workspace"); return SMK_DEVICE_ERROR; }
     SMK_HIP(hipMemsetAsync(s->comm_ws, 0, bytes, s->st));
     carve_workspace(s, s->comm_ws);
     if (!s->a->sparse && s->pl2.S == 1 && s->red_f64) {
         // one row split and fp64 on the wire: the partial products ARE the send buffer.  They get room for the equal
         // blocks of the last chunk (rows past the padded row count are never written and stay zero).
-        if (s->P2) (void)smk::dev_free(s->P2);
-        s->P2 = nullptr;
+        s->own.drop(&s->P2);
         const size_t pe = (size_t)comm_rows(s) * s->kpp;
-        if (dev_alloc(&s->P2, pe)) return SMK_DEVICE_ERROR;
+        if (s->own.dev(&s->P2, pe)) return SMK_DEVICE_ERROR;
         SMK_HIP(hipMemsetAsync(s->P2, 0, pe * sizeof(double), s->st));
         s->R2red = (float*)s->P2;
         s->r2_alias = true;
     }
     if (s->w_sharded) {
         // the packed operand of W is gathered in equal blocks: room for rows_cap rows, groups laid out for that length
-        if (s->packW) (void)smk::dev_free(s->packW);
-        s->packW = nullptr;
+        s->own.drop(&s->packW);
         const size_t pb = packed_bytes(s->a->storage, s->k, s->rows_cap, s->nsplit);
-        if (dev_alloc((unsigned char**)&s->packW, pb)) return SMK_DEVICE_ERROR;
+        if (s->own.dev((unsigned char**)&s->packW, pb)) return SMK_DEVICE_ERROR;
         SMK_HIP(hipMemsetAsync(s->packW, 0, pb, s->st));
         size_t off = 0;
         for (int g = 0; g < s->ng; ++g) {
@@ -503,8 +457,8 @@ int smk_solver_attach_comm(smk_solver* s, smk_comm* comm)
         s->pl1.pack_offset = s->pg1[0].pack_offset;
         const size_t own_rows = (size_t)s->nchunk * s->blk;
         const size_t rb = s->red_f64 ? sizeof(double) : sizeof(float);
-        if (dev_alloc(&s->Wown, own_rows * s->KP)) return SMK_DEVICE_ERROR;
-        if (dev_alloc((unsigned char**)&s->R2own, own_rows * s->kpp * rb)) return SMK_DEVICE_ERROR;
+        if (s->own.dev(&s->Wown, own_rows * s->KP)) return SMK_DEVICE_ERROR;
+        if (s->own.dev((unsigned char**)&s->R2own, own_rows * s->kpp * rb)) return SMK_DEVICE_ERROR;
         SMK_HIP(hipMemsetAsync(s->Wown, 0, own_rows * s->KP * sizeof(double), s->st));
         SMK_HIP(hipMemsetAsync(s->R2own, 0, own_rows * s->kpp * rb, s->st));
         s->n_own = 0;
@@ -514,14 +468,11 @@ int smk_solver_attach_comm(smk_solver* s, smk_comm* comm)
             if (b > a) s->n_own += b - a;
         }
     }
-    SMK_HIP(hipStreamCreateWithFlags(&s->st2, hipStreamNonBlocking));
-    hipEvent_t* evs[] = {&s->ev_gram, &s->ev_gh, &s->ev_x, &s->ev_y};
-    for (hipEvent_t* e : evs) SMK_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    for (int j = 0; j < MAX_CHUNKS; ++j) {
-        SMK_HIP(hipEventCreateWithFlags(&s->ev_c[j], hipEventDisableTiming));
-        SMK_HIP(hipEventCreateWithFlags(&s->ev_r[j], hipEventDisableTiming));
-        SMK_HIP(hipEventCreateWithFlags(&s->ev_a[j], hipEventDisableTiming));
-    }
+    int erc = s->own.stream(&s->st2, hipStreamNonBlocking);
+    for (hipEvent_t* e : {&s->ev_gram, &s->ev_gh, &s->ev_x, &s->ev_y}) erc |= s->own.event(e, hipEventDisableTiming);
+    for (int j = 0; j < MAX_CHUNKS; ++j)
+        for (hipEvent_t* e : {&s->ev_c[j], &s->ev_r[j], &s->ev_a[j]}) erc |= s->own.event(e, hipEventDisableTiming);
+    if (erc) return SMK_DEVICE_ERROR;
     // nothing is allocated once the collectives are in flight (several ranks may live in one process)
     return progress_prealloc(s);
 }
@@ -627,6 +578,16 @@ static int dist_allreduce_cb(smk_solver* s, void* ptr, i64 count, int f64)
     return 0;
 }
 
+// A pair of timing events for one span of smk_solver_kernel_time: a pair whose times resolve_events has read, else a new one
+// from the owner.  The caller records both and pushes the span onto s->ev[slot], or hands it back to s->span_pool.
+static int span_open(smk_solver* s, smk_solver::TimedSpan* sp, int counts = 1)
+{
+    if (!s->span_pool.empty()) { *sp = s->span_pool.back(); s->span_pool.pop_back(); }
+    else if (s->own.event(&sp->e0, hipEventDefault) || s->own.event(&sp->e1, hipEventDefault)) return SMK_DEVICE_ERROR;
+    sp->counts = counts;
+    return 0;
+}
+
 // native communicator: st2 picks up after everything enqueued on the main stream so far
 static int comm_fork(smk_solver* s, hipEvent_t ev)
 {
@@ -641,35 +602,33 @@ static int comm_fork(smk_solver* s, hipEvent_t ev)
 static int main_waits_for_comm(smk_solver* s, const hipEvent_t* evs, int n)
 {
     const bool timed = s->timing && (s->pass_timed[0] || s->pass_timed[1]);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    smk_solver::TimedSpan sp{};
     if (timed && (s->cal_counter++ & 3u) == 0 && s->st2) {        // every fourth bracket is preceded by a calibration bracket
         if (!s->ev_cal) {
-            SMK_HIP(hipEventCreateWithFlags(&s->ev_cal, hipEventDisableTiming));
+            if (s->own.event(&s->ev_cal, hipEventDisableTiming)) return SMK_DEVICE_ERROR;
             SMK_HIP(hipEventRecord(s->ev_cal, s->st2));
         } else {
-            hipEvent_t c0 = nullptr, c1 = nullptr;
-            SMK_HIP(hipEventCreate(&c0));
-            if (hipEventCreate(&c1) != hipSuccess) { (void)hipEventDestroy(c0); set_error("hipEventCreate failed"); return SMK_DEVICE_ERROR; }
-            (void)hipEventRecord(c0, s->st);
+            smk_solver::TimedSpan cal{};
+            if (span_open(s, &cal)) return SMK_DEVICE_ERROR;
+            (void)hipEventRecord(cal.e0, s->st);
             (void)hipStreamWaitEvent(s->st, s->ev_cal, 0);
-            (void)hipEventRecord(c1, s->st);
-            s->ev[4].push_back({c0, c1, 1});
+            (void)hipEventRecord(cal.e1, s->st);
+            s->ev[4].push_back(cal);
         }
     }
     if (timed) {
-        SMK_HIP(hipEventCreate(&e0));
-        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_error("hipEventCreate failed"); return SMK_DEVICE_ERROR; }
-        (void)hipEventRecord(e0, s->st);
+        if (span_open(s, &sp)) return SMK_DEVICE_ERROR;
+        (void)hipEventRecord(sp.e0, s->st);
     }
     for (int i = 0; i < n; ++i)
         if (hipStreamWaitEvent(s->st, evs[i], 0) != hipSuccess) {
-            if (timed) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
+            if (timed) s->span_pool.push_back(sp);
             set_error("hipStreamWaitEvent failed");
             return SMK_DEVICE_ERROR;
         }
     if (timed) {
-        (void)hipEventRecord(e1, s->st);
-        s->ev[3].push_back({e0, e1, 1});
+        (void)hipEventRecord(sp.e1, s->st);
+        s->ev[3].push_back(sp);
     }
     return 0;
 }
@@ -684,14 +643,13 @@ static int comm_join(smk_solver* s, hipEvent_t ev)
 static int timed_collective(smk_solver* s, int pass, const std::function<int()>& issue)
 {
     if (!s->timing || !s->pass_timed[pass]) return issue();
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    SMK_HIP(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_error("hipEventCreate failed"); return SMK_DEVICE_ERROR; }
-    (void)hipEventRecord(e0, s->st2);
+    smk_solver::TimedSpan sp{};
+    if (span_open(s, &sp)) return SMK_DEVICE_ERROR;
+    (void)hipEventRecord(sp.e0, s->st2);
     const int rc = issue();
-    if (rc) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
-    (void)hipEventRecord(e1, s->st2);
-    s->ev[2].push_back({e0, e1, 1});
+    if (rc) { s->span_pool.push_back(sp); return rc; }
+    (void)hipEventRecord(sp.e1, s->st2);
+    s->ev[2].push_back(sp);
     return 0;
 }
 
@@ -794,6 +752,12 @@ static bool check_rides_in_nnls(const smk_solver* s)
     return (s->n + gpb - 1) / gpb <= (i64)s->pg_half;          // one partial per workgroup of the H-side launch
 }
 
+// the snapshot (W, H, W'W) of progress slot b, allocated when a check first needs it
+static inline int ensure_snapshot(smk_solver* s, int b)
+{
+    return s->snap[b] ? 0 : s->own.dev(&s->snap[b], snapshot_elems(s->k, s->m, s->n));
+}
+
 static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, PartialView R, const double* G)
 {
     if (s->inv_pending[side]) {
@@ -825,12 +789,10 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
     }
     s->nnls_packed[fx] = false;
     // slot 5 of smk_solver_kernel_time: the block-pivoting launches (both kernels of a k > 16 solve), sampled with the pass that fed them
-    hipEvent_t te0 = nullptr, te1 = nullptr;
-    if (s->timing && s->pass_timed[side] && c1 > c0) {
-        if (hipEventCreate(&te0) == hipSuccess && hipEventCreate(&te1) == hipSuccess) (void)hipEventRecord(te0, s->st);
-        else { if (te0) (void)hipEventDestroy(te0); te0 = te1 = nullptr; }
-    }
-    struct Stamp { smk_solver* s; hipEvent_t a, b; ~Stamp() { if (a) { (void)hipEventRecord(b, s->st); s->ev[5].push_back({a, b, 1}); } } } stamp{s, te0, te1};
+    smk_solver::TimedSpan tsp{};
+    if (s->timing && s->pass_timed[side] && c1 > c0 && span_open(s, &tsp) == 0) (void)hipEventRecord(tsp.e0, s->st);
+    else tsp.e1 = nullptr;                      // (a launch that cannot be timed still runs)
+    struct Stamp { smk_solver* s; smk_solver::TimedSpan sp; ~Stamp() { if (sp.e1) { (void)hipEventRecord(sp.e1, s->st); s->ev[5].push_back(sp); } } } stamp{s, tsp};
     // riders of the checked loop (check_rides_in_nnls): the previous iteration's projected-gradient sum, this iteration's snapshot
     NnlsRiders rd;
     bool riders = false;
@@ -839,7 +801,7 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
         if (side == 0 && s->pg_defer_slot >= 0) { rd.pg_part = s->pg_partials + s->pg_half; rd.pg_nblk = &s->pg_defer_nblk; riders = true; }
         if (s->iter_snap_slot >= 0) {
             const int b = s->iter_snap_slot;
-            if (!s->snap[b]) { const int arc = dev_alloc(&s->snap[b], snapshot_elems(s->k, s->m, s->n)); if (arc) return arc; }
+            const int arc = ensure_snapshot(s, b); if (arc) return arc;
             rd.snap_x = s->snap[b] + (side == 0 ? (size_t)s->m * k2 : 0);        // snapshot_kernel's layout: [W'][H][W'W]
             rd.k2 = k2;
             riders = true;
@@ -886,15 +848,14 @@ static int timed_bigprod(smk_solver* s, int which, const BigProdPlan& pl_in, con
     }
     s->inv_ride[which] = false;
     if (s->timing && s->pass_timed[which]) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        SMK_HIP(hipEventCreate(&e0));
-        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_error("hipEventCreate failed"); return SMK_DEVICE_ERROR; }
-        s->ev[which].push_back({e0, e1, counts});   // owned by the solver from here on (destroyed with it)
-        SMK_HIP(hipEventRecord(e0, s->st));
+        smk_solver::TimedSpan sp{};
+        if (span_open(s, &sp, counts)) return SMK_DEVICE_ERROR;
+        s->ev[which].push_back(sp);
+        SMK_HIP(hipEventRecord(sp.e0, s->st));
         int rc = launch_bigprod(pl, B, ldb, Xp, P, s->st);
         if (rc == 1) { s->inv_done[which] = true; rc = 0; }        // the launch carried the inverse
-        if (rc) { s->ev[which].pop_back(); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
-        SMK_HIP(hipEventRecord(e1, s->st));
+        if (rc) { s->ev[which].pop_back(); s->span_pool.push_back(sp); return rc; }
+        SMK_HIP(hipEventRecord(sp.e1, s->st));
         return 0;
     }
     int rc = launch_bigprod(pl, B, ldb, Xp, P, s->st);
@@ -906,12 +867,11 @@ static int timed_bigprod(smk_solver* s, int which, const BigProdPlan& pl_in, con
 static int timed_spmm(smk_solver* s, int which, const i64* colptr, const unsigned* rowidx, const double* val, i64 ncols,
                       const double* X, int ldx, double* P)
 {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    smk_solver::TimedSpan sp{};
     const bool timed = s->timing && s->pass_timed[which];
     if (timed) {
-        SMK_HIP(hipEventCreate(&e0));
-        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_error("hipEventCreate failed"); return SMK_DEVICE_ERROR; }
-        (void)hipEventRecord(e0, s->st);
+        if (span_open(s, &sp)) return SMK_DEVICE_ERROR;
+        (void)hipEventRecord(sp.e0, s->st);
     }
     int rc;
     const BlockedCsc& blk = (which == 0) ? s->a->bA : s->a->bAt;
@@ -932,8 +892,7 @@ static int timed_spmm(smk_solver* s, int which, const i64* colptr, const unsigne
     if (ldx == 2 && blk.nb > 1) rc = launch_spmm_blocked2(blk, X, P, which == 0 ? s->pl1.ncols_pad : s->pl2.ncols_pad, s->st);
     else if (seg_route) {
         // the partial sums of long columns live in the SOLVER (two solvers on one sparse matrix run on their own streams)
-        if (seg.npieces > 0 && !s->seg_pieces[which] && smk::dev_malloc((void**)&s->seg_pieces[which], (size_t)seg.npieces * 128 * sizeof(double)) != hipSuccess) {
-            s->seg_pieces[which] = nullptr;
+        if (seg.npieces > 0 && !s->seg_pieces[which] && s->own.dev(&s->seg_pieces[which], (size_t)seg.npieces * 128)) {
             set_error("no memory for the long-column partial sums");
             return SMK_DEVICE_ERROR;
         }
@@ -947,9 +906,9 @@ static int timed_spmm(smk_solver* s, int which, const i64* colptr, const unsigne
     else rc = launch_spmm_gather(colptr, rowidx, val, ncols, s->a->nnz, X, ldx, s->k, P, s->kpp, s->st, &ride);
     if (rc == 1) { s->inv_done[which] = true; rc = 0; }             // the launch carried the inverse
     if (timed) {
-        if (rc) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
-        (void)hipEventRecord(e1, s->st);
-        s->ev[which].push_back({e0, e1, 1});
+        if (rc) { s->span_pool.push_back(sp); return rc; }
+        (void)hipEventRecord(sp.e1, s->st);
+        s->ev[which].push_back(sp);
     }
     return rc;
 }
@@ -1408,9 +1367,8 @@ static int resolve_events(smk_solver* s)
             SMK_HIP(hipEventElapsedTime(&ms, e.e0, e.e1));
             s->acc_ms[w] += (double)ms;                                // sampled totals; smk_solver_kernel_time scales them by passes seen / passes sampled
             s->launches[w] += e.counts;
-            (void)hipEventDestroy(e.e0);
-            (void)hipEventDestroy(e.e1);
         }
+        s->span_pool.insert(s->span_pool.end(), s->ev[w].begin(), s->ev[w].end());      // read: span_open hands them out again
         s->ev[w].clear();
     }
     return 0;
@@ -1499,27 +1457,29 @@ static int update_progress(smk_solver* s, int iter_index, double* metric)
 }
 
 // ---- the same evaluation, one iteration late ------------------------------------------------
+// the pinned result slots and their events, on first use
+static int ensure_progress_slots(smk_solver* s)
+{
+    if (s->pin) return 0;
+    int rc = s->own.pinned((void**)&s->pin, smk_solver::PROG_SLOTS * sizeof(smk_solver::ProgSlot));
+    for (int i = 0; i < smk_solver::PROG_SLOTS && !rc; ++i) rc = s->own.event(&s->pev[i], hipEventDisableTiming);
+    return rc;
+}
 // Enqueue the progress kernels of the iteration that has just been enqueued, copy their scalars and
 // the failure flag into pinned slot `b` and record an event; when `snapshot` is set also keep
 // (W, H, W'W) of this iteration so that the NEXT, speculatively enqueued iteration can be undone.
+// (sharded runs: everything a checked iteration needs, before the collectives start)
 static int progress_prealloc(smk_solver* s)
 {
-    if (!s->pin) {
-        SMK_HIP(hipHostMalloc((void**)&s->pin, smk_solver::PROG_SLOTS * sizeof(smk_solver::ProgSlot)));
-        for (int i = 0; i < smk_solver::PROG_SLOTS; ++i) SMK_HIP(hipEventCreateWithFlags(&s->pev[i], hipEventDisableTiming));
-    }
-    for (int b = 0; b < 2; ++b)            // a sharded run keeps ONE check in flight (two slots)
-        if (!s->snap[b]) { const int rc = dev_alloc(&s->snap[b], snapshot_elems(s->k, s->m, s->n)); if (rc) return rc; }
-    return 0;
+    int rc = ensure_progress_slots(s);
+    for (int b = 0; b < 2 && !rc; ++b) rc = ensure_snapshot(s, b);            // a sharded run keeps ONE check in flight (two slots)
+    return rc;
 }
 
 static int progress_begin(smk_solver* s, int b, bool snapshot, bool allow_defer = true)
 {
-    if (!s->pin) {
-        SMK_HIP(hipHostMalloc((void**)&s->pin, smk_solver::PROG_SLOTS * sizeof(smk_solver::ProgSlot)));
-        for (int i = 0; i < smk_solver::PROG_SLOTS; ++i) SMK_HIP(hipEventCreateWithFlags(&s->pev[i], hipEventDisableTiming));
-    }
-    int rc = wait_r2(s);
+    int rc = s->pin ? 0 : ensure_progress_slots(s);
+    if (!rc) rc = wait_r2(s);
     if (rc) return rc;
     s->poll_tag[b] = 0.0;
     s->pin[b].h[7] = 0.0;
@@ -1535,9 +1495,9 @@ static int progress_begin(smk_solver* s, int b, bool snapshot, bool allow_defer 
     ++s->check_routes[1];
     if (s->o.algorithm == SMK_ALG_RANK2 && s->o.prog_est_algorithm == SMK_PROG_PG_RATIO && !is_dist(s)) {
         // one launch: both gradient sums, the failure flag and the snapshot (rank2.hip)
-        if (snapshot && !s->snap[b]) { rc = dev_alloc(&s->snap[b], snapshot_elems(s->k, s->m, s->n)); if (rc) return rc; }
+        if (snapshot) { rc = ensure_snapshot(s, b); if (rc) return rc; }
         const size_t pe = rank2_progress_scratch_elems(s->m, s->n);
-        if (!s->pin_r2[b]) SMK_HIP(hipHostMalloc((void**)&s->pin_r2[b], pe * sizeof(double)));
+        if (!s->pin_r2[b] && s->own.pinned((void**)&s->pin_r2[b], pe * sizeof(double))) return SMK_DEVICE_ERROR;
         rc = launch_rank2_progress(s->Wt, s->m, view2(s), s->Gh, s->H, s->n, view1(s), s->Gw, s->r2_prog, s->fail_flag,
                                    snapshot ? s->snap[b] : nullptr, s->st);
         if (rc) return rc;
@@ -1553,7 +1513,7 @@ static int progress_begin(smk_solver* s, int b, bool snapshot, bool allow_defer 
     if (fused_check && s->o.prog_est_algorithm == SMK_PROG_PG_RATIO && !is_dist(s) && !is_wide(s->k) && !s->w_sharded) {
         // round 6: gradients + snapshot in one launch, sums + failure flag written into the pinned slot by a second (kernels.hip:
         // grad_pg2_snap_kernel, sum_partials2_host_kernel); SMK_PROGRESS_FUSED=0: the four stream operations of before
-        if (snapshot && !s->snap[b]) { rc = dev_alloc(&s->snap[b], snapshot_elems(s->k, s->m, s->n)); if (rc) return rc; }
+        if (snapshot) { rc = ensure_snapshot(s, b); if (rc) return rc; }
         const double tag = progress_polls() ? (double)(s->iter + 1) : 0.0;
         rc = launch_grad_pg2_fused(s->Wt, s->m, view2(s), s->Gh, s->pg_partials, s->H, s->n, view1(s), s->Gw, s->pg_partials + s->pg_half,
                                    s->k, s->scal, s->fail_flag, 5, snapshot ? s->snap[b] : nullptr, s->pin[b].h, s->st,
@@ -1579,7 +1539,7 @@ static int progress_begin(smk_solver* s, int b, bool snapshot, bool allow_defer 
         SMK_HIP(hipMemcpyAsync(&s->pin[b].flag, s->fail_flag, sizeof(int), hipMemcpyDeviceToHost, s->st));
     }
     if (snapshot) {
-        if (!s->snap[b]) { rc = dev_alloc(&s->snap[b], snapshot_elems(s->k, s->m, s->n)); if (rc) return rc; }
+        rc = ensure_snapshot(s, b); if (rc) return rc;
         rc = s->w_sharded ? launch_snapshot(s->Wown, s->n_own, s->H, s->n, s->Gw, s->snap[b], s->k, 1, s->st)
                           : launch_snapshot(s->Wt, s->m, s->H, s->n, s->Gw, s->snap[b], s->k, 1, s->st);
         if (rc) return rc;
@@ -1830,9 +1790,9 @@ static int guard_enqueue(smk_solver* s)
         std::vector<unsigned> cols((size_t)nc);
         for (int i = 0; i < nc; ++i) cols[(size_t)i] = (unsigned)((i64)i * s->n / nc);
         const i64 es = elem_size(s->a->storage);
-        int rc = dev_alloc(&s->guard_cols, (size_t)nc);
-        rc |= dev_alloc((unsigned char**)&s->guard_As, (size_t)s->a->ldA * COL_PAD * es);
-        rc |= dev_alloc(&s->guard_dev, 2 + 2 * kk);
+        int rc = s->own.dev(&s->guard_cols, (size_t)nc);
+        rc |= s->own.dev((unsigned char**)&s->guard_As, (size_t)s->a->ldA * COL_PAD * es);
+        rc |= s->own.dev(&s->guard_dev, 2 + 2 * kk);
         if (rc) return SMK_DEVICE_ERROR;
         SMK_HIP(hipMemsetAsync(s->guard_As, 0, (size_t)s->a->ldA * COL_PAD * es, s->st));
         SMK_HIP(hipMemcpyAsync(s->guard_cols, cols.data(), (size_t)nc * sizeof(unsigned), hipMemcpyHostToDevice, s->st));
@@ -1841,9 +1801,9 @@ static int guard_enqueue(smk_solver* s)
         SMK_HIP(hipStreamSynchronize(s->st));              // `cols` leaves scope
         const int ng = plan_bigprod_groups(s->a->storage, s->k, s->m, nc, NSPLIT_F64, ctx().cus, s->guard_pl);
         for (int g = 0; g < ng; ++g) s->guard_pl[g].ldx = s->KP;
-        if (dev_alloc(&s->guard_P, s->guard_pl[0].p_elems)) return SMK_DEVICE_ERROR;
-        SMK_HIP(hipHostMalloc((void**)&s->guard_pin, (2 + 2 * kk) * sizeof(double)));
-        SMK_HIP(hipEventCreateWithFlags(&s->guard_ev, hipEventDisableTiming));
+        if (s->own.dev(&s->guard_P, s->guard_pl[0].p_elems) || s->own.pinned((void**)&s->guard_pin, (2 + 2 * kk) * sizeof(double)) ||
+            s->own.event(&s->guard_ev, hipEventDisableTiming))
+            return SMK_DEVICE_ERROR;
         s->guard_ncols = nc;
     }
     // the full fp64 W (s->Wt) against the sampled columns, one launch per group of 64 factor rows
@@ -2009,13 +1969,13 @@ static int rank2_persist_run(smk_solver* s, int* status, int* count)
     // launch-per-kernel loop from the state solver.Init left)
     if (sw::r2p_test_abort()) { *status = R2P_ABORTED; return 0; }
     if (!s->r2p_sync) {
-        int rc = dev_alloc(&s->r2p_hc1, (size_t)2 * s->n);
-        rc |= dev_alloc(&s->r2p_r2c, (size_t)2 * s->m);
-        rc |= dev_alloc(&s->r2p_part, (size_t)3 * 8 * 1024);                  // three arrays of [workgroups <= 1024][8]
-        rc |= dev_alloc(&s->r2p_out, (size_t)16);
-        rc |= dev_alloc((unsigned char**)&s->r2p_sync, rank2_persist_sync_bytes());
+        int rc = s->own.dev(&s->r2p_hc1, (size_t)2 * s->n);
+        rc |= s->own.dev(&s->r2p_r2c, (size_t)2 * s->m);
+        rc |= s->own.dev(&s->r2p_part, (size_t)3 * 8 * 1024);                  // three arrays of [workgroups <= 1024][8]
+        rc |= s->own.dev(&s->r2p_out, (size_t)16);
+        rc |= s->own.pinned((void**)&s->r2p_pin, 16 * sizeof(double));
+        rc |= s->own.dev((unsigned char**)&s->r2p_sync, rank2_persist_sync_bytes());           // last: its presence says the set is complete
         if (rc) return SMK_DEVICE_ERROR;
-        SMK_HIP(hipHostMalloc((void**)&s->r2p_pin, 16 * sizeof(double)));
     }
     R2PersistArgs a;
     a.colptr = s->a->colptr; a.rowidx = s->a->rowidx; a.val = s->a->val;
@@ -2277,18 +2237,16 @@ int smk_nnls_blockpivot(int k, int64_t ncols, const double* LHS, int64_t ldL, co
             hr[(size_t)c * KP + r] = RHS[(size_t)c * ldR + r];
             hx[(size_t)c * KP + r] = X[(size_t)c * ldX + r];
         }
-    double *dg = nullptr, *dr = nullptr, *dx = nullptr, *dy = nullptr, *dscratch = nullptr;
-    int* dflag = nullptr;
-    int rc = 0;
-    rc |= dev_alloc(&dg, hg.size());
-    rc |= dev_alloc(&dr, hr.size());
-    rc |= dev_alloc(&dx, hx.size());
-    rc |= dev_alloc(&dy, hx.size());
-    rc |= dev_alloc(&dscratch, nnls_uses_tiles(k) ? nnls_wide_scratch_elems(k, ctx().cus, ncols) : nnls_scratch_elems(k));
-    rc |= dev_alloc(&dflag, (size_t)1);
-    unsigned* ddefer = nullptr;
-    if (KP == 64 && !nnls_uses_tiles(k)) rc |= dev_alloc(&ddefer, nnls_defer_elems(ncols));
-    struct Free { std::vector<void*> p; ~Free() { for (void* q : p) if (q) (void)smk::dev_free(q); } } guard{{dg, dr, dx, dy, dscratch, dflag, ddefer}};
+    Scratch<double> dg, dr, dx, dy, dscratch;
+    Scratch<int> dflag;
+    Scratch<unsigned> ddefer;
+    int rc = dg.alloc(hg.size());
+    rc |= dr.alloc(hr.size());
+    rc |= dx.alloc(hx.size());
+    rc |= dy.alloc(hx.size());
+    rc |= dscratch.alloc(nnls_uses_tiles(k) ? nnls_wide_scratch_elems(k, ctx().cus, ncols) : nnls_scratch_elems(k));
+    rc |= dflag.alloc(1);
+    if (KP == 64 && !nnls_uses_tiles(k)) rc |= ddefer.alloc(nnls_defer_elems(ncols));
     if (rc) return SMK_DEVICE_ERROR;
     const int big = INT_MAX;
     SMK_HIP(hipMemcpyAsync(dg, hg.data(), hg.size() * sizeof(double), hipMemcpyHostToDevice, ctx().stream));
@@ -2333,7 +2291,7 @@ int smk_solver_get_factors(smk_solver* s, int normalize, double* W, int64_t ldW,
     if (s->k == s->KP && ldH == s->k) {
         SMK_HIP(hipMemcpyAsync(H, s->H, (size_t)s->k * s->n * sizeof(double), hipMemcpyDeviceToHost, s->st));
     } else {
-        if (!s->tmpH) { rc = dev_alloc(&s->tmpH, (size_t)s->k * s->n); if (rc) return rc; }
+        if (!s->tmpH) { rc = s->own.dev(&s->tmpH, (size_t)s->k * s->n); if (rc) return rc; }
         rc = launch_compact_rows(s->H, s->KP, s->tmpH, s->k, s->n, s->st);
         if (rc) return rc;
         if (ldH == s->k) {
@@ -2490,13 +2448,13 @@ int smk_nmf_dense_sharded(const smk_options* opts, const double* A, int64_t ldA,
         if (wrc == SMK_OK) wrc = smk_solver_set_factors(s, Wcopy.data(), m, H + (size_t)c0 * ldH, ldH);
         // a shard that failed before the first collective would strand the others: agree on the setup first
         {
-            double ok = (wrc == SMK_OK) ? 0.0 : 1.0, *dflag = nullptr;
-            if (smk::dev_malloc((void**)&dflag, sizeof(double)) == hipSuccess) {
+            double ok = (wrc == SMK_OK) ? 0.0 : 1.0;
+            Scratch<double> dflag;
+            if (smk::dev_malloc(dflag.put(), sizeof(double)) == hipSuccess) {
                 (void)hipMemcpy(dflag, &ok, sizeof(double), hipMemcpyHostToDevice);
                 (void)comm_allreduce(comms[(size_t)r], dflag, 1, 1, ctx().stream);
                 (void)hipStreamSynchronize(ctx().stream);
                 (void)hipMemcpy(&ok, dflag, sizeof(double), hipMemcpyDeviceToHost);
-                (void)smk::dev_free(dflag);
             }
             if (ok != 0.0 && wrc == SMK_OK) wrc = SMK_FAILURE;
         }

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "switches.h"
+#include "owned.h"
 #include "../../include/smallk_amd.h"
 
 #include <chrono>
@@ -32,18 +33,6 @@ static inline double wall_us()
 {
     using namespace std::chrono;
     return (double)duration_cast<nanoseconds>(steady_clock::now().time_since_epoch()).count() * 1e-3;
-}
-
-template <typename T>
-static int dev_alloc(T** p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0) count = 1;
-    SMK_HIP(smk::dev_malloc((void**)p, count * sizeof(T)));
-    // debugging aid: SMK_POISON=1 fills every fresh workspace with 0xFF bytes (NaN as fp64 / fp32, -1 as int), so that a
-    // kernel reading memory nobody wrote shows up in every run instead of once in a hundred
-    if (sw::poison()) { SMK_HIP(hipMemset(*p, 0xFF, count * sizeof(T))); SMK_HIP(hipDeviceSynchronize()); }   // the fill must not trail work on the non-blocking streams
-    return 0;
 }
 
 static const int MAX_CHUNKS = 8;
@@ -82,6 +71,7 @@ struct smk_matrix {
     mutable bool seg_tried = false;
     mutable std::vector<unsigned> h_colptr, h_rowidx;     // fetched on first use (ensure_host_csc)
     mutable std::vector<double> h_val;
+    mutable smk::Owned own;                          // every device block above (the lazily built stored transpose included); the blocked CSC and the segment plans free themselves
 };
 
 struct smk_solver {
@@ -90,6 +80,7 @@ struct smk_solver {
     int k = 0, KP = 0, kpp = 0, nsplit = 3;
     i64 m = 0, n = 0;
     hipStream_t st = nullptr;
+    smk::Owned own;                       // every device block, pinned block, event and stream below was created through it and is released by it alone
     double *H = nullptr, *Wt = nullptr, *Gw = nullptr, *Gh = nullptr, *gram_scratch = nullptr;
     double* seg_pieces[2] = {nullptr, nullptr};     // sparse A, spmm_seg.hip: partial sums of the long columns of pass 0 / 1
     double *Wprev = nullptr, *hals_scratch = nullptr, *pg_partials = nullptr, *scal = nullptr, *tmpW = nullptr;
@@ -146,7 +137,6 @@ struct smk_solver {
     double *W0c = nullptr, *H0c = nullptr;
     bool hals_multi = false;
     int hals_calls = 0;
-    double *Gh_own = nullptr, *scal_own = nullptr, *Wt_own = nullptr;
     void *packW = nullptr, *packH = nullptr;
     double *P1 = nullptr, *P2 = nullptr;
     float* R2red = nullptr;
@@ -161,6 +151,7 @@ struct smk_solver {
     // comm: a native communicator (RCCL or the in-process stand-in, comm.cpp) or -- test hook -- a host callback
     int rank = 0, world = 1;
     smk_allreduce_fn ar = nullptr;
+    double* home[3] = {nullptr, nullptr, nullptr};   // callback hook: where Gh / scal / Wt pointed before smk_solver_set_comm moved them into the caller's workspace
     void* ar_user = nullptr;
     smk_comm* comm = nullptr;
     void* comm_ws = nullptr;              // owned workspace when a native communicator is attached
@@ -207,6 +198,7 @@ struct smk_solver {
     // 4: the same bracket around a wait for an event that completed long ago -- what a bracket costs by itself (three packets
     // through the command processor, ~15 us): exposure = slot 3 - brackets x the average of slot 4
     std::vector<TimedSpan> ev[6];       // 0 / 1: the passes, 2 - 4: collectives, waits, calibration, 5: the block-pivoting launches
+    std::vector<TimedSpan> span_pool;   // event pairs whose times have been read (resolve_events): span_open hands them out again
     double acc_ms[6] = {0, 0, 0, 0, 0, 0};
     int launches[6] = {0, 0, 0, 0, 0, 0};
     hipEvent_t ev_cal = nullptr;          // recorded once on the collective stream
