@@ -168,6 +168,34 @@ int smk_matrix_sparse_product(const smk_matrix* a, int transposed, int k, const 
                               int64_t ldo, int reps, double* avg_ms);
 int64_t smk_matrix_nnz(const smk_matrix* a);
 int64_t smk_matrix_height(const smk_matrix* a);
+
+/* ---- data that is already in device memory (a torch tensor: data_ptr(), stride(), the current stream) -------------------------
+ * A view is a pointer, an element type and one stride per dimension IN ELEMENTS (>= 0; 0 only for inputs); any layout is taken,
+ * row-major and column-major ones at copy rate.  `stream` is the HIP stream on which the caller produced the data or will consume
+ * the result (0: the null stream): the entry records an event there, the library's stream waits for it, the work runs on the
+ * library's stream, and the entry returns after that stream has been synchronised -- a source may be freed or overwritten, and an
+ * output read from any stream, as soon as the call returns.  Checked before anything is launched (SMK_BAD_PARAM + smk_last_error):
+ * null pointers, the element type, the strides, that the pointer is device memory of the current device, and that the strided
+ * extent stays inside its allocation.
+ * Rounding is that of smk_matrix_upload_f64 applied to the same values widened to fp64: to fp32 round-to-nearest-even, then (bf16
+ * storage) to bf16 round-to-nearest-even; fp16 / bf16 sources widen exactly. */
+enum { SMK_DT_F64 = 0, SMK_DT_F32 = 1, SMK_DT_BF16 = 2, SMK_DT_F16 = 3 };
+enum { SMK_IDX_I32 = 0, SMK_IDX_I64 = 1 };
+/* device twin of smk_matrix_upload_f64 (dense; `src` is the local height x ncols_local block): A and the stored transpose are
+ * written from one read of the source */
+int smk_matrix_adopt_device(smk_matrix* a, const void* src, int dtype, int64_t row_stride, int64_t col_stride, void* stream);
+/* the stored values of a dense matrix into a strided device buffer (device twin of smk_matrix_download_f64) */
+int smk_matrix_copy_to_device(const smk_matrix* a, void* dst, int dtype, int64_t row_stride, int64_t col_stride, void* stream);
+/* CSC arrays in device memory: width + 1 offsets starting at 0, nnz row indices and values (fp64 / fp32 / bf16 / fp16).  A kernel
+ * checks the index arrays (offsets monotone, spanning nnz and below 2^32; row indices < height) before anything consumes them; bad
+ * arrays give SMK_BAD_PARAM.  The same matrix as smk_matrix_create_sparse on the same arrays. */
+int smk_matrix_create_sparse_device(smk_matrix** out, int64_t height, int64_t width, int64_t nnz, const void* col_offsets, int idx_type,
+                                    const void* row_indices, int row_idx_type, const void* values, int dtype, void* stream);
+/* 1 when a rows x cols view with these strides, of elements of elem_size bytes, starting offset_bytes into an allocation of
+ * alloc_bytes, stays inside it; 0 when it does not (or the arithmetic leaves 64 bits); the check behind the entries above */
+int smk_strided_extent_fits(int64_t rows, int64_t cols, int64_t row_stride, int64_t col_stride, int64_t elem_size, int64_t offset_bytes,
+                            int64_t alloc_bytes);
+
 /* same generator on the host, for W0/H0 (RandomMatrix stand-in, smallk.cpp:533,554) */
 void smk_uniform_fill_host(double* buf, int64_t ld, int64_t rows, int64_t cols, int64_t r0, int64_t c0,
                            int64_t global_height, uint64_t seed, int quant /* 0: 24 bit, 1: bf16 */);
@@ -194,6 +222,12 @@ int smk_solver_sync(smk_solver* s); /* wait + report solver failures (Result cod
 int smk_solver_progress(smk_solver* s, double* metric);
 /* optional final NormalizeAndScale (normalize.hpp:118-140), then copy factors to the host */
 int smk_solver_get_factors(smk_solver* s, int normalize, double* W, int64_t ldW, double* H, int64_t ldH);
+/* the same two with the factors in device memory (views as above; SMK_DT_F64 or SMK_DT_F32, fp32 output is the fp64 factor
+ * rounded to nearest even): W is m x k, H is k x ncols_local */
+int smk_solver_set_factors_device(smk_solver* s, const void* W0, int dtypeW, int64_t rsW, int64_t csW, const void* H0, int dtypeH,
+                                  int64_t rsH, int64_t csH, void* stream);
+int smk_solver_get_factors_device(smk_solver* s, int normalize, void* W, int dtypeW, int64_t rsW, int64_t csW, void* H, int dtypeH,
+                                  int64_t rsH, int64_t csH, void* stream);
 int smk_solver_iteration_count(const smk_solver* s);
 /* the product form in use (SMK_NSPLIT numbering: 3 = bf16x3, 4 = fp16 two-term, 8 = the accurate fp64 form) and what the
  * opt-in run-time guard (BPP, SMK_GUARD_EVERY=n) has done so far: every n iterations it compares the fast form with the

@@ -18,6 +18,8 @@ DEVICE_ERROR, UNSUPPORTED = -100, -101
 ALG_MU, ALG_HALS, ALG_RANK2, ALG_BPP = 0, 1, 2, 3
 PROG_PG_RATIO, PROG_DELTA_FNORM = 0, 1
 STORE_F32, STORE_BF16 = 0, 1
+DT_F64, DT_F32, DT_BF16, DT_F16 = 0, 1, 2, 3          # element types of views in device memory (SMK_DT_*)
+IDX_I32, IDX_I64 = 0, 1
 
 RESULT_NAMES = {0: "OK", -1: "NOTINITIALIZED", -2: "INITIALIZED", -3: "BAD_PARAM", -4: "FAILURE",
                 -5: "SIZE_TOO_LARGE", -6: "FLATCLUST_FAILURE", -100: "DEVICE_ERROR", -101: "UNSUPPORTED"}
@@ -81,6 +83,10 @@ SYMBOLS = {
     "smk_matrix_fill_uniform": (C.c_int, [_vp, C.c_uint64]),
     "smk_matrix_fill_planted": (C.c_int, [_vp, C.c_uint64, C.c_int, C.c_double, C.c_double]),
     "smk_matrix_download_f64": (C.c_int, [_vp, _dp, _i64]),
+    "smk_matrix_adopt_device": (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _vp]),
+    "smk_matrix_copy_to_device": (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _vp]),
+    "smk_matrix_create_sparse_device": (C.c_int, [C.POINTER(_vp), _i64, _i64, _i64, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
+    "smk_strided_extent_fits": (C.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, _i64]),
     "smk_matrix_destroy": (None, [_vp]),
     "smk_matrix_clone": (C.c_int, [_vp, C.POINTER(_vp)]),
     "smk_thread_context_begin": (C.c_int, [C.c_int]),
@@ -115,6 +121,8 @@ SYMBOLS = {
     "smk_solver_sync": (C.c_int, [_vp]),
     "smk_solver_progress": (C.c_int, [_vp, _dp]),
     "smk_solver_get_factors": (C.c_int, [_vp, C.c_int, _dp, _i64, _dp, _i64]),
+    "smk_solver_set_factors_device": (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp]),
+    "smk_solver_get_factors_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp]),
     "smk_solver_iteration_count": (C.c_int, [_vp]),
     "smk_solver_product_form": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp]),
     "smk_nnls_blockpivot": (C.c_int, [C.c_int, _i64, _dp, _i64, _dp, _i64, _dp, _i64, _dp, _i64]),

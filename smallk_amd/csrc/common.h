@@ -119,6 +119,27 @@ int launch_gather_cols(const void* src, i64 ld_src_bytes, const unsigned* cols_d
                        i64 ld_dst_bytes, i64 col_bytes, hipStream_t st);
 int launch_transpose_f64(const double* src, i64 ld_src, double* dst, i64 ld_dst, i64 rows, i64 cols, hipStream_t st);
 
+// ---- adopt.hip: strided views in device memory (a torch tensor's data_ptr and strides) <-> the library's layouts ----------
+// element and index types of such views (= SMK_DT_* / SMK_IDX_* of include/smallk_amd.h)
+enum { DT_F64 = 0, DT_F32 = 1, DT_BF16 = 2, DT_F16 = 3 };
+enum { IDX_I32 = 0, IDX_I64 = 1 };
+inline int dtype_size(int dt) { return dt == DT_F64 ? 8 : dt == DT_F32 ? 4 : (dt == DT_BF16 || dt == DT_F16) ? 2 : 0; }
+// dst(r, c) = src(r, c) converted; strides in elements, >= 0 (a source stride may be 0).  To fp64 exactly, to the narrower types
+// through fp32, round-to-nearest-even at each step.  64 x 64 tiles read along the source's unit-stride dimension and written along
+// the destination's (through LDS when they differ); a plain kernel when either side has no unit stride.
+int launch_strided_convert(const void* src, int src_dtype, i64 src_rs, i64 src_cs, void* dst, int dst_dtype, i64 dst_rs, i64 dst_cs,
+                           i64 rows, i64 cols, hipStream_t st);
+// the stored A (leading dimension ldA) and, unless At is null, the stored transpose from ONE read of the source; same values as
+// launch_convert_f64 + launch_transpose_store of the source widened to fp64.  Pads are not written.
+int launch_adopt_dense(const void* src, int src_dtype, i64 src_rs, i64 src_cs, void* A, i64 ldA, void* At, i64 ldAt, int storage, i64 rows,
+                       i64 cols, hipStream_t st);
+// CSC arrays in device memory: *flag = 0 when offsets[0 .. width] run monotonically from 0 to nnz inside 32 bits and every one of
+// the nnz row indices is in [0, height) (bits: 1 not monotone, 2 wrong span, 4 row index, 8 offset range); reads nothing else
+int launch_csc_validate(const void* offsets, int idx_type, i64 width, i64 nnz, const void* rows, int row_idx_type, i64 height, unsigned* flag,
+                        hipStream_t st);
+int launch_csc_convert(const void* offsets, int idx_type, i64 width, i64 nnz, const void* rows, int row_idx_type, i64* colptr, unsigned* rowidx,
+                       hipStream_t st);
+
 // packed MFMA operand of X (k x N): bytes needed
 // nsplit: 1..3 = bf16 terms of the skinny operand; NSPLIT_F16X2 = two fp16 terms with per-row power-of-two scales
 constexpr int NSPLIT_F16X2 = 4;

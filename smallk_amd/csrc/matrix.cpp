@@ -103,9 +103,71 @@ int matrix_measure_norms(const smk_matrix* a, hipStream_t st)
     return 0;
 }
 
+// ---- views in device memory handed in by a caller ------------------------------------------------------------------------
+// last element of a rows x cols view, in bytes from its first one, and whether [offset, offset + that + elem_size) stays inside
+// alloc_bytes; every step in 64-bit integers with the overflow checked (a view of 2^40 elements is ordinary arithmetic here)
+static bool strided_extent_fits(i64 rows, i64 cols, i64 rs, i64 cs, i64 es, i64 offset_bytes, i64 alloc_bytes)
+{
+    if (rows <= 0 || cols <= 0 || rs < 0 || cs < 0 || es <= 0 || offset_bytes < 0 || alloc_bytes < 0) return false;
+    i64 a, b, last, end;
+    if (__builtin_mul_overflow(rows - 1, rs, &a) || __builtin_mul_overflow(cols - 1, cs, &b) || __builtin_add_overflow(a, b, &last) ||
+        __builtin_add_overflow(last, (i64)1, &last) || __builtin_mul_overflow(last, es, &end) || __builtin_add_overflow(end, offset_bytes, &end))
+        return false;
+    return end <= alloc_bytes;
+}
+
+int check_device_view(const void* p, int dtype, i64 rows, i64 cols, i64 rs, i64 cs, bool output, const char* what)
+{
+    const std::string w(what);
+    if (!p) { set_error(w + ": null pointer"); return SMK_BAD_PARAM; }
+    const int es = dtype_size(dtype);
+    if (!es) { set_error(w + ": unknown element type"); return SMK_BAD_PARAM; }
+    if (rs < 0 || cs < 0) { set_error(w + ": negative stride"); return SMK_BAD_PARAM; }
+    if (output && ((rs == 0 && rows > 1) || (cs == 0 && cols > 1) || (rows > 1 && cols > 1 && rs == cs))) {
+        set_error(w + ": the elements of an output overlap");
+        return SMK_BAD_PARAM;
+    }
+    int dev = -1;
+    hipPointerAttribute_t at;
+    if (hipGetDevice(&dev) != hipSuccess || hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != dev) {
+        (void)hipGetLastError();              // a host pointer is reported as an error by some runtimes: it is not one of ours
+        set_error(w + ": not a pointer to memory of the current device");
+        return SMK_BAD_PARAM;
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error(w + ": the allocation behind the pointer is unknown to the runtime");
+        return SMK_BAD_PARAM;
+    }
+    if (!strided_extent_fits(rows, cols, rs, cs, es, (i64)((const char*)p - (const char*)base), (i64)size)) {
+        set_error(w + ": the strided extent leaves the allocation");
+        return SMK_BAD_PARAM;
+    }
+    return SMK_OK;
+}
+
+int join_caller_stream(Owned& own, hipStream_t lib, void* caller_stream)
+{
+    hipStream_t caller = (hipStream_t)caller_stream;
+    if (caller == lib) return 0;
+    hipEvent_t ev;
+    if (own.event(&ev, hipEventDisableTiming)) return SMK_DEVICE_ERROR;
+    SMK_HIP(hipEventRecord(ev, caller));
+    SMK_HIP(hipStreamWaitEvent(lib, ev, 0));
+    return 0;
+}
+
 }  // namespace smk
 
 extern "C" {
+
+int smk_strided_extent_fits(int64_t rows, int64_t cols, int64_t row_stride, int64_t col_stride, int64_t elem_size, int64_t offset_bytes,
+                            int64_t alloc_bytes)
+{
+    return strided_extent_fits(rows, cols, row_stride, col_stride, elem_size, offset_bytes, alloc_bytes) ? 1 : 0;
+}
 
 static thread_local bool g_create_single = false;
 int smk_matrix_create(smk_matrix** out, int64_t height, int64_t width_global, int64_t col0, int64_t ncols_local,
@@ -267,6 +329,83 @@ int smk_matrix_download_f64(const smk_matrix* a, double* host, int64_t ld)
         }
     }
     return SMK_OK;
+}
+
+// ---- device memory -> resident matrix -> device memory ("Device tensors in and out") -----------------------------
+// The device twin of smk_matrix_upload_f64: nothing crosses PCIe, and A and the stored transpose come from one read of the
+// source (adopt.hip) instead of a conversion pass and a transpose pass that reads A again.
+int smk_matrix_adopt_device(smk_matrix* a, const void* src, int dtype, int64_t row_stride, int64_t col_stride, void* stream)
+{
+    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; }     // new contents, as in smk_matrix_upload_f64
+    if (!a || a->sparse) return SMK_BAD_PARAM;
+    int rc = check_device_view(src, dtype, a->m, a->n, row_stride, col_stride, false, "smk_matrix_adopt_device");
+    if (rc) return rc;
+    Owned own;
+    rc = join_caller_stream(own, ctx().stream, stream);
+    if (rc) return rc;
+    rc = launch_adopt_dense(src, dtype, row_stride, col_stride, a->A, a->ldA, a->single ? nullptr : a->At, a->ldAt, a->storage, a->m, a->n,
+                            ctx().stream);
+    if (rc) return rc;
+    SMK_HIP(hipStreamSynchronize(ctx().stream));
+    return SMK_OK;
+}
+
+int smk_matrix_copy_to_device(const smk_matrix* a, void* dst, int dtype, int64_t row_stride, int64_t col_stride, void* stream)
+{
+    if (!a || a->sparse) return SMK_BAD_PARAM;
+    int rc = check_device_view(dst, dtype, a->m, a->n, row_stride, col_stride, true, "smk_matrix_copy_to_device");
+    if (rc) return rc;
+    Owned own;
+    rc = join_caller_stream(own, ctx().stream, stream);      // what the caller's stream still does with dst comes first
+    if (rc) return rc;
+    rc = launch_strided_convert(a->A, a->storage == SMK_STORE_BF16 ? DT_BF16 : DT_F32, 1, a->ldA, dst, dtype, row_stride, col_stride, a->m,
+                                a->n, ctx().stream);
+    if (rc) return rc;
+    SMK_HIP(hipStreamSynchronize(ctx().stream));
+    return SMK_OK;
+}
+
+int smk_matrix_create_sparse_device(smk_matrix** out, int64_t height, int64_t width, int64_t nnz, const void* col_offsets, int idx_type,
+                                    const void* row_indices, int row_idx_type, const void* values, int dtype, void* stream)
+{
+    if (!out) return SMK_BAD_PARAM;
+    *out = nullptr;
+    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (height <= 0 || width <= 0 || nnz <= 0 || height > 0xFFFFFFFFll) { set_error("smk_matrix_create_sparse_device: empty or oversized matrix"); return SMK_BAD_PARAM; }
+    if ((idx_type != SMK_IDX_I32 && idx_type != SMK_IDX_I64) || (row_idx_type != SMK_IDX_I32 && row_idx_type != SMK_IDX_I64)) {
+        set_error("smk_matrix_create_sparse_device: unknown index type");
+        return SMK_BAD_PARAM;
+    }
+    // the three arrays as views of 8- / 4- / 2-byte elements: same pointer and extent checks as a dense view
+    const auto idx_dt = [](int t) { return t == SMK_IDX_I64 ? (int)DT_F64 : (int)DT_F32; };
+    int rc = check_device_view(col_offsets, idx_dt(idx_type), width + 1, 1, 1, width + 1, false, "smk_matrix_create_sparse_device(col_offsets)");
+    if (!rc) rc = check_device_view(row_indices, idx_dt(row_idx_type), nnz, 1, 1, nnz, false, "smk_matrix_create_sparse_device(row_indices)");
+    if (!rc) rc = check_device_view(values, dtype, nnz, 1, 1, nnz, false, "smk_matrix_create_sparse_device(values)");
+    if (rc) return rc;
+    Owned own;
+    hipStream_t st = ctx().stream;
+    rc = join_caller_stream(own, st, stream);
+    if (rc) return rc;
+    // the index arrays are checked on the device before the fill, the transpose or any gather reads them
+    Scratch<unsigned> flag;
+    rc = flag.alloc(1);
+    if (rc) return rc;
+    unsigned bad = 0;
+    rc = launch_csc_validate(col_offsets, idx_type, width, nnz, row_indices, row_idx_type, height, flag, st);
+    if (rc) return rc;
+    SMK_HIP(hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, st));
+    SMK_HIP(hipStreamSynchronize(st));
+    if (bad) {
+        set_error(std::string("smk_matrix_create_sparse_device:") + ((bad & 1) ? " col_offsets not monotone;" : "") +
+                  ((bad & 2) ? " col_offsets do not run from 0 to nnz;" : "") + ((bad & 4) ? " row index out of range;" : "") +
+                  ((bad & 8) ? " offset outside 32 bits;" : ""));
+        return SMK_BAD_PARAM;
+    }
+    return matrix_create_sparse_device(out, height, width, nnz, [&](i64* colptr, unsigned* rowidx, double* val, hipStream_t fst) -> int {
+        int frc = launch_csc_convert(col_offsets, idx_type, width, nnz, row_indices, row_idx_type, colptr, rowidx, fst);
+        if (!frc) frc = launch_strided_convert(values, dtype, 1, nnz, val, DT_F64, 1, nnz, nnz, 1, fst);
+        return frc;
+    });
 }
 
 void smk_matrix_destroy(smk_matrix* a)

@@ -490,10 +490,11 @@ static int scatter_own(smk_solver* s)
     return 0;
 }
 
-int smk_solver_set_factors(smk_solver* s, const double* W0, int64_t ldW, const double* H0, int64_t ldH)
+// What every way of setting the factors shares.  Before the factors are written: a matrix refilled after this solver was created
+// has its fp16 product scale and its norms measured again.  After: the failure flag, the copies of the start, this rank's blocks
+// of a row-sharded W, the state of a fresh run.
+static int factors_begin(smk_solver* s)
 {
-    if (!s || !W0 || !H0) return SMK_BAD_PARAM;
-    if (ldW < s->m || ldH < s->k) { set_error("leading dimension too small"); return SMK_BAD_PARAM; }
     if (s->nsplit == NSPLIT_F16X2 && (s->a->ascale == 0.f || s->a->ascale != s->pg1[0].ascale)) {
         // the matrix was refilled after this solver was created: its fp16 product scale follows the new contents
         if (s->a->ascale == 0.f) { const int rc0 = matrix_measure_scale(s->a, s->st); if (rc0) return rc0; }
@@ -504,23 +505,18 @@ int smk_solver_set_factors(smk_solver* s, const double* W0, int64_t ldW, const d
         const int rc0 = matrix_measure_norms(s->a, s->st);
         if (rc0) return rc0;
     }
-    // pad rows of the KP x N device layout must be (and stay) zero
-    SMK_HIP(hipMemsetAsync(s->Wt, 0, (size_t)s->KP * s->m * sizeof(double), s->st));
-    SMK_HIP(hipMemsetAsync(s->H, 0, (size_t)s->KP * s->n * sizeof(double), s->st));
-    // W0 (m x k, host) -> tmpW (m x k, ld m) -> Wt (KP x m)
-    SMK_HIP(hipMemcpy2DAsync(s->tmpW, (size_t)s->m * sizeof(double), W0, (size_t)ldW * sizeof(double),
-                             (size_t)s->m * sizeof(double), (size_t)s->k, hipMemcpyHostToDevice, s->st));
-    int rc = launch_transpose_f64(s->tmpW, s->m, s->Wt, s->KP, s->m, s->k, s->st);
-    if (rc) return rc;
-    SMK_HIP(hipMemcpy2DAsync(s->H, (size_t)s->KP * sizeof(double), H0, (size_t)ldH * sizeof(double),
-                             (size_t)s->k * sizeof(double), (size_t)s->n, hipMemcpyHostToDevice, s->st));
+    return 0;
+}
+
+static int factors_end(smk_solver* s)
+{
     const int big = INT_MAX;
     SMK_HIP(hipMemcpyAsync(s->fail_flag, &big, sizeof(int), hipMemcpyHostToDevice, s->st));
     if (s->W0c) {
         SMK_HIP(hipMemcpyAsync(s->W0c, s->Wt, (size_t)s->KP * s->m * sizeof(double), hipMemcpyDeviceToDevice, s->st));
         SMK_HIP(hipMemcpyAsync(s->H0c, s->H, (size_t)s->KP * s->n * sizeof(double), hipMemcpyDeviceToDevice, s->st));
     }
-    if (s->w_sharded) { rc = scatter_own(s); if (rc) return rc; }
+    if (s->w_sharded) { const int rc = scatter_own(s); if (rc) return rc; }
     SMK_HIP(hipStreamSynchronize(s->st));
     s->w_full = true;
     s->wc_valid = false;
@@ -533,6 +529,54 @@ int smk_solver_set_factors(smk_solver* s, const double* W0, int64_t ldW, const d
     return SMK_OK;
 }
 
+// pad rows of the KP x N device layout must be (and stay) zero
+static int factors_clear(smk_solver* s)
+{
+    SMK_HIP(hipMemsetAsync(s->Wt, 0, (size_t)s->KP * s->m * sizeof(double), s->st));
+    SMK_HIP(hipMemsetAsync(s->H, 0, (size_t)s->KP * s->n * sizeof(double), s->st));
+    return 0;
+}
+
+int smk_solver_set_factors(smk_solver* s, const double* W0, int64_t ldW, const double* H0, int64_t ldH)
+{
+    if (!s || !W0 || !H0) return SMK_BAD_PARAM;
+    if (ldW < s->m || ldH < s->k) { set_error("leading dimension too small"); return SMK_BAD_PARAM; }
+    int rc = factors_begin(s);
+    if (!rc) rc = factors_clear(s);
+    if (rc) return rc;
+    // W0 (m x k, host) -> tmpW (m x k, ld m) -> Wt (KP x m)
+    SMK_HIP(hipMemcpy2DAsync(s->tmpW, (size_t)s->m * sizeof(double), W0, (size_t)ldW * sizeof(double),
+                             (size_t)s->m * sizeof(double), (size_t)s->k, hipMemcpyHostToDevice, s->st));
+    rc = launch_transpose_f64(s->tmpW, s->m, s->Wt, s->KP, s->m, s->k, s->st);
+    if (rc) return rc;
+    SMK_HIP(hipMemcpy2DAsync(s->H, (size_t)s->KP * sizeof(double), H0, (size_t)ldH * sizeof(double),
+                             (size_t)s->k * sizeof(double), (size_t)s->n, hipMemcpyHostToDevice, s->st));
+    return factors_end(s);
+}
+
+static bool factor_dtype(int dt) { return dt == SMK_DT_F64 || dt == SMK_DT_F32; }
+
+// The same start from views in device memory (a torch tensor's data_ptr and strides): W0 is m x k, H0 is k x n.  The strided
+// convert kernel writes Wt (KP x m) and H (KP x n) directly -- a row-major W0 already has the layout of Wt with pitch k instead
+// of KP, so it is a straight copy, with no pass through tmpW.
+int smk_solver_set_factors_device(smk_solver* s, const void* W0, int dtypeW, int64_t rsW, int64_t csW, const void* H0, int dtypeH,
+                                  int64_t rsH, int64_t csH, void* stream)
+{
+    if (!s) return SMK_BAD_PARAM;
+    if (!factor_dtype(dtypeW) || !factor_dtype(dtypeH)) { set_error("smk_solver_set_factors_device: factors are fp64 or fp32"); return SMK_BAD_PARAM; }
+    int rc = check_device_view(W0, dtypeW, s->m, s->k, rsW, csW, false, "smk_solver_set_factors_device(W0)");
+    if (!rc) rc = check_device_view(H0, dtypeH, s->k, s->n, rsH, csH, false, "smk_solver_set_factors_device(H0)");
+    if (rc) return rc;
+    Owned own;
+    rc = join_caller_stream(own, s->st, stream);
+    if (!rc) rc = factors_begin(s);
+    if (!rc) rc = factors_clear(s);
+    if (!rc) rc = launch_strided_convert(W0, dtypeW, rsW, csW, s->Wt, DT_F64, s->KP, 1, s->m, s->k, s->st);
+    if (!rc) rc = launch_strided_convert(H0, dtypeH, rsH, csH, s->H, DT_F64, 1, s->KP, s->k, s->n, s->st);
+    if (rc) return rc;
+    return factors_end(s);
+}
+
 // The same start as smk_solver_set_factors(W0, H0) with W0 = smk_uniform_fill_host(m x k, seed_w), H0 = smk_uniform_fill_host
 // (k x n, seed_h) -- the RandomMatrix stand-in of every caller in this library -- generated on the device: no host fill, no
 // upload.  (HierNMF2 draws two such matrices per node.)  Unsharded solvers only.
@@ -540,34 +584,11 @@ int smk_solver_set_factors_uniform(smk_solver* s, uint64_t seed_w, uint64_t seed
 {
     if (!s) return SMK_BAD_PARAM;
     if (is_dist(s) || s->comm) { set_error("set_factors_uniform: not for sharded solvers"); return SMK_UNSUPPORTED; }
-    if (s->nsplit == NSPLIT_F16X2 && (s->a->ascale == 0.f || s->a->ascale != s->pg1[0].ascale)) {
-        if (s->a->ascale == 0.f) { const int rc0 = matrix_measure_scale(s->a, s->st); if (rc0) return rc0; }
-        for (int g = 0; g < s->ng; ++g) s->pg1[g].ascale = s->pg2[g].ascale = s->a->ascale;
-        s->pl1.ascale = s->pl2.ascale = s->a->ascale;
-    }
-    if (s->pack_in_solve && (s->a->colnorm_max < 0.0 || s->a->rownorm_max < 0.0)) {      // ... and so do the norms behind the packing NNLS launch
-        const int rc0 = matrix_measure_norms(s->a, s->st);
-        if (rc0) return rc0;
-    }
-    int rc = launch_fill_factor_uniform(s->Wt, s->k, s->m, seed_w, 1, s->st);
+    int rc = factors_begin(s);
+    if (!rc) rc = launch_fill_factor_uniform(s->Wt, s->k, s->m, seed_w, 1, s->st);
     if (!rc) rc = launch_fill_factor_uniform(s->H, s->k, s->n, seed_h, 0, s->st);
     if (rc) return rc;
-    const int big = INT_MAX;
-    SMK_HIP(hipMemcpyAsync(s->fail_flag, &big, sizeof(int), hipMemcpyHostToDevice, s->st));
-    if (s->W0c) {
-        SMK_HIP(hipMemcpyAsync(s->W0c, s->Wt, (size_t)s->KP * s->m * sizeof(double), hipMemcpyDeviceToDevice, s->st));
-        SMK_HIP(hipMemcpyAsync(s->H0c, s->H, (size_t)s->KP * s->n * sizeof(double), hipMemcpyDeviceToDevice, s->st));
-    }
-    SMK_HIP(hipStreamSynchronize(s->st));
-    s->w_full = true;
-    s->wc_valid = false;
-    s->have_factors = true;
-    s->inited = false;
-    s->normalized = false;
-    s->iter = 0;
-    s->pg0 = 1.0;
-    s->last_metric = 1.0;
-    return SMK_OK;
+    return factors_end(s);       // never row-sharded here
 }
 
 // ---- collectives -------------------------------------------------------------------------------
@@ -2270,13 +2291,39 @@ int smk_nnls_blockpivot(int k, int64_t ncols, const double* LHS, int64_t ldL, co
     return flag == INT_MAX ? SMK_OK : SMK_FAILURE;
 }
 
+// what every way of reading the factors does first
+static int factors_ready(smk_solver* s, int normalize)
+{
+    int rc = gather_w(s);                 // a collective when W is row-sharded and stale: every rank must be here
+    if (rc) return rc;
+    if (normalize) { rc = normalize_device(s); if (rc) return rc; }
+    return 0;
+}
+
+// ... into views in device memory: W (m x k) from Wt, H (k x n) from the first k rows of the resident H, converted in flight
+int smk_solver_get_factors_device(smk_solver* s, int normalize, void* W, int dtypeW, int64_t rsW, int64_t csW, void* H, int dtypeH,
+                                  int64_t rsH, int64_t csH, void* stream)
+{
+    if (!s) return SMK_BAD_PARAM;
+    if (!factor_dtype(dtypeW) || !factor_dtype(dtypeH)) { set_error("smk_solver_get_factors_device: factors are fp64 or fp32"); return SMK_BAD_PARAM; }
+    int rc = check_device_view(W, dtypeW, s->m, s->k, rsW, csW, true, "smk_solver_get_factors_device(W)");
+    if (!rc) rc = check_device_view(H, dtypeH, s->k, s->n, rsH, csH, true, "smk_solver_get_factors_device(H)");
+    if (rc) return rc;
+    Owned own;
+    rc = join_caller_stream(own, s->st, stream);
+    if (!rc) rc = factors_ready(s, normalize);
+    if (!rc) rc = launch_strided_convert(s->Wt, DT_F64, s->KP, 1, W, dtypeW, rsW, csW, s->m, s->k, s->st);
+    if (!rc) rc = launch_strided_convert(s->H, DT_F64, 1, s->KP, H, dtypeH, rsH, csH, s->k, s->n, s->st);
+    if (rc) return rc;
+    return sync_and_check(s, nullptr);
+}
+
 int smk_solver_get_factors(smk_solver* s, int normalize, double* W, int64_t ldW, double* H, int64_t ldH)
 {
     if (!s || !W || !H) return SMK_BAD_PARAM;
     if (ldW < s->m || ldH < s->k) { set_error("leading dimension too small"); return SMK_BAD_PARAM; }
-    int rc = gather_w(s);                 // a collective when W is row-sharded and stale: every rank must be here
+    int rc = factors_ready(s, normalize);
     if (rc) return rc;
-    if (normalize) { rc = normalize_device(s); if (rc) return rc; }
     rc = launch_transpose_f64(s->Wt, s->KP, s->tmpW, s->m, s->k, s->m, s->st);
     if (rc) return rc;
     // Device-to-host copies are kept contiguous: a strided hipMemcpy2DAsync into pageable memory leaves

@@ -220,4 +220,12 @@ int ensure_seg_plans(const smk_matrix* a);
 int matrix_measure_scale(const smk_matrix* a, hipStream_t st);
 int matrix_measure_norms(const smk_matrix* a, hipStream_t st);
 
+// matrix.cpp: a strided view in device memory handed in by a caller (the *_device entries).  check_device_view: SMK_OK, or
+// SMK_BAD_PARAM with the error text set -- null pointer, unknown element type, negative stride (or a zero stride of an output),
+// not device memory of the current device, or an extent that leaves the allocation; nothing is launched.
+// join_caller_stream: the library's stream waits for what the caller has enqueued on its own so far (event record + stream
+// wait).  The event belongs to `own`, a local of the entry: it lives until the entry returns and is destroyed on every path.
+int check_device_view(const void* p, int dtype, i64 rows, i64 cols, i64 rs, i64 cs, bool output, const char* what);
+int join_caller_stream(smk::Owned& own, hipStream_t lib, void* caller_stream);
+
 }  // namespace smk

@@ -25,6 +25,38 @@ def _p(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _tensor_view(t, what, *, ndim=2, kinds="float"):
+    """(data_ptr, SMK_DT_* / SMK_IDX_* code, strides in elements) of a torch tensor in GPU memory.  Raises TypeError / ValueError
+    before the library is called: not a tensor, a wrong rank, an element type the entry does not take, a CPU tensor, a tensor on
+    another device than the library's.  torch is imported here, not with the package."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch.Tensor, got {type(t).__name__}")
+    codes = {"float": {torch.float64: L.DT_F64, torch.float32: L.DT_F32, torch.bfloat16: L.DT_BF16, torch.float16: L.DT_F16},
+             "factor": {torch.float64: L.DT_F64, torch.float32: L.DT_F32},
+             "index": {torch.int32: L.IDX_I32, torch.int64: L.IDX_I64}}[kinds]
+    if t.layout != torch.strided:
+        raise TypeError(f"{what}: expected a strided tensor, got layout {t.layout}")
+    if t.dtype not in codes:
+        raise TypeError(f"{what}: dtype {t.dtype} is not one of {sorted(str(d) for d in codes)}")
+    if t.dim() != ndim:
+        raise ValueError(f"{what}: expected {ndim} dimensions, got shape {tuple(t.shape)}")
+    if t.numel() == 0:
+        raise ValueError(f"{what}: empty tensor")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: the tensor is on {t.device}; it must be in GPU memory")
+    dev = L.lib().smk_current_device()
+    if t.device.index != dev:
+        raise ValueError(f"{what}: the tensor is on {t.device}, the library works on device {dev}")
+    return C.c_void_p(t.data_ptr()), codes[t.dtype], tuple(int(x) for x in t.stride())
+
+
+def _stream_of(t):
+    """the stream torch is issuing work on for t's device: where t was produced / where a result will be consumed"""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
 def initialize(device: int = -1):
     """NmfInitialize (nmf.hpp:71): select the GPU, create the stream.  Raises without a GPU."""
     L.check(L.lib().smk_initialize(device), "smk_initialize")
@@ -103,6 +135,35 @@ class DenseMatrix:
         mat.upload(A)
         return mat
 
+    @classmethod
+    def from_device(cls, t, *, storage="f32", single_copy=False):
+        """The resident matrix of a 2-D torch tensor that is already in GPU memory (float64 / float32 / bfloat16 / float16, any
+        strides): converted and transposed on the device, nothing crosses PCIe.  Same stored values as ``from_host`` of
+        ``t.cpu().double()``.  Ordered after the work queued on torch's current stream; returns when the copy is done."""
+        _tensor_view(t, "DenseMatrix.from_device")
+        mat = cls(t.shape[0], t.shape[1], storage=storage, single_copy=single_copy)
+        mat.adopt(t)
+        return mat
+
+    def adopt(self, t):
+        """new contents from a torch tensor in GPU memory (the device twin of ``upload``)"""
+        ptr, dt, (rs, cs) = _tensor_view(t, "DenseMatrix.adopt")
+        if tuple(t.shape) != (self.height, self.ncols):
+            raise ValueError(f"DenseMatrix.adopt: shape {tuple(t.shape)} does not match the matrix ({self.height}, {self.ncols})")
+        L.check(L.lib().smk_matrix_adopt_device(self._h, ptr, dt, rs, cs, _stream_of(t)), "smk_matrix_adopt_device")
+
+    def to_device(self, dtype=None, *, out=None):
+        """the stored values as a torch tensor on the GPU (``dtype`` default torch.float32), or written into ``out`` (any strides)"""
+        import torch
+        if out is None:
+            out = torch.empty((self.height, self.ncols), dtype=dtype or torch.float32,
+                              device=torch.device("cuda", L.lib().smk_current_device()))
+        ptr, dt, (rs, cs) = _tensor_view(out, "DenseMatrix.to_device")
+        if tuple(out.shape) != (self.height, self.ncols):
+            raise ValueError(f"DenseMatrix.to_device: out has shape {tuple(out.shape)}, the matrix ({self.height}, {self.ncols})")
+        L.check(L.lib().smk_matrix_copy_to_device(self._h, ptr, dt, rs, cs, _stream_of(out)), "smk_matrix_copy_to_device")
+        return out
+
     def upload(self, A_local):
         A_local = _f(A_local)
         assert A_local.shape == (self.height, self.ncols)
@@ -151,6 +212,36 @@ class SparseMatrix(DenseMatrix):
                                                  self.ncols, self.nnz, co.ctypes.data_as(C.POINTER(C.c_uint)),
                                                  ri.ctypes.data_as(C.POINTER(C.c_uint)), _p(d)),
                 "smk_matrix_create_sparse")
+
+    @classmethod
+    def from_device(cls, ccol_indices, row_indices=None, values=None, shape=None):
+        """CSC arrays that are already in GPU memory: 1-D torch tensors (int32 / int64 offsets and row indices, float values) and
+        ``shape``, or one ``torch.sparse_csc_tensor``.  The index arrays are checked on the device before anything reads through
+        them; bad arrays raise SmallkError(BAD_PARAM)."""
+        import torch
+        if isinstance(ccol_indices, torch.Tensor) and ccol_indices.layout == torch.sparse_csc:
+            t = ccol_indices
+            if t.dim() != 2:
+                raise ValueError(f"SparseMatrix.from_device: expected a 2-D sparse tensor, got shape {tuple(t.shape)}")
+            ccol_indices, row_indices, values, shape = t.ccol_indices(), t.row_indices(), t.values(), tuple(t.shape)
+        if row_indices is None or values is None or shape is None:
+            raise TypeError("SparseMatrix.from_device: ccol_indices, row_indices, values and shape, or a sparse CSC tensor")
+        views = []
+        for t, what, kinds in ((ccol_indices, "ccol_indices", "index"), (row_indices, "row_indices", "index"), (values, "values", "float")):
+            _tensor_view(t, f"SparseMatrix.from_device({what})", ndim=1, kinds=kinds)
+            t = t.contiguous()
+            views.append((t,) + _tensor_view(t, f"SparseMatrix.from_device({what})", ndim=1, kinds=kinds))
+        (co, co_p, co_t, _), (ri, ri_p, ri_t, _), (va, va_p, va_t, _) = views
+        self = cls.__new__(cls)
+        self.height, self.ncols = int(shape[0]), int(shape[1])
+        self.width_global, self.col0, self.storage = self.ncols, 0, L.STORE_F32
+        if co.numel() != self.ncols + 1 or ri.numel() != va.numel():
+            raise ValueError("SparseMatrix.from_device: ccol_indices needs shape[1] + 1 entries, row_indices as many as values")
+        self.nnz = int(va.numel())
+        self._h = C.c_void_p()
+        L.check(L.lib().smk_matrix_create_sparse_device(C.byref(self._h), self.height, self.ncols, self.nnz, co_p, co_t, ri_p, ri_t,
+                                                        va_p, va_t, _stream_of(va)), "smk_matrix_create_sparse_device")
+        return self
 
     @classmethod
     def from_scipy(cls, A):
@@ -229,6 +320,30 @@ class NmfSolver:
         L.check(L.lib().smk_solver_set_factors(self._h, _p(W0), W0.shape[0], _p(H0), H0.shape[0]),
                 "smk_solver_set_factors")
 
+    def set_factors_device(self, W0, H0_local):
+        """``set_factors`` from torch tensors in GPU memory (float64 or float32, any strides): W0 (m, k), H0 (k, ncols)"""
+        wp, wt, (wrs, wcs) = _tensor_view(W0, "set_factors_device(W0)", kinds="factor")
+        hp, ht, (hrs, hcs) = _tensor_view(H0_local, "set_factors_device(H0)", kinds="factor")
+        if tuple(W0.shape) != (self.A.height, self.k) or tuple(H0_local.shape) != (self.k, self.A.ncols):
+            raise ValueError(f"set_factors_device: W0 {tuple(W0.shape)} / H0 {tuple(H0_local.shape)} do not match "
+                             f"({self.A.height}, {self.k}) / ({self.k}, {self.A.ncols})")
+        L.check(L.lib().smk_solver_set_factors_device(self._h, wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W0)),
+                "smk_solver_set_factors_device")
+
+    def factors_device(self, normalize=False, dtype=None):
+        """``factors`` as torch tensors on the GPU: W (m, k) and H (k, ncols), float64 (default) or float32 = the fp64 factor
+        rounded to nearest even.  They never visit the host."""
+        import torch
+        dev = torch.device("cuda", L.lib().smk_current_device())
+        W = torch.empty((self.A.height, self.k), dtype=dtype or torch.float64, device=dev)
+        H = torch.empty((self.k, self.A.ncols), dtype=dtype or torch.float64, device=dev)
+        wp, wt, (wrs, wcs) = _tensor_view(W, "factors_device", kinds="factor")
+        hp, ht, (hrs, hcs) = _tensor_view(H, "factors_device", kinds="factor")
+        rc = L.lib().smk_solver_get_factors_device(self._h, int(normalize), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W))
+        if rc not in (L.OK, L.FAILURE):
+            L.check(rc, "smk_solver_get_factors_device")
+        return W, H
+
     def set_factors_uniform(self, seed_w, seed_h):
         """W0 / H0 = uniform_host(m, k, seed_w) / uniform_host(k, n, seed_h), generated on the device"""
         L.check(L.lib().smk_solver_set_factors_uniform(self._h, seed_w, seed_h), "smk_solver_set_factors_uniform")
@@ -279,8 +394,8 @@ class NmfSolver:
 
     def kernel_name(self, which) -> str:
         """the kernel pass `which` (0 = W'A, 1 = H*At) launches; which = 2: how the stopping-rule checks were formed so far (counts per route)"""
-        buf = C.create_string_buffer(160)
-        L.check(L.lib().smk_solver_kernel_name(self._h, which, buf, 160), "smk_solver_kernel_name")
+        buf = C.create_string_buffer(512)
+        L.check(L.lib().smk_solver_kernel_name(self._h, which, buf, 512), "smk_solver_kernel_name")
         return buf.value.decode()
 
     def kernel_work(self, which):
@@ -336,6 +451,35 @@ def nmf(A, W0, H0, algorithm, *, storage="f32", **kw) -> NmfResult:
     if rc not in (L.OK, L.FAILURE, L.BAD_PARAM, L.NOTINITIALIZED, L.SIZE_TOO_LARGE):
         L.check(rc, "smk_nmf_dense")
     return NmfResult(rc, W, H, st.iteration_count, st.elapsed_us)
+
+
+def nmf_device(A, W0, H0, algorithm, *, storage="f32", **kw) -> NmfResult:
+    """One-shot NMF of a torch tensor that is already in GPU memory: A dense (2-D, any float type, any strides) or a sparse CSC
+    tensor, W0 (m, k) and H0 (k, n) float64 or float32 tensors.  The steps of ``nmf`` / ``nmf_sparse``; the factors come back as
+    tensors of W0's dtype and never leave the device."""
+    import torch
+    sparse = isinstance(A, torch.Tensor) and A.layout == torch.sparse_csc
+    if not sparse:
+        _tensor_view(A, "nmf_device(A)")
+    _tensor_view(W0, "nmf_device(W0)", kinds="factor")
+    _tensor_view(H0, "nmf_device(H0)", kinds="factor")
+    mat = SparseMatrix.from_device(A) if sparse else DenseMatrix.from_device(A, storage=storage)
+    solver = None
+    try:
+        o = make_options(mat.height, mat.ncols, int(W0.shape[1]), algorithm, **kw)
+        if not L.lib().smk_is_valid(C.byref(o), 1):
+            return NmfResult(L.BAD_PARAM, W0, H0, 0, 0)
+        solver = NmfSolver(mat, o)
+        solver.set_factors_device(W0, H0)
+        rc, iters, us = solver.run()
+        if rc not in (L.OK, L.FAILURE):
+            L.check(rc, "smk_solver_run")
+        W, H = solver.factors_device(dtype=W0.dtype)     # like the reference, the last iterate even when the solver reports failure
+        return NmfResult(rc, W, H, iters, us)
+    finally:
+        if solver is not None:
+            solver.close()
+        mat.close()
 
 
 def nnls_blockpivot(LHS, RHS, Xinit):
