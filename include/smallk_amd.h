@@ -235,6 +235,19 @@ int smk_solver_iteration_count(const smk_solver* s);
  * iteration could move the factors by 1e-4 */
 int smk_solver_product_form(const smk_solver* s, int* guard_checks, int* guard_fired, double* guard_last);
 
+/* ---- the reconstruction error of a factorisation, on the device (the reference reports only its stopping-rule metric) --------
+ * ||A - W H||_F^2 and ||A||_F^2 of the local columns of a resident matrix (dense or sparse), W m x k, H k x ncols_local;
+ * col_resid_sq (ncols_local doubles, may be NULL): the same per column.  Stored values of A, fp64 throughout. */
+int smk_matrix_residual(const smk_matrix* a, int k, const double* W, int64_t ldW, const double* H, int64_t ldH,
+                        double* resid_sq, double* a_sq, double* col_resid_sq);
+/* the same with the factors in device memory (views as for smk_solver_set_factors_device: SMK_DT_F64 / SMK_DT_F32, strides in
+ * elements, the caller's stream); col_resid_sq: ncols_local contiguous fp64 in device memory, or NULL */
+int smk_matrix_residual_device(const smk_matrix* a, int k, const void* W, int dtypeW, int64_t rsW, int64_t csW,
+                               const void* H, int dtypeH, int64_t rsH, int64_t csH, void* stream,
+                               double* resid_sq, double* a_sq, void* col_resid_sq);
+/* of the solver's current factors on its matrix; the solver is left exactly as it was */
+int smk_solver_residual(smk_solver* s, double* resid_sq, double* a_sq, double* col_resid_sq);
+
 /* bool NnlsBlockpivot(LHS, RHS, X, Y), common/include/nnls.hpp:144-244, by itself (the reference's
  * tests/src/test_bpp.cpp drives the solver this way): LHS k x k SPD, RHS k x ncols, X in/out (warm start:
  * passive set = X > 0), Y = LHS X - RHS out (may be NULL).  SMK_FAILURE = the reference's `false`

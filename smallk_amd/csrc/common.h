@@ -464,6 +464,19 @@ void gram_partial_shape(i64 N, int max_blocks, int* nblk_out, i64* cpw_out);
 int launch_spmm_seg(const SegPlan& sp, const i64* colptr, const double* val, const double* X, int k, double* P, int kpp,
                     hipStream_t st, double* pieces = nullptr, const InvRide* ride = nullptr, const GramRide* gram = nullptr);
 
+// residual.hip: ||A - W H||_F^2 and ||A||_F^2 per column (col_r / col_a, n doubles each) and in total (out2[0], out2[1]), fp64
+// against the stored values of A, the same bits on every run.  Wt: m x k with ldf doubles per row of W, H: n columns of ldf
+// doubles; factor rows from k on are never read.  scratch: residual_*_scratch_elems doubles.  Dense: one read of A, never of A'.
+size_t residual_dense_scratch_elems(i64 m, i64 n, int num_cus);
+int launch_residual_dense(const void* A, int storage, i64 ldA, i64 m, i64 n, const double* Wt, const double* H, int ldf, int k,
+                          double* scratch, double* col_r, double* col_a, double* out2, int num_cus, hipStream_t st);
+// sparse: the segments of CSC(A) read-only (the piece buffer is part of scratch); G = W'W (ldg doubles per row); col_merged: the sum
+// of squares per column of the merged entries of a matrix that stores duplicates, else null
+size_t residual_sparse_scratch_elems(const SegPlan& sp, i64 n);
+int launch_residual_sparse(const SegPlan& sp, const i64* colptr, const double* val, i64 n, const double* Wt, const double* H, int ldf,
+                           int k, const double* G, int ldg, const double* col_merged, double* scratch, double* col_r, double* col_a,
+                           double* out2, hipStream_t st);
+
 // spmm_blocked.hip: the rank-2 gather product with the gathered factor cut into row blocks that stay in one XCD's L2.
 // A matrix regrouped by row block: block b is a CSC of its own (cp[b * (ncols + 1) + j] .. are absolute positions in ri / va)
 struct BlockedCsc {

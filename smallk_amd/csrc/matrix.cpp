@@ -617,7 +617,9 @@ int matrix_create_sparse_device(smk_matrix** out, i64 height, i64 width, i64 nnz
 
 // host copy of a resident CSC (32-bit offsets), fetched on first use: only column subsets whose list is not strictly
 // increasing are cut on the host
-static int ensure_host_csc(const smk_matrix* a)
+extern "C++" {
+namespace smk {
+int matrix_host_csc(const smk_matrix* a)
 {
     if (!a->h_colptr.empty()) return SMK_OK;
     a->h_colptr.resize((size_t)a->n + 1);
@@ -627,6 +629,8 @@ static int ensure_host_csc(const smk_matrix* a)
     if (rc != SMK_OK) { a->h_colptr.clear(); return rc; }
     return SMK_OK;
 }
+}  // namespace smk
+}  // extern "C++"
 
 // Column subset of a resident matrix as a new matrix (HierNMF2 node, SubMatrixColsCompact).
 // Dense (dense_matrix_impl.hpp:224-281): all rows kept, columns gathered HBM -> HBM, transpose rebuilt
@@ -685,7 +689,7 @@ int smk_matrix_gather_cols(const smk_matrix* src, const unsigned* cols, int64_t 
         return SMK_OK;
     }
     int64_t nh = 0, nz = 0;
-    int rc = ensure_host_csc(src);
+    int rc = matrix_host_csc(src);
     if (rc != SMK_OK) return rc;
     rc = smk_csc_subset_cols_compact(src->m, src->n, src->h_colptr.data(), src->h_rowidx.data(), src->h_val.data(), cols,
                                          ncols, nullptr, nullptr, nullptr, nullptr, nullptr, &nh, &nz);

@@ -69,8 +69,13 @@ struct smk_matrix {
     // ranks 3 .. 128 on sparse A: the entry-balanced segments of CSC(A) / CSC(A') (spmm_seg.hip), built on first use
     mutable SegPlan segA, segAt;
     mutable bool seg_tried = false;
-    mutable std::vector<unsigned> h_colptr, h_rowidx;     // fetched on first use (ensure_host_csc)
+    mutable std::vector<unsigned> h_colptr, h_rowidx;     // fetched on first use (matrix_host_csc)
     mutable std::vector<double> h_val;
+    // sparse A, residual.cpp: whether the CSC stores an entry twice (they add up in every product, so sum a_e^2 over the stored
+    // entries is not ||A||^2): -1 = not yet looked, 0 = no, 1 = yes and dup_colsq holds the sum of squares per column of the
+    // merged entries.  Looked up once: a sparse matrix does not change after creation.
+    mutable int dup_state = -1;
+    mutable double* dup_colsq = nullptr;
     mutable smk::Owned own;                          // every device block above (the lazily built stored transpose included); the blocked CSC and the segment plans free themselves
 };
 
@@ -219,6 +224,7 @@ int matrix_materialize_transpose(const smk_matrix* ca);
 int ensure_seg_plans(const smk_matrix* a);
 int matrix_measure_scale(const smk_matrix* a, hipStream_t st);
 int matrix_measure_norms(const smk_matrix* a, hipStream_t st);
+int matrix_host_csc(const smk_matrix* a);         // the host copy of a resident CSC (h_colptr / h_rowidx / h_val), fetched on first use
 
 // matrix.cpp: a strided view in device memory handed in by a caller (the *_device entries).  check_device_view: SMK_OK, or
 // SMK_BAD_PARAM with the error text set -- null pointer, unknown element type, negative stride (or a zero stride of an output),

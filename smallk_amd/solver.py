@@ -7,6 +7,7 @@ All compute happens in libsmallk_amd.so on the GPU.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -55,6 +56,54 @@ def _stream_of(t):
     """the stream torch is issuing work on for t's device: where t was produced / where a result will be consumed"""
     import torch
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _is_tensor(x) -> bool:
+    """a torch tensor, told without importing torch (a process that never made one has none to pass)"""
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+@dataclass
+class Residual:
+    """||A - W H||_F^2 and ||A||_F^2 of a factorisation (stored values of A, fp64), and the former per column when asked for
+    (a numpy array, or a torch tensor on the GPU when the factors were tensors)."""
+    resid_sq: float
+    a_sq: float
+    col_resid_sq: object = None
+
+    @property
+    def norm(self) -> float:
+        """||A - W H||_F"""
+        return math.sqrt(self.resid_sq)
+
+    @property
+    def relative(self) -> float:
+        """||A - W H||_F / ||A||_F; nan for an all-zero A"""
+        return math.sqrt(self.resid_sq / self.a_sq) if self.a_sq > 0 else math.nan
+
+
+def _residual_factors(W, H, height, ncols, what):
+    """The checks of ``DenseMatrix.residual`` made before the library is called: both factors on the host (array-likes of
+    numbers) or both torch tensors, 2-D, W (height, k) and H (k, ncols) with k >= 1.  Returns (on_device, k)."""
+    tw, th = _is_tensor(W), _is_tensor(H)
+    if tw != th:
+        raise TypeError(f"{what}: W and H must both be host arrays or both be torch tensors in GPU memory")
+    if tw:
+        for x, name in ((W, "W"), (H, "H")):
+            if str(x.dtype) not in ("torch.float64", "torch.float32"):
+                raise TypeError(f"{what}: {name} has dtype {x.dtype}; the factors are float64 or float32")
+    else:
+        for x, name in ((W, "W"), (H, "H")):
+            kind = np.asarray(x).dtype.kind
+            if kind not in "fiu":
+                raise TypeError(f"{what}: {name} has dtype {np.asarray(x).dtype}; expected real numbers")
+    ws, hs = tuple(W.shape) if hasattr(W, "shape") else np.shape(W), tuple(H.shape) if hasattr(H, "shape") else np.shape(H)
+    if len(ws) != 2 or len(hs) != 2:
+        raise ValueError(f"{what}: W and H must be 2-D, got shapes {ws} and {hs}")
+    k = int(ws[1])
+    if k < 1 or ws[0] != height or hs != (k, ncols):
+        raise ValueError(f"{what}: W {ws} / H {hs} do not match ({height}, k) / (k, {ncols})")
+    return tw, k
 
 
 def initialize(device: int = -1):
@@ -180,6 +229,27 @@ class DenseMatrix:
         out = np.empty((self.height, self.ncols), order="F")
         L.check(L.lib().smk_matrix_download_f64(self._h, _p(out), self.height), "smk_matrix_download_f64")
         return out
+
+    def residual(self, W, H, *, per_column=False) -> Residual:
+        """||A - W H||_F^2 and ||A||_F^2 of the local columns, computed on the device in fp64 against the stored values of A
+        (dense: one streaming read of A; sparse: over the stored entries; no m x n temporary either way).  W (height, k) and
+        H (k, ncols): both numpy arrays, or both torch tensors in GPU memory (float64 or float32, any strides); with tensors
+        the per-column values come back as a tensor on the GPU."""
+        on_device, k = _residual_factors(W, H, self.height, self.ncols, "residual")
+        r, a = C.c_double(0), C.c_double(0)
+        if on_device:
+            import torch
+            wp, wt, (wrs, wcs) = _tensor_view(W, "residual(W)", kinds="factor")
+            hp, ht, (hrs, hcs) = _tensor_view(H, "residual(H)", kinds="factor")
+            col = torch.empty(self.ncols, dtype=torch.float64, device=W.device) if per_column else None
+            L.check(L.lib().smk_matrix_residual_device(self._h, k, wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), C.byref(r), C.byref(a),
+                                                       C.c_void_p(col.data_ptr()) if per_column else None), "smk_matrix_residual_device")
+        else:
+            W, H = _f(W), _f(H)
+            col = np.empty(self.ncols) if per_column else None
+            L.check(L.lib().smk_matrix_residual(self._h, k, _p(W), W.shape[0], _p(H), H.shape[0], C.byref(r), C.byref(a),
+                                                _p(col) if per_column else None), "smk_matrix_residual")
+        return Residual(r.value, a.value, col)
 
     def close(self):
         if self._h:
@@ -378,6 +448,14 @@ class NmfSolver:
             L.check(rc, "smk_solver_get_factors")
         return W, H
 
+    def residual(self, per_column=False) -> Residual:
+        """``A.residual`` of the solver's current factors (not normalised), taken on the device; the solver is left exactly as
+        it was.  Not for a solver with a communicator attached; a plain column shard returns its local sums."""
+        r, a = C.c_double(0), C.c_double(0)
+        col = np.empty(self.A.ncols) if per_column else None
+        L.check(L.lib().smk_solver_residual(self._h, C.byref(r), C.byref(a), _p(col) if per_column else None), "smk_solver_residual")
+        return Residual(r.value, a.value, col)
+
     def product_form(self):
         """(form, guard_checks, guard_fired, cond x delta of the last check); form: 3 bf16x3, 4 fp16 two-term, 8 accurate"""
         c, f, v = C.c_int(0), C.c_int(0), C.c_double(0)
@@ -451,6 +529,12 @@ def nmf(A, W0, H0, algorithm, *, storage="f32", **kw) -> NmfResult:
     if rc not in (L.OK, L.FAILURE, L.BAD_PARAM, L.NOTINITIALIZED, L.SIZE_TOO_LARGE):
         L.check(rc, "smk_nmf_dense")
     return NmfResult(rc, W, H, st.iteration_count, st.elapsed_us)
+
+
+def relative_error(A, W, H) -> float:
+    """||A - W H||_F / ||A||_F of a resident matrix (DenseMatrix or SparseMatrix) and factors on the host or on the GPU: the
+    short form of ``A.residual(W, H).relative``"""
+    return A.residual(W, H).relative
 
 
 def nmf_device(A, W0, H0, algorithm, *, storage="f32", **kw) -> NmfResult:
