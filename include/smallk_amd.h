@@ -248,6 +248,25 @@ int smk_matrix_residual_device(const smk_matrix* a, int k, const void* W, int dt
 /* of the solver's current factors on its matrix; the solver is left exactly as it was */
 int smk_solver_residual(smk_solver* s, double* resid_sq, double* a_sq, double* col_resid_sq);
 
+/* ---- labels, memberships, top terms and fold-in, on the device (the device twins of smk_compute_assignments,
+ * smk_compute_fuzzy_assignments and smk_top_terms below: the same comparisons in the same order, so the same integers and the
+ * same membership bits; no k <= n and no height >= width requirement) -----------------------------------------------------
+ * H: k x n view in device memory (SMK_DT_F64 / SMK_DT_F32, strides in elements, the caller's stream).
+ * labels: n uint32; memberships: k*n float, document c at c*k, or NULL -- both device memory */
+int smk_labels_device(const void* H, int dtype, int64_t rsH, int64_t csH, int k, int64_t n, void* stream,
+                      void* labels, void* memberships);
+/* W: m x k view.  term_indices: maxterms*k int32 in device memory, topic j at j*maxterms; min(maxterms, m) slots per topic are
+ * written, in the order d[a] > d[b] || (d[a] == d[b] && a < b).  Any maxterms (above 256: a radix sort per topic). */
+int smk_top_terms_device(const void* W, int dtype, int64_t rsW, int64_t csW, int64_t m, int k, int maxterms,
+                         void* stream, void* term_indices);
+/* the same on a solver's resident factors, no copy of H / W; normalize as in smk_solver_get_factors */
+int smk_solver_labels(smk_solver* s, int normalize, void* stream, void* labels, void* memberships);
+int smk_solver_top_terms(smk_solver* s, int normalize, int maxterms, void* stream, void* term_indices);
+/* H := argmin_{H >= 0} ||A - W H||_F with the solver's W fixed: one exact block-pivoting solve (BPP solvers, unsharded), warm
+ * start = the current H.  W, the normalisation state of W and the iteration count stay.  SMK_FAILURE: the reference's `false`
+ * (rank-deficient W). */
+int smk_solver_project_h(smk_solver* s);
+
 /* bool NnlsBlockpivot(LHS, RHS, X, Y), common/include/nnls.hpp:144-244, by itself (the reference's
  * tests/src/test_bpp.cpp drives the solver this way): LHS k x k SPD, RHS k x ncols, X in/out (warm start:
  * passive set = X > 0), Y = LHS X - RHS out (may be NULL).  SMK_FAILURE = the reference's `false`

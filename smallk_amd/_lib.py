@@ -128,6 +128,11 @@ SYMBOLS = {
     "smk_matrix_residual": (C.c_int, [_vp, C.c_int, _dp, _i64, _dp, _i64, _dp, _dp, _dp]),
     "smk_matrix_residual_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _dp, _dp, _vp]),
     "smk_solver_residual": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "smk_labels_device": (C.c_int, [_vp, C.c_int, _i64, _i64, C.c_int, _i64, _vp, _vp, _vp]),
+    "smk_top_terms_device": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, _vp, _vp]),
+    "smk_solver_labels": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "smk_solver_top_terms": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "smk_solver_project_h": (C.c_int, [_vp]),
     "smk_nnls_blockpivot": (C.c_int, [C.c_int, _i64, _dp, _i64, _dp, _i64, _dp, _i64, _dp, _i64]),
     "smk_solver_enable_timing": (C.c_int, [_vp, C.c_int]),
     "smk_solver_kernel_time": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_int)]),

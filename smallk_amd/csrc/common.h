@@ -477,6 +477,17 @@ int launch_residual_sparse(const SegPlan& sp, const i64* colptr, const double* v
                            int k, const double* G, int ldg, const double* col_merged, double* scratch, double* col_r, double* col_a,
                            double* out2, hipStream_t st);
 
+// assign.hip: labels / memberships of the columns of H and the top terms of the columns of W, the factors fp64 or fp32 (DT_*) in
+// their k-contiguous layout: column c of H at H + c * ldc, row i of W at W + i * ld (elements).  The host functions' comparisons in
+// the host functions' order: the same integers, the same membership bits.  memb: k * n floats (document c at c * k) or null.
+// out: topic j at out + j * maxterms, min(maxterms, m) slots written.  launch_top_terms selects in LDS (maxterms <= TOPTERMS_CAP,
+// scratch: topterms_scratch_bytes); launch_top_terms_sorted is the radix sort route for any maxterms (allocates, synchronises).
+constexpr int TOPTERMS_CAP = 256;
+int launch_labels(const void* H, int dtype, i64 ldc, int k, i64 n, unsigned* labels, float* memb, hipStream_t st);
+size_t topterms_scratch_bytes(i64 m, int k, int maxterms, int num_cus);
+int launch_top_terms(const void* W, int dtype, i64 ld, i64 m, int k, int maxterms, void* scratch, int* out, int num_cus, hipStream_t st);
+int launch_top_terms_sorted(const void* W, int dtype, i64 ld, i64 m, int k, int maxterms, int* out, hipStream_t st);
+
 // spmm_blocked.hip: the rank-2 gather product with the gathered factor cut into row blocks that stay in one XCD's L2.
 // A matrix regrouped by row block: block b is a CSC of its own (cp[b * (ncols + 1) + j] .. are absolute positions in ri / va)
 struct BlockedCsc {

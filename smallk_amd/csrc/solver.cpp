@@ -2241,6 +2241,41 @@ int smk_solver_nnls_hals(smk_solver* s, double tol, int verbose, int max_iter, i
     return success ? SMK_OK : SMK_FAILURE;
 }
 
+// The fold-in ("transform") step of a trained model: H = argmin_{H >= 0} ||A - W H||_F with the solver's W fixed, by ONE exact
+// block-pivoting solve of (W'W) H = W'A from the current H as the warm start (passive set = H > 0).  W is not touched, nothing is
+// normalised, the iteration count stays.  SMK_FAILURE = the reference's `false` (a rank-deficient W).
+int smk_solver_project_h(smk_solver* s)
+{
+    if (!s) { set_error("smk_solver_project_h: null solver"); return SMK_BAD_PARAM; }
+    if (!s->have_factors) { set_error("smk_solver_project_h: set_factors() first"); return SMK_BAD_PARAM; }
+    if (s->o.algorithm != SMK_ALG_BPP) { set_error("smk_solver_project_h: a BPP solver"); return SMK_BAD_PARAM; }
+    if (is_dist(s) || s->w_sharded) { set_error("smk_solver_project_h: not available on a sharded solver"); return SMK_UNSUPPORTED; }
+    int rc = 0;
+    // one pass: the accurate product form (the fp64 product of the stored data) costs one slower pass, and H then differs from the
+    // reference's by summation order only (as smk_solver_nnls_hals)
+    if (!s->a->sparse && s->nsplit != NSPLIT_F64 && !sw::nsplit().set) {
+        s->nsplit = NSPLIT_F64;
+        rc = plan_products(s);
+        if (!rc && alloc_product_buffers(s)) rc = SMK_DEVICE_ERROR;
+        if (rc) return rc;
+    }
+    // as solver.Init: the factors are the caller's, nothing is known to come from an NNLS launch, nothing is pending
+    s->from_nnls[0] = s->from_nnls[1] = false;
+    s->nnls_packed[0] = s->nnls_packed[1] = false;
+    s->tail_nblk[0] = s->tail_nblk[1] = 0;
+    s->pg_defer_slot = s->iter_snap_slot = s->pg_totals_slot = -1;
+    s->normalized = false;          // H is about to change
+    rc = gram_w(s);
+    if (!rc) rc = prod1(s);
+    if (!rc) rc = nnls_side(s, 0, s->H, 0, s->n, view1(s), s->Gw);
+    s->inited = false;              // Gw / R1 no longer describe a solver schedule
+    s->from_nnls[0] = s->from_nnls[1] = false;
+    s->nnls_packed[0] = s->nnls_packed[1] = false;      // (by-products of the solve for a schedule that does not follow)
+    s->nnls_gram_nblk[0] = s->nnls_gram_nblk[1] = 0;
+    if (rc) return rc;
+    return sync_and_check(s, nullptr);
+}
+
 // NnlsBlockpivot(LHS, RHS, X, Y), common/include/nnls.hpp:144-244, on its own: min ||.|| s.t. X >= 0 for
 // LHS X = RHS with LHS k x k SPD, warm start X (passive set = X > 0), dual Y = LHS X - RHS.
 int smk_nnls_blockpivot(int k, int64_t ncols, const double* LHS, int64_t ldL, const double* RHS, int64_t ldR, double* X,
@@ -2316,6 +2351,39 @@ int smk_solver_get_factors_device(smk_solver* s, int normalize, void* W, int dty
     if (!rc) rc = launch_strided_convert(s->H, DT_F64, 1, s->KP, H, dtypeH, rsH, csH, s->k, s->n, s->st);
     if (rc) return rc;
     return sync_and_check(s, nullptr);
+}
+
+// Labels / memberships of the local columns and the top terms of the topics, straight from the resident factors (H at H + c KP,
+// W as Wt + i KP: the k-contiguous layout the kernels of assign.hip read; the pad rows are never candidates).  normalize as in
+// smk_solver_get_factors; the solver is otherwise left exactly as it was.
+int smk_solver_labels(smk_solver* s, int normalize, void* stream, void* labels, void* memberships)
+{
+    if (!s) { set_error("smk_solver_labels: null solver"); return SMK_BAD_PARAM; }
+    if (!s->have_factors) { set_error("smk_solver_labels: the solver has no factors yet"); return SMK_BAD_PARAM; }
+    if (!labels) { set_error("smk_solver_labels: null output"); return SMK_BAD_PARAM; }
+    int rc = check_device_view(labels, DT_F32, s->n, 1, 1, s->n, true, "smk_solver_labels(labels)");       // 32-bit integers
+    if (!rc && memberships) rc = check_device_view(memberships, DT_F32, s->k, s->n, 1, s->k, true, "smk_solver_labels(memberships)");
+    if (rc) return rc;
+    Owned own;
+    rc = join_caller_stream(own, s->st, stream);
+    if (!rc) rc = factors_ready(s, normalize);
+    if (rc) return rc;
+    return labels_from_view(s->H, DT_F64, 1, s->KP, s->k, s->n, s->st, own, labels, memberships);
+}
+
+int smk_solver_top_terms(smk_solver* s, int normalize, int maxterms, void* stream, void* term_indices)
+{
+    if (!s) { set_error("smk_solver_top_terms: null solver"); return SMK_BAD_PARAM; }
+    if (!s->have_factors) { set_error("smk_solver_top_terms: the solver has no factors yet"); return SMK_BAD_PARAM; }
+    if (maxterms < 1) { set_error("smk_solver_top_terms: maxterms < 1"); return SMK_BAD_PARAM; }
+    if (!term_indices) { set_error("smk_solver_top_terms: null output"); return SMK_BAD_PARAM; }
+    int rc = check_device_view(term_indices, DT_F32, maxterms, s->k, 1, maxterms, true, "smk_solver_top_terms(term_indices)");
+    if (rc) return rc;
+    Owned own;
+    rc = join_caller_stream(own, s->st, stream);
+    if (!rc) rc = factors_ready(s, normalize);       // a row-sharded W is gathered here
+    if (rc) return rc;
+    return top_terms_from_view(s->Wt, DT_F64, s->KP, 1, s->m, s->k, maxterms, s->st, own, term_indices);
 }
 
 int smk_solver_get_factors(smk_solver* s, int normalize, double* W, int64_t ldW, double* H, int64_t ldH)

@@ -234,4 +234,10 @@ int matrix_host_csc(const smk_matrix* a);         // the host copy of a resident
 int check_device_view(const void* p, int dtype, i64 rows, i64 cols, i64 rs, i64 cs, bool output, const char* what);
 int join_caller_stream(smk::Owned& own, hipStream_t lib, void* caller_stream);
 
+// assign.cpp: labels / memberships of H (k x n) and top terms of W (m x k) from strided fp64 / fp32 views in device memory, on `st`
+// (DESIGN.md 14).  A view that is not k-contiguous is converted into a workspace of `own` first.  The outputs are device memory the
+// caller has checked.  Both synchronise `st` before they return.
+int labels_from_view(const void* H, int dtype, i64 rs, i64 cs, int k, i64 n, hipStream_t st, smk::Owned& own, void* labels, void* memberships);
+int top_terms_from_view(const void* W, int dtype, i64 rs, i64 cs, i64 m, int k, int maxterms, hipStream_t st, smk::Owned& own, void* term_indices);
+
 }  // namespace smk

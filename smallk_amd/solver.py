@@ -106,6 +106,58 @@ def _residual_factors(W, H, height, ncols, what):
     return tw, k
 
 
+def _factor_tensor(t, what):
+    """``_tensor_view(t, what, kinds="factor")`` for the labelling entries: a 2-D float64 / float32 torch tensor in GPU memory.
+    Everything else -- not a tensor, another element type, another rank, an empty or a CPU tensor -- is a ValueError, raised
+    before the library is loaded."""
+    if not _is_tensor(t):
+        raise ValueError(f"{what}: expected a torch tensor in GPU memory, got {type(t).__name__}")
+    if str(t.dtype) not in ("torch.float64", "torch.float32"):
+        raise ValueError(f"{what}: dtype {t.dtype}; the factors are float64 or float32")
+    if t.dim() != 2:
+        raise ValueError(f"{what}: expected 2 dimensions, got shape {tuple(t.shape)}")
+    if t.numel() == 0:
+        raise ValueError(f"{what}: empty tensor")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: the tensor is on {t.device}; it must be in GPU memory")
+    return _tensor_view(t, what, kinds="factor")
+
+
+def _maxterms(maxterms, what):
+    if isinstance(maxterms, bool) or not isinstance(maxterms, (int, np.integer)) or maxterms < 1:
+        raise ValueError(f"{what}: maxterms must be an integer >= 1, got {maxterms!r}")
+    return int(maxterms)
+
+
+def labels_device(H, *, memberships=False):
+    """Cluster labels of the columns of H (k, n), a float64 / float32 torch tensor in GPU memory (any strides): an int32 tensor
+    (n,), label = row of the largest entry, the first one on ties -- ``flatclust.compute_assignments`` without the download and
+    without its k <= n rule.  With ``memberships`` also P (k, n) float32, column c = column c of H scaled to sum 1, bit-equal to
+    ``compute_fuzzy_assignments`` (NaN for an all-zero column); its memory is document-major as the host function's."""
+    import torch
+    hp, ht, (rs, cs) = _factor_tensor(H, "labels_device(H)")
+    k, n = int(H.shape[0]), int(H.shape[1])
+    labels = torch.empty(n, dtype=torch.int32, device=H.device)
+    P = torch.empty((n, k), dtype=torch.float32, device=H.device) if memberships else None
+    L.check(L.lib().smk_labels_device(hp, ht, rs, cs, k, n, _stream_of(H), C.c_void_p(labels.data_ptr()),
+                                      C.c_void_p(P.data_ptr()) if memberships else None), "smk_labels_device")
+    return (labels, P.t()) if memberships else labels
+
+
+def top_terms_device(W, maxterms):
+    """The indices of the ``maxterms`` largest entries of every column of W (m, k), a float64 / float32 torch tensor in GPU
+    memory: an int32 tensor (k, maxterms), row j for topic j, largest first, equal entries by increasing index --
+    ``flatclust.top_terms`` without the download.  Slots past min(maxterms, m) read -1."""
+    import torch
+    maxterms = _maxterms(maxterms, "top_terms_device")
+    wp, wt, (rs, cs) = _factor_tensor(W, "top_terms_device(W)")
+    m, k = int(W.shape[0]), int(W.shape[1])
+    out = torch.full((k, maxterms), -1, dtype=torch.int32, device=W.device)
+    L.check(L.lib().smk_top_terms_device(wp, wt, rs, cs, m, k, maxterms, _stream_of(W), C.c_void_p(out.data_ptr())),
+            "smk_top_terms_device")
+    return out
+
+
 def initialize(device: int = -1):
     """NmfInitialize (nmf.hpp:71): select the GPU, create the stream.  Raises without a GPU."""
     L.check(L.lib().smk_initialize(device), "smk_initialize")
@@ -448,6 +500,36 @@ class NmfSolver:
             L.check(rc, "smk_solver_get_factors")
         return W, H
 
+    def labels_device(self, normalize=True, memberships=False):
+        """``labels_device`` of the solver's resident H (the local columns), no copy of it; ``normalize`` as in ``factors`` (the
+        clustering flows label from normalised factors)."""
+        import torch
+        dev = torch.device("cuda", L.lib().smk_current_device())
+        n = self.A.ncols
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        P = torch.empty((n, self.k), dtype=torch.float32, device=dev) if memberships else None
+        L.check(L.lib().smk_solver_labels(self._h, int(normalize), _stream_of(labels), C.c_void_p(labels.data_ptr()),
+                                          C.c_void_p(P.data_ptr()) if memberships else None), "smk_solver_labels")
+        return (labels, P.t()) if memberships else labels
+
+    def top_terms_device(self, maxterms, normalize=True):
+        """``top_terms_device`` of the solver's resident W, no copy of it"""
+        import torch
+        maxterms = _maxterms(maxterms, "top_terms_device")
+        out = torch.full((self.k, maxterms), -1, dtype=torch.int32, device=torch.device("cuda", L.lib().smk_current_device()))
+        L.check(L.lib().smk_solver_top_terms(self._h, int(normalize), maxterms, _stream_of(out), C.c_void_p(out.data_ptr())),
+                "smk_solver_top_terms")
+        return out
+
+    def project(self):
+        """H := argmin_{H >= 0} ||A - W H||_F with the solver's W fixed (BPP solvers): one exact block-pivoting solve, warm
+        start = the current H.  W and ``iteration_count`` stay.  Raises SmallkError(FAILURE) for a rank-deficient W."""
+        L.check(L.lib().smk_solver_project_h(self._h), "smk_solver_project_h")
+
+    @property
+    def iteration_count(self) -> int:
+        return int(L.lib().smk_solver_iteration_count(self._h))
+
     def residual(self, per_column=False) -> Residual:
         """``A.residual`` of the solver's current factors (not normalised), taken on the device; the solver is left exactly as
         it was.  Not for a solver with a communicator attached; a plain column shard returns its local sums."""
@@ -564,6 +646,48 @@ def nmf_device(A, W0, H0, algorithm, *, storage="f32", **kw) -> NmfResult:
         if solver is not None:
             solver.close()
         mat.close()
+
+
+def transform(A, W, *, H0=None):
+    """Fold new documents into a trained model: H = argmin_{H >= 0} ||A - W H||_F for the columns of A, a resident
+    ``DenseMatrix`` / ``SparseMatrix``, and W (m, k) a torch tensor in GPU memory or a numpy array.  Returns H (k, ncols) as a
+    float64 tensor on the GPU.  H0 (k, ncols, tensor or array; default zeros) is only the warm start of the block-pivoting
+    solve.  A BPP solver is built for the call, so its rule k <= ncols applies."""
+    if not isinstance(A, DenseMatrix):
+        raise ValueError(f"transform: A must be a resident DenseMatrix / SparseMatrix, got {type(A).__name__}")
+
+    def check(X, name, shape):
+        if _is_tensor(X):
+            _factor_tensor(X, f"transform({name})")
+        else:
+            X = np.asarray(X)
+            if X.dtype.kind not in "fiu":
+                raise ValueError(f"transform({name}): dtype {X.dtype}; expected real numbers")
+            X = np.ascontiguousarray(X, dtype=np.float64)
+        if len(X.shape) != 2 or (shape[0] is not None and X.shape[0] != shape[0]) or (shape[1] is not None and X.shape[1] != shape[1]):
+            raise ValueError(f"transform({name}): shape {tuple(X.shape)} does not match {shape}")
+        return X
+
+    W = check(W, "W", (A.height, None))
+    k = int(W.shape[1])
+    if k < 1:
+        raise ValueError("transform(W): k < 1")
+    if H0 is not None:
+        H0 = check(H0, "H0", (k, A.ncols))
+    import torch
+    dev = torch.device("cuda", L.lib().smk_current_device())
+    Wt = W if _is_tensor(W) else torch.from_numpy(W).to(dev)
+    if H0 is None:
+        H0t = torch.zeros((k, A.ncols), dtype=torch.float64, device=dev)
+    else:
+        H0t = H0 if _is_tensor(H0) else torch.from_numpy(H0).to(dev)
+    solver = NmfSolver(A, make_options(A.height, A.width_global, k, "BPP"))
+    try:
+        solver.set_factors_device(Wt, H0t)
+        solver.project()
+        return solver.factors_device()[1]
+    finally:
+        solver.close()
 
 
 def nnls_blockpivot(LHS, RHS, Xinit):
