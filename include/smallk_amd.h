@@ -248,6 +248,35 @@ int smk_matrix_residual_device(const smk_matrix* a, int k, const void* W, int dt
 /* of the solver's current factors on its matrix; the solver is left exactly as it was */
 int smk_solver_residual(smk_solver* s, double* resid_sq, double* a_sq, double* col_resid_sq);
 
+/* ---- truncated SVD and the NNDSVD start (Boutsidis & Gallopoulos 2008), on the device -------------------------------------------
+ * A randomised range finder with power iterations (Halko, Martinsson, Tropp), fp64 against the stored values of A, the same bits
+ * on every call.  l = min(k + oversample, m, n) columns are carried; k + oversample <= 128.
+ * oversample / power_iters < 0: the defaults (8 / 2).  omega: NULL (the test matrix is drawn from `seed`), or the caller's test
+ * matrix, an n x l view in device memory (SMK_DT_F64 / SMK_DT_F32, strides in elements).
+ * SMK_BAD_PARAM: k < 1, k > min(m, n), a bad omega.  SMK_UNSUPPORTED: k + oversample > 128, a column shard, a single-copy dense
+ * matrix (its transpose is NOT built behind the caller's back), a solver with a communicator. */
+typedef struct smk_svd_options {
+    int k, oversample, power_iters;
+    uint64_t seed;
+    const void* omega;
+    int omega_dtype;
+    int64_t omega_rs, omega_cs;
+} smk_svd_options;
+enum { SMK_NNDSVD = 0, SMK_NNDSVDA = 1 };       /* nndsvda: every zero of the start is replaced by mean(A) */
+/* A ~ U diag(S) V': U m x k and V n x k views in device memory (SMK_DT_F64 / SMK_DT_F32, the caller's stream), S_host k doubles,
+ * largest first.  A triplet past the numerical rank of A comes back as S = 0 with zero vectors.  No sign convention. */
+int smk_matrix_svd_device(const smk_matrix* a, const smk_svd_options* opts, void* U, int dtypeU, int64_t rsU, int64_t csU,
+                          double* S_host, void* V, int dtypeV, int64_t rsV, int64_t csV, void* stream);
+/* the NNDSVD start built from that SVD: W m x k, H k x n */
+int smk_matrix_nndsvd_device(const smk_matrix* a, const smk_svd_options* opts, int variant, void* W, int dtypeW, int64_t rsW,
+                             int64_t csW, void* H, int dtypeH, int64_t rsH, int64_t csH, void* stream);
+/* the same start as the solver's initial factors (opts->k is ignored: the solver's k); leaves the solver exactly as
+ * smk_solver_set_factors_device would with those factors.  opts may be NULL (all defaults, seed 0). */
+int smk_solver_set_factors_nndsvd(smk_solver* s, const smk_svd_options* opts, int variant);
+/* diagnostics of the calling thread's last SVD / NNDSVD call: the Gram matrices that went to the host for their eigendecomposition
+ * and the host time those decompositions took (tools/svd_rate.py) */
+int smk_svd_last_profile(int* host_trips, double* host_ms);
+
 /* ---- labels, memberships, top terms and fold-in, on the device (the device twins of smk_compute_assignments,
  * smk_compute_fuzzy_assignments and smk_top_terms below: the same comparisons in the same order, so the same integers and the
  * same membership bits; no k <= n and no height >= width requirement) -----------------------------------------------------

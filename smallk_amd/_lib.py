@@ -54,6 +54,15 @@ class PreprocessOptions(C.Structure):
     _fields_ = [("max_iter", C.c_uint), ("docs_per_term", C.c_uint), ("terms_per_doc", C.c_uint), ("boolean_mode", C.c_int)]
 
 
+class SvdOptions(C.Structure):
+    """struct smk_svd_options: rank, oversampling, power iterations, seed and the optional caller's test matrix (a device view)."""
+    _fields_ = [("k", C.c_int), ("oversample", C.c_int), ("power_iters", C.c_int), ("seed", C.c_uint64), ("omega", C.c_void_p),
+                ("omega_dtype", C.c_int), ("omega_rs", C.c_int64), ("omega_cs", C.c_int64)]
+
+
+NNDSVD, NNDSVDA = 0, 1
+
+
 class TreeNodeInfo(C.Structure):
     """struct smk_tree_node: the scalar fields of TreeNode<T> (hierclust/include/tree.hpp:31-50)."""
     _fields_ = [("priority", C.c_double), ("parent", C.c_uint), ("left_child", C.c_uint), ("right_child", C.c_uint),
@@ -128,6 +137,10 @@ SYMBOLS = {
     "smk_matrix_residual": (C.c_int, [_vp, C.c_int, _dp, _i64, _dp, _i64, _dp, _dp, _dp]),
     "smk_matrix_residual_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _dp, _dp, _vp]),
     "smk_solver_residual": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "smk_matrix_svd_device": (C.c_int, [_vp, C.POINTER(SvdOptions), _vp, C.c_int, _i64, _i64, _dp, _vp, C.c_int, _i64, _i64, _vp]),
+    "smk_matrix_nndsvd_device": (C.c_int, [_vp, C.POINTER(SvdOptions), C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp]),
+    "smk_solver_set_factors_nndsvd": (C.c_int, [_vp, C.POINTER(SvdOptions), C.c_int]),
+    "smk_svd_last_profile": (C.c_int, [C.POINTER(C.c_int), _dp]),
     "smk_labels_device": (C.c_int, [_vp, C.c_int, _i64, _i64, C.c_int, _i64, _vp, _vp, _vp]),
     "smk_top_terms_device": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, _vp, _vp]),
     "smk_solver_labels": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),

@@ -477,6 +477,29 @@ int launch_residual_sparse(const SegPlan& sp, const i64* colptr, const double* v
                            int k, const double* G, int ldg, const double* col_merged, double* scratch, double* col_r, double* col_a,
                            double* out2, hipStream_t st);
 
+// svd.hip: the tall-skinny kernels of the truncated SVD / NNDSVD.  Factors are KP x N, pitch KP = kp_of(l), l <= 128.
+// launch_svd_apply: Xout[:, c] = M' Xin[:, c] (M lin x lout, row-major, pitch ldm, device memory); rows >= lin of Xin are not
+// relied on, rows >= lout of Xout are written as zeros; Xout may be Xin.
+int launch_svd_apply(const double* Xin, double* Xout, int KP, i64 N, const double* M, int ldm, int lin, int lout, int num_cus, hipStream_t st);
+// the same apply that also leaves the Gram matrix of its output as *nblk_out partial sums in Gp ([.][KP * KP], for
+// launch_gram_reduce); Gp: svd_apply_gram_blocks(..) * KP * KP doubles.  Returns 1 (nothing launched) where KP has no fused kernel.
+int svd_apply_gram_blocks(int KP, i64 N, int num_cus);
+int launch_svd_apply_gram(const double* Xin, double* Xout, int KP, i64 N, const double* M, int ldm, int lin, int lout, double* Gp, int* nblk_out,
+                          int num_cus, hipStream_t st);
+// rows [0, l) of X: counter-based uniform values centred to [-0.5, 0.5), entry (row r, column j) keyed by j * l + r; pad rows zero
+int launch_svd_fill_centred(double* X, int KP, int l, i64 N, unsigned long long seed, hipStream_t st);
+// out[4][KP]: per factor row the sum of squares of its positive entries, of its negative entries, the largest positive entry, the
+// largest magnitude of a negative one (fixed order); scratch: nndsvd_stats_scratch_elems doubles
+size_t nndsvd_stats_scratch_elems(int KP, i64 N);
+int launch_nndsvd_stats(const double* X, int KP, int k, i64 N, double* scratch, double* out, hipStream_t st);
+// in place: row r becomes its chosen part (prm[r]: 2 |x|, 1 max(x, 0), -1 max(-x, 0), 0 nothing) times prm[KP + r]; a part below
+// prm[2 KP + r] becomes zero and every zero becomes `fill`
+int launch_nndsvd_write(double* X, int KP, int k, i64 N, const double* prm, double fill, hipStream_t st);
+// *out = the sum of the stored entries in a fixed order; part: sum_entries_blocks(..) doubles
+int sum_entries_blocks(i64 cols);
+int launch_sum_entries_dense(const void* A, int storage, i64 ld, i64 rows, i64 cols, double* part, double* out, hipStream_t st);
+int launch_sum_entries_sparse(const double* val, i64 nnz, double* part, double* out, hipStream_t st);
+
 // assign.hip: labels / memberships of the columns of H and the top terms of the columns of W, the factors fp64 or fp32 (DT_*) in
 // their k-contiguous layout: column c of H at H + c * ldc, row i of W at W + i * ld (elements).  The host functions' comparisons in
 // the host functions' order: the same integers, the same membership bits.  memb: k * n floats (document c at c * k) or null.

@@ -106,6 +106,35 @@ def _residual_factors(W, H, height, ncols, what):
     return tw, k
 
 
+NNDSVD_VARIANTS = {"nndsvd": L.NNDSVD, "nndsvda": L.NNDSVDA}
+
+
+def _svd_options(what, k, height, ncols, oversample, power_iters, seed, omega):
+    """The checks of ``DenseMatrix.svd`` / ``nndsvd`` made before the library is called, and the ``smk_svd_options`` they fill.
+    Integers are integers (TypeError otherwise) and non-negative (ValueError); ``omega`` is None or a 2-D float64 / float32 torch
+    tensor in GPU memory (``_tensor_view``).  Its shape must be (ncols, min(k + oversample, height, ncols)): another shape is the
+    library's SMK_BAD_PARAM, raised here because the C entry sees only a pointer and strides.  Returns (options, keep-alive)."""
+    for name, v in (("k", k), ("oversample", oversample), ("power_iters", power_iters), ("seed", seed)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{what}: {name} must be an integer, got {type(v).__name__}")
+    if oversample < 0 or power_iters < 0 or seed < 0:
+        raise ValueError(f"{what}: oversample, power_iters and seed must be >= 0")
+    o = L.SvdOptions(int(k), int(oversample), int(power_iters), int(seed), None, L.DT_F64, 0, 0)
+    if omega is not None:
+        ptr, dt, (rs, cs) = _tensor_view(omega, f"{what}(omega)", kinds="factor")
+        l = min(int(k) + int(oversample), height, ncols)
+        if 1 <= k <= min(height, ncols) and tuple(omega.shape) != (ncols, l):
+            raise L.SmallkError(L.BAD_PARAM, what, f"omega has shape {tuple(omega.shape)}, expected ({ncols}, {l})")
+        o.omega, o.omega_dtype, o.omega_rs, o.omega_cs = ptr, dt, rs, cs
+    return o, omega
+
+
+def _nndsvd_variant(what, variant):
+    if variant not in NNDSVD_VARIANTS:
+        raise ValueError(f"{what}: variant must be one of {sorted(NNDSVD_VARIANTS)}, got {variant!r}")
+    return NNDSVD_VARIANTS[variant]
+
+
 def _factor_tensor(t, what):
     """``_tensor_view(t, what, kinds="factor")`` for the labelling entries: a 2-D float64 / float32 torch tensor in GPU memory.
     Everything else -- not a tensor, another element type, another rank, an empty or a CPU tensor -- is a ValueError, raised
@@ -303,6 +332,40 @@ class DenseMatrix:
                                                 _p(col) if per_column else None), "smk_matrix_residual")
         return Residual(r.value, a.value, col)
 
+    def svd(self, k, *, oversample=8, power_iters=2, seed=0, omega=None):
+        """The k leading singular triplets of the stored A, computed on the device in fp64 (randomised range finder with
+        ``power_iters`` power iterations on min(k + oversample, m, n) columns; k + oversample <= 128): ``(U, S, V)`` with U (m, k)
+        and V (n, k) float64 torch tensors on the GPU and S a numpy array, largest first.  The same bits on every call; no sign
+        convention.  Triplets past the numerical rank of A come back as S = 0 with zero vectors.  ``omega``: the caller's test
+        matrix (n, l), a float64 / float32 tensor in GPU memory, instead of the one drawn from ``seed``."""
+        import torch
+        o, keep = _svd_options("svd", k, self.height, self.ncols, oversample, power_iters, seed, omega)
+        dev = torch.device("cuda", L.lib().smk_current_device())
+        kk = max(int(k), 1)
+        U = torch.empty((self.height, kk), dtype=torch.float64, device=dev)
+        V = torch.empty((self.ncols, kk), dtype=torch.float64, device=dev)
+        S = np.zeros(kk)
+        L.check(L.lib().smk_matrix_svd_device(self._h, C.byref(o), C.c_void_p(U.data_ptr()), L.DT_F64, U.stride(0), U.stride(1), _p(S),
+                                              C.c_void_p(V.data_ptr()), L.DT_F64, V.stride(0), V.stride(1), _stream_of(U)),
+                "smk_matrix_svd_device")
+        return U, S, V
+
+    def nndsvd(self, k, *, variant="nndsvd", oversample=8, power_iters=2, seed=0, omega=None):
+        """The NNDSVD start (Boutsidis & Gallopoulos 2008) of a rank-k factorisation from ``svd`` with the same arguments:
+        ``(W0, H0)``, float64 torch tensors on the GPU, W0 (m, k) and H0 (k, n).  ``variant``: "nndsvd" keeps the zeros,
+        "nndsvda" replaces them by mean(A).  Deterministic: no seed files, the same start on every run."""
+        import torch
+        v = _nndsvd_variant("nndsvd", variant)
+        o, keep = _svd_options("nndsvd", k, self.height, self.ncols, oversample, power_iters, seed, omega)
+        dev = torch.device("cuda", L.lib().smk_current_device())
+        kk = max(int(k), 1)
+        W = torch.empty((self.height, kk), dtype=torch.float64, device=dev)
+        H = torch.empty((kk, self.ncols), dtype=torch.float64, device=dev)
+        L.check(L.lib().smk_matrix_nndsvd_device(self._h, C.byref(o), v, C.c_void_p(W.data_ptr()), L.DT_F64, W.stride(0), W.stride(1),
+                                                 C.c_void_p(H.data_ptr()), L.DT_F64, H.stride(0), H.stride(1), _stream_of(W)),
+                "smk_matrix_nndsvd_device")
+        return W, H
+
     def close(self):
         if self._h:
             L.lib().smk_matrix_destroy(self._h)
@@ -451,6 +514,13 @@ class NmfSolver:
                              f"({self.A.height}, {self.k}) / ({self.k}, {self.A.ncols})")
         L.check(L.lib().smk_solver_set_factors_device(self._h, wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W0)),
                 "smk_solver_set_factors_device")
+
+    def set_factors_nndsvd(self, variant="nndsvd", *, oversample=8, power_iters=2, seed=0, omega=None):
+        """The NNDSVD start of ``A.nndsvd(k, ...)`` as the initial factors, built and handed over on the device: the solver is
+        left exactly as ``set_factors_device(*A.nndsvd(k, ...))`` leaves it."""
+        v = _nndsvd_variant("set_factors_nndsvd", variant)
+        o, keep = _svd_options("set_factors_nndsvd", self.k, self.A.height, self.A.ncols, oversample, power_iters, seed, omega)
+        L.check(L.lib().smk_solver_set_factors_nndsvd(self._h, C.byref(o), v), "smk_solver_set_factors_nndsvd")
 
     def factors_device(self, normalize=False, dtype=None):
         """``factors`` as torch tensors on the GPU: W (m, k) and H (k, ncols), float64 (default) or float32 = the fp64 factor
