@@ -56,10 +56,9 @@ struct BPCfg {
     static constexpr int PD = NSTAGE_ - 1;          // stages in flight ahead of the consumer
     static constexpr int TI = STAGE_BYTES / 1024;   // wave-level 1-KiB loads per stage
     static constexpr int LPS = TI / NLD;            // per loading wave
-    static_assert(TI % NLD == 0, "loads per stage must split evenly over the loading waves");
-    static_assert(KT % WK_ == 0, "k tiles must split evenly over the wave groups");
-    static_assert(LPS * PD <= 63, "vmcnt is a 6-bit counter");
-    static_assert(STAGE_BYTES * NSTAGE <= 160 * 1024, "LDS ring exceeds 160 KiB");
+    static_assert(STAGE_BYTES == bp_stage_bytes(EBYTES, KT, NSPLIT, BPRow{MB_, NSTAGE_, CW_, WK_, NWL_}), "the planner's stage is the kernel's");
+    static_assert(bp_fits(EBYTES, KT, NSPLIT, BPRow{MB_, NSTAGE_, CW_, WK_, NWL_}),
+                  "k tiles and loads split evenly over the waves, vmcnt stays <= 63, the ring <= 160 KiB");
 };
 
 #ifdef SMK_BP_PROFILE
@@ -643,7 +642,6 @@ __global__ __launch_bounds__(256) void reduce_pack_f16x2_k16_kernel(const double
 // operand format: bf16 fragments (E = 8) for bf16 storage and for the fp32 "bf16x3" emulation
 // (nsplit == 3); native fp32 fragments (E = 4, one term) otherwise
 static inline bool pack_is_bf16(int storage, int nsplit) { return storage == STORE_BF16 || nsplit >= 2; }
-static inline int pack_terms(int nsplit) { return nsplit == NSPLIT_F16X2 ? 2 : nsplit; }
 
 static inline i64 pack_nq(int storage, int nsplit, i64 N)
 {
@@ -771,7 +769,8 @@ struct F3Cfg {
     static constexpr int PD = NSTAGE_ - 1;
     static constexpr int TI = STAGE_BYTES / 1024;
     static constexpr int LPS = TI / NLD;
-    static constexpr bool OK = (TI % NLD == 0) && (LPS * PD <= 63) && (STAGE_BYTES * NSTAGE <= 160 * 1024);
+    static_assert(STAGE_BYTES == f3_stage_bytes(F3Row{F3, MB_, NSTAGE_, NWL_}, KT, NS), "the planner's stage is the kernel's");
+    static constexpr bool OK = f3_fits(F3Row{F3, MB_, NSTAGE_, NWL_}, KT, NS);          // (the shape columns of a row)
 };
 
 // TAIL workgroups of bigprod_f3_kernel (256 threads): workgroup w of 16 adds up entries 16 w .. 16 w + 15 of nblk partial
@@ -1373,6 +1372,18 @@ __global__ __launch_bounds__(64 * (4 + NWL), 2) void bigprod_f3p_kernel(const un
             }
 }
 
+// workgroups of a streaming launch and log2 of its row splits: up to 8 splits, a group of 8 blocks (one per XCD) holds the 8 / S
+// tiles whose splits share an XCD's L2
+static i64 bigprod_grid(const BigProdPlan& pl, int* logS_out)
+{
+    int logS = 0;
+    while ((1 << logS) < pl.S) ++logS;
+    *logS_out = logS;
+    if (pl.S > 8) return pl.tiles * pl.S;
+    const i64 per = 8 >> logS;                       // tiles per group of 8 blocks
+    return (pl.tiles + per - 1) / per * 8;
+}
+
 template <int KT, int NS, int NSTAGE, int NWL, int FOLD, int PIN = 1, int FMT = 0>
 static int launch_f3p_t(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
 {
@@ -1388,57 +1399,14 @@ static int launch_f3p_t(const BigProdPlan& pl, const void* B, i64 ldb, const voi
             SMK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             once.done();
         }
-        int logS = 0;
-        while ((1 << logS) < pl.S) ++logS;
-        i64 grid;
-        if (pl.S <= 8) {
-            const i64 per = 8 >> logS;
-            grid = (pl.tiles + per - 1) / per * 8;
-        } else {
-            grid = pl.tiles * pl.S;
-        }
+        int logS;
+        const i64 grid = bigprod_grid(pl, &logS);
         kern<<<(unsigned)grid, 64 * C::NW, lds, st>>>((const unsigned char*)B, ldb * 4, (const unsigned char*)Xp, P, pl.stages,
                                                       pl.nst, pl.tiles, pl.ncols_pad, pl.S, logS, pl.pstride, pl.oscale, (float)pl.ascale, pl.accum | (pl.temporal ? 2 : 0));
         SMK_HIP(hipGetLastError());
         return 0;
     }
 }
-
-struct F3Variant { int mb, nstage, nwl, fold, wps; };
-static const F3Variant kF3Variants[] = {
-    {32, 2, 0, 2, 2},   // 100: no loader waves, two workgroups per CU
-    {32, 3, 0, 2, 2},   // 101
-    {32, 4, 4, 2, 2},   // 102: 4 loader waves, one workgroup per CU, deep ring
-    {32, 5, 4, 2, 2},   // 103
-    {32, 2, 2, 2, 3},   // 104: 2 loader waves, two workgroups per CU (168 registers)
-    {64, 2, 0, 1, 2},   // 105: 64-row stages
-    {64, 2, 4, 1, 2},   // 106
-    {32, 4, 4, 4, 2},   // 107: fold every 4 stages (128-row chains)
-    {32, 2, 0, 4, 2},   // 108
-    {32, 4, 2, 2, 2},   // 109
-    // software-pipelined kernel (bigprod_f3p_kernel); wps unused
-    {32, 4, 4, 4, 0},   // 110: 4 loader waves, 4-deep ring, fold every 4 stages
-    {32, 5, 4, 4, 0},   // 111
-    {32, 5, 4, 2, 0},   // 112
-    {32, 4, 2, 4, 0},   // 113: 2 loader waves
-    {32, 5, 2, 4, 0},   // 114
-    {32, 3, 2, 4, 0},   // 115: shallow ring, two workgroups per CU fit
-    {32, 5, 4, 8, 0},   // 116: fold every 8 stages
-    {32, 5, 4, 4, 0},   // 117: as 111 without the pinned interleave (compiler's own schedule)
-    {32, 5, 4, 4, 0},   // 118: EXPERIMENT no bf16 split
-    {32, 5, 4, 4, 0},   // 119: EXPERIMENT no MFMA
-    {32, 5, 4, 4, 0},   // 120: EXPERIMENT neither
-    {32, 5, 4, 4, 0},   // 121: loader waves at priority 3
-    {32, 5, 4, 4, 0},   // 122: loader priority, compiler schedule
-    {32, 5, 4, 4, 0},   // 123: EXPERIMENT no X fetch (full compute)
-    {32, 5, 4, 4, 0},   // 124: EXPERIMENT no X fetch, no MFMA, no split
-    {32, 2, 0, 8, 2},   // 125: as 108, folding into fp64 every 8 stages (256-row fp32 chains)
-    {32, 3, 0, 4, 2},   // 126: as 108 with a 3-deep ring
-    {32, 2, 0, 16, 2},  // 127: as 125, folding every 16 stages (512-row fp32 chains)
-    {32, 2, 0, 2, 2},   // 128: as 108, folding every 2 stages (64-row fp32 chains)
-    {32, 2, 0, 1, 2},   // 129: as 108, folding every stage (32-row fp32 chains: two roundings per accumulator and fold)
-};
-static const int kNumF3 = (int)(sizeof(kF3Variants) / sizeof(kF3Variants[0]));
 
 template <int KT, int NS, int MB, int NSTAGE, int NWL, int FOLD, int WPS, int FMT = 0, int TAIL = 0>
 static int launch_f3_t(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
@@ -1455,15 +1423,8 @@ static int launch_f3_t(const BigProdPlan& pl, const void* B, i64 ldb, const void
             SMK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
             once.done();
         }
-        int logS = 0;
-        while ((1 << logS) < pl.S) ++logS;
-        i64 grid;
-        if (pl.S <= 8) {
-            const i64 per = 8 >> logS;
-            grid = (pl.tiles + per - 1) / per * 8;
-        } else {
-            grid = pl.tiles * pl.S;
-        }
+        int logS;
+        i64 grid = bigprod_grid(pl, &logS);
         if (TAIL == 1) grid += pl.tail_check.part ? 24 : 16;
         InvRide ride;
         if (TAIL != 2 && pl.inv_ride.G && pl.inv_ride.k > 16 && pl.inv_ride.k <= 64) { ride = pl.inv_ride; grid += 8; }
@@ -1475,97 +1436,58 @@ static int launch_f3_t(const BigProdPlan& pl, const void* B, i64 ldb, const void
     }
 }
 
+// ---- dispatch over kF3Variants (bigprod_plan.h): row I of the table under one form -- NS operand terms, FMT = 1 the fp16 two-term
+// form, TAIL = 1 with the Gram reduction -- is instantiated exactly where the row carries the form's column
+using LaunchFn = int (*)(const BigProdPlan&, const void*, i64, const void*, double*, hipStream_t);
+constexpr int NOT_BUILT = -1;        // the caller names the form in its error (a launcher returns 0, 1 with a rider, or -100: never this)
+
+template <int KT, int NS, int FMT, int TAIL, int I>
+static int launch_f3_row(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
+{
+    constexpr F3Row r = kF3Variants[I];
+    static_assert(!r.tail || (r.kernel == F3 && r.f16), "the Gram reduction rides in bigprod_f3_kernel under the fp16 form");
+    if constexpr (!(TAIL == 1 ? r.tail : FMT == 1 ? r.f16 : r.bf)) return NOT_BUILT;
+    else if constexpr (r.kernel == F3P) return launch_f3p_t<KT, NS, r.nstage, r.nwl, r.fold, r.arg, FMT>(pl, B, ldb, Xp, P, st);
+    else return launch_f3_t<KT, NS, r.mb, r.nstage, r.nwl, r.fold, r.arg, FMT, TAIL>(pl, B, ldb, Xp, P, st);
+}
+
+template <int KT, int NS, int FMT, int TAIL, size_t... I>
+static int launch_f3_rows(std::index_sequence<I...>, const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
+{
+    static constexpr LaunchFn row[] = {&launch_f3_row<KT, NS, FMT, TAIL, (int)I>...};
+    return is_f3_variant(pl.variant) ? row[pl.variant - 100](pl, B, ldb, Xp, P, st) : NOT_BUILT;
+}
+
+// the two- and three-term bf16 forms
 template <int KT, int NS>
 static int launch_f3(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
 {
-    switch (pl.variant - 100) {
-        case 0: return launch_f3_t<KT, NS, 32, 2, 0, 2, 2>(pl, B, ldb, Xp, P, st);
-        case 1: return launch_f3_t<KT, NS, 32, 3, 0, 2, 2>(pl, B, ldb, Xp, P, st);
-        case 2: return launch_f3_t<KT, NS, 32, 4, 4, 2, 2>(pl, B, ldb, Xp, P, st);
-        case 3: return launch_f3_t<KT, NS, 32, 5, 4, 2, 2>(pl, B, ldb, Xp, P, st);
-        case 4: return launch_f3_t<KT, NS, 32, 2, 2, 2, 3>(pl, B, ldb, Xp, P, st);
-        case 5: return launch_f3_t<KT, NS, 64, 2, 0, 1, 2>(pl, B, ldb, Xp, P, st);
-        case 6: return launch_f3_t<KT, NS, 64, 2, 4, 1, 2>(pl, B, ldb, Xp, P, st);
-        case 7: return launch_f3_t<KT, NS, 32, 4, 4, 4, 2>(pl, B, ldb, Xp, P, st);
-        case 8: return launch_f3_t<KT, NS, 32, 2, 0, 4, 2>(pl, B, ldb, Xp, P, st);
-        case 9: return launch_f3_t<KT, NS, 32, 4, 2, 2, 2>(pl, B, ldb, Xp, P, st);
-        case 10: return launch_f3p_t<KT, NS, 4, 4, 4>(pl, B, ldb, Xp, P, st);
-        case 11: return launch_f3p_t<KT, NS, 5, 4, 4>(pl, B, ldb, Xp, P, st);
-        case 12: return launch_f3p_t<KT, NS, 5, 4, 2>(pl, B, ldb, Xp, P, st);
-        case 13: return launch_f3p_t<KT, NS, 4, 2, 4>(pl, B, ldb, Xp, P, st);
-        case 14: return launch_f3p_t<KT, NS, 5, 2, 4>(pl, B, ldb, Xp, P, st);
-        case 15: return launch_f3p_t<KT, NS, 3, 2, 4>(pl, B, ldb, Xp, P, st);
-        case 16: return launch_f3p_t<KT, NS, 5, 4, 8>(pl, B, ldb, Xp, P, st);
-        case 17: return launch_f3p_t<KT, NS, 5, 4, 4, 0>(pl, B, ldb, Xp, P, st);
-        case 18: return launch_f3p_t<KT, NS, 5, 4, 4, 2>(pl, B, ldb, Xp, P, st);
-        case 19: return launch_f3p_t<KT, NS, 5, 4, 4, 4>(pl, B, ldb, Xp, P, st);
-        case 20: return launch_f3p_t<KT, NS, 5, 4, 4, 6>(pl, B, ldb, Xp, P, st);
-        case 21: return launch_f3p_t<KT, NS, 5, 4, 4, 9>(pl, B, ldb, Xp, P, st);
-        case 22: return launch_f3p_t<KT, NS, 5, 4, 4, 8>(pl, B, ldb, Xp, P, st);
-        case 23: return launch_f3p_t<KT, NS, 5, 4, 4, 16>(pl, B, ldb, Xp, P, st);
-        case 24: return launch_f3p_t<KT, NS, 5, 4, 4, 22>(pl, B, ldb, Xp, P, st);
-        case 25: return launch_f3_t<KT, NS, 32, 2, 0, 8, 2>(pl, B, ldb, Xp, P, st);
-        case 26: return launch_f3_t<KT, NS, 32, 3, 0, 4, 2>(pl, B, ldb, Xp, P, st);
-        case 27: return launch_f3_t<KT, NS, 32, 2, 0, 16, 2>(pl, B, ldb, Xp, P, st);
-        default: break;
-    }
-    set_error("unknown bigprod f3 variant");
-    return -100;
+    const int rc = launch_f3_rows<KT, NS, 0, 0>(std::make_index_sequence<kNumF3>{}, pl, B, ldb, Xp, P, st);
+    if (rc == NOT_BUILT) { set_error("unknown bigprod f3 variant"); return -100; }
+    return rc;
 }
 
-// the launches that go to bigprod_f3_kernel from the stored transpose (launch_bigprod's dispatch): they can carry the Gram inverse
-bool bigprod_supports_ride(const BigProdPlan& pl)
-{
-    if (pl.nsplit == NSPLIT_F64) return !pl.tr;                  // the accurate form (bigprod_f64_kernel at k > 2), either storage
-    if (pl.tr) return false;
-    if (pl.storage == STORE_BF16 || pl.variant < 100) return true;  // bigprod_kernel (bf16 storage; fp32 storage in its older forms)
-    if (pl.storage != STORE_F32) return false;
-    const int v = pl.variant - 100;
-    if (pl.nsplit == NSPLIT_F16X2) return v == 8 || (v >= 25 && v <= 29);
-    if (pl.nsplit == 2 || pl.nsplit == 3) return (v >= 0 && v <= 9) || (v >= 25 && v <= 27);
-    return false;
-}
+// the launches that can carry the Gram inverse / the Gram reduction (launch_bigprod's dispatch, read from the tables)
+bool bigprod_supports_ride(const BigProdPlan& pl) { return variant_rides(pl.storage, pl.nsplit, pl.variant, pl.tr != 0); }
+bool bigprod_supports_tail(const BigProdPlan& pl) { return variant_tails(pl.storage, pl.nsplit, pl.kt, pl.variant); }
 
-// fp16 two-term form: the variants that won for the bf16 forms
-// the variants (fold intervals 4 / 8 / 2 / 1 of the two-workgroup kernel, one k tile) that can carry the Gram reduction
-bool bigprod_supports_tail(const BigProdPlan& pl)
-{
-    return pl.nsplit == NSPLIT_F16X2 && pl.storage == STORE_F32 && pl.kt == 1 &&
-           (pl.variant == 108 || pl.variant == 125 || pl.variant == 128 || pl.variant == 129);
-}
-
+// the fp16 two-term form
 template <int KT>
 static int launch_f3_f16(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
 {
+    constexpr auto rows = std::make_index_sequence<kNumF3>{};
     if constexpr (KT == 1) {
         if (pl.tail_nblk > 0) {
             if (!pl.tail_gp || !pl.tail_g) { set_error("bigprod: tail without buffers"); return -100; }
-            switch (pl.variant - 100) {
-                case 8: return launch_f3_t<KT, 2, 32, 2, 0, 4, 2, 1, 1>(pl, B, ldb, Xp, P, st);
-                case 25: return launch_f3_t<KT, 2, 32, 2, 0, 8, 2, 1, 1>(pl, B, ldb, Xp, P, st);
-                case 28: return launch_f3_t<KT, 2, 32, 2, 0, 2, 2, 1, 1>(pl, B, ldb, Xp, P, st);
-                case 29: return launch_f3_t<KT, 2, 32, 2, 0, 1, 2, 1, 1>(pl, B, ldb, Xp, P, st);
-                default: break;
-            }
-            set_error("bigprod: this variant cannot carry the Gram reduction");
-            return -100;
+            const int rc = launch_f3_rows<KT, 2, 1, 1>(rows, pl, B, ldb, Xp, P, st);
+            if (rc == NOT_BUILT) { set_error("bigprod: this variant cannot carry the Gram reduction"); return -100; }
+            return rc;
         }
     }
     if (pl.tail_nblk > 0) { set_error("bigprod: this shape cannot carry the Gram reduction"); return -100; }
-    switch (pl.variant - 100) {
-        case 8: return launch_f3_t<KT, 2, 32, 2, 0, 4, 2, 1>(pl, B, ldb, Xp, P, st);
-        case 10: return launch_f3p_t<KT, 2, 4, 4, 4, 1, 1>(pl, B, ldb, Xp, P, st);
-        case 11: return launch_f3p_t<KT, 2, 5, 4, 4, 1, 1>(pl, B, ldb, Xp, P, st);
-        case 15: return launch_f3p_t<KT, 2, 3, 2, 4, 1, 1>(pl, B, ldb, Xp, P, st);
-        case 25: return launch_f3_t<KT, 2, 32, 2, 0, 8, 2, 1>(pl, B, ldb, Xp, P, st);
-        case 26: return launch_f3_t<KT, 2, 32, 3, 0, 4, 2, 1>(pl, B, ldb, Xp, P, st);
-        case 27: return launch_f3_t<KT, 2, 32, 2, 0, 16, 2, 1>(pl, B, ldb, Xp, P, st);
-        case 28: return launch_f3_t<KT, 2, 32, 2, 0, 2, 2, 1>(pl, B, ldb, Xp, P, st);
-        case 29: return launch_f3_t<KT, 2, 32, 2, 0, 1, 2, 1>(pl, B, ldb, Xp, P, st);
-        default: break;
-    }
-    set_error("unknown bigprod f16 variant");
-    return -100;
+    const int rc = launch_f3_rows<KT, 2, 1, 0>(rows, pl, B, ldb, Xp, P, st);
+    if (rc == NOT_BUILT) { set_error("unknown bigprod f16 variant"); return -100; }
+    return rc;
 }
 
 // ==========================================================================
@@ -1825,46 +1747,64 @@ static int launch_bigprod_f64(const BigProdPlan& pl, const void* B, i64 ldb, con
     return ride.G ? 1 : 0;                       // 1: the launch carried the Gram inverse
 }
 
-constexpr bool bp_fits(int ebytes, int kt, int nsplit, int mb, int nstage, int cw, int wk, int nwl);
-// ---- kernel variants (tile shape / pipeline depth); chosen per plan, SMK_BP_VARIANT overrides ----
-struct BPVariant { int mb, nstage, cw, wk, nwl; };
-static const BPVariant kVariants[] = {
-    {64, 3, 1, 1, 0},    // 0: 128 cols x 64 rows, 3-deep ring
-    {64, 4, 1, 1, 0},    // 1
-    {64, 5, 1, 1, 0},    // 2
-    {128, 2, 1, 1, 0},   // 3
-    {128, 3, 1, 1, 0},   // 4
-    {64, 3, 2, 1, 0},    // 5: 256 cols per workgroup
-    {64, 2, 1, 1, 0},    // 6: two workgroups per CU
-    {32, 2, 1, 1, 0},    // 7: 32-row stages (fp32: one 128-B line per column per stage)
-    {32, 3, 1, 1, 0},    // 8
-    {32, 4, 1, 1, 0},    // 9
-    {64, 2, 1, 2, 0},    // 10: k in (32,64]: 8 waves, the two k tiles on different waves
-    {64, 3, 1, 2, 0},    // 11
-    {64, 4, 1, 2, 0},    // 12
-    {32, 4, 1, 2, 0},    // 13
-    {64, 2, 2, 2, 0},    // 14: 256 columns, 8 waves
-    // wave-specialised: +4 (or +2) loader waves that only issue the LDS-DMA loads
-    {64, 3, 1, 1, 4},    // 15
-    {64, 4, 1, 1, 4},    // 16
-    {64, 5, 1, 1, 4},    // 17
-    {64, 3, 1, 2, 4},    // 18: k in (32,64]
-    {64, 4, 1, 2, 4},    // 19
-    {32, 4, 1, 1, 2},    // 20: fp32 emulation, k <= 32
-    {32, 4, 1, 2, 4},    // 21: fp32 emulation, k in (32,64]
-    {32, 5, 1, 2, 4},    // 22
-    {64, 2, 1, 1, 4},    // 23
-};
-static const int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
+// row splits of a streaming pass: enough workgroups for >= 4 rounds over the CUs, but keep >= 8 stages per split;
+// SMK_BP_SPLITS=n asks for n instead (rounded up to a power of two, at most 64)
+static int bigprod_row_splits(i64 tiles, i64 stages, int num_cus)
+{
+    int S = 1;
+    while (tiles * S < 2 * (i64)num_cus && S < 64 && stages / (2 * S) >= 8) S *= 2;
+    const int want = sw::bp_splits();
+    if (want > 0) { S = 1; while (S < want && S < 64) S *= 2; }
+    return S;
+}
 
-int plan_bigprod_groups(int storage, int k, i64 len, i64 ncols, int nsplit, int num_cus, BigProdPlan* out)
+// stages, tiles, padding and row splits of a plan whose kernel takes mb rows per stage and nb columns per tile
+static void plan_geometry(BigProdPlan& pl, int mb, int nb, i64 len, i64 ncols, int num_cus)
+{
+    pl.mb = mb; pl.nb = nb;
+    pl.stages = (len + mb - 1) / mb;
+    pl.tiles = (ncols + nb - 1) / nb;
+    pl.ncols_pad = round_up(ncols, COL_PAD);
+    int S = 1;
+    if (pl.nsplit == NSPLIT_F64) while (pl.tiles * S < 4 * (i64)num_cus && S < 64 && pl.stages / (2 * S) >= 4) S *= 2;
+    else S = bigprod_row_splits(pl.tiles, pl.stages, num_cus);
+    pl.S = S;
+    pl.nst = (pl.stages + S - 1) / S;
+    pl.p_elems = (size_t)S * pl.ncols_pad * pl.pstride;   // doubles
+}
+
+// the plan of one group of at most 64 factor rows.  tr: the H*A' pass of a single-copy matrix taken from A itself -- the geometry of
+// the stored-transpose pass (128 rows of A per tile, a stage of columns of A) on the kernel shapes that exist for that source
+static BigProdPlan plan_group(int storage, int k, i64 len, i64 ncols, int nsplit, int num_cus, bool tr)
+{
+    BigProdPlan pl;
+    pl.storage = storage;
+    pl.kt = kt_of(k);
+    pl.k0 = 0; pl.kg = k; pl.pstride = kpp_of(k); pl.pack_offset = 0;
+    pl.tr = tr;
+    // fp32 storage: nsplit 3 selects the bf16x3 emulation (default), 1 the native fp32 MFMA
+    pl.nsplit = (tr || nsplit == NSPLIT_F64) ? nsplit : plan_nsplit(storage, nsplit);
+    Want want{}, want_k64{};
+    if (!tr && nsplit != NSPLIT_F64) {     // read per plan
+        const auto e = sw::bp_variant(), e64 = sw::bp_variant_k64();
+        want = {e.set, e.v}; want_k64 = {e64.set, e64.v};
+    }
+    const int v = pl.variant = choose_variant(storage, pl.kt, nsplit, len, want, want_k64, tr);
+    if (tr || v == ACCURATE_VARIANT) pl.len = len;
+    if (v == ACCURATE_VARIANT) plan_geometry(pl, 64, 64, len, ncols, num_cus);         // fp64 matrix cores, 64 x 64 tiles
+    else if (v >= 100) plan_geometry(pl, kF3Variants[v - 100].mb, 128, len, ncols, num_cus);
+    else plan_geometry(pl, kVariants[v].mb, 128 * kVariants[v].cw, len, ncols, num_cus);
+    return pl;
+}
+
+static int plan_groups(int storage, int k, i64 len, i64 ncols, int nsplit, int num_cus, bool tr, BigProdPlan* out)
 {
     int ng = 0;
     size_t off = 0;
     const int pstride = kpp_of(k);
     for (int k0 = 0; k0 < k; k0 += 64, ++ng) {
         const int kg = k - k0 < 64 ? k - k0 : 64;
-        BigProdPlan pl = plan_bigprod(storage, kg, len, ncols, nsplit, num_cus);
+        BigProdPlan pl = plan_group(storage, kg, len, ncols, nsplit, num_cus, tr);
         pl.k0 = k0; pl.kg = kg; pl.pstride = pstride; pl.pack_offset = off;
         if (ng > 0) {                              // one P layout for all groups: the first group's row splits
             pl.S = out[0].S;
@@ -1877,152 +1817,15 @@ int plan_bigprod_groups(int storage, int k, i64 len, i64 ncols, int nsplit, int 
     return ng;
 }
 
-// row splits of a streaming pass: enough workgroups for >= 4 rounds over the CUs, but keep >= 8 stages per split;
-// SMK_BP_SPLITS=n asks for n instead (rounded up to a power of two, at most 64)
-static int bigprod_row_splits(i64 tiles, i64 stages, int num_cus)
-{
-    int S = 1;
-    while (tiles * S < 2 * (i64)num_cus && S < 64 && stages / (2 * S) >= 8) S *= 2;
-    const int want = sw::bp_splits();
-    if (want > 0) { S = 1; while (S < want && S < 64) S *= 2; }
-    return S;
-}
-
-// the H*A' pass of a single-copy (bf16) matrix: same geometry as the stored-transpose pass -- 128 rows of A per tile, 64 columns
-// of A per stage -- on the two kernel shapes that exist for the transposed source (k <= 32: 4 waves, 2-deep ring, two workgroups
-// per CU; k in (32, 64]: 8 compute + 4 loader waves, 3-deep)
+BigProdPlan plan_bigprod(int storage, int k, i64 len, i64 ncols, int nsplit, int num_cus) { return plan_group(storage, k, len, ncols, nsplit, num_cus, false); }
+int plan_bigprod_groups(int storage, int k, i64 len, i64 ncols, int nsplit, int num_cus, BigProdPlan* out) { return plan_groups(storage, k, len, ncols, nsplit, num_cus, false, out); }
 int plan_bigprod_groups_tr(int storage, int k, i64 len, i64 ncols, int nsplit, int num_cus, BigProdPlan* out)
 {
-    int ng = 0;
-    size_t off = 0;
-    const int pstride = kpp_of(k);
-    const bool f32 = storage == STORE_F32;
     // forms the transposed-source kernels exist for (fp32 A: the fp16 two-term form or bf16x3; bf16 A: 1 .. 3 bf16 terms).  Anything
     // else -- the accurate form above all -- must not be re-labelled here: the caller would then hand an fp64 factor to a kernel
     // that reads packed 16-bit fragments (plan_products materialises the stored transpose instead)
-    if (f32 ? (nsplit != NSPLIT_F16X2 && nsplit != 3) : (nsplit < 1 || nsplit > 3)) return -1;
-    for (int k0 = 0; k0 < k; k0 += 64, ++ng) {
-        const int kg = k - k0 < 64 ? k - k0 : 64;
-        BigProdPlan pl;
-        pl.storage = storage;
-        pl.kt = kt_of(kg);
-        pl.k0 = k0; pl.kg = kg; pl.pstride = pstride; pl.pack_offset = off;
-        pl.nsplit = nsplit;
-        pl.tr = 1;
-        if (f32) {
-            // the two-workgroup shape of bigprod_f3_kernel (32-column stages, 2-deep ring); the fold interval follows the
-            // contraction length as in plan_bigprod
-            pl.variant = len >= 65536 ? 125 : len >= 16384 ? 108 : len >= 4096 ? 128 : 129;
-            pl.mb = 32;
-        } else {
-            pl.variant = pl.kt == 2 ? 18 : 6;
-            pl.mb = 64;
-        }
-        pl.nb = 128;
-        pl.len = len;
-        pl.stages = (len + pl.mb - 1) / pl.mb;
-        pl.tiles = (ncols + 127) / 128;
-        pl.ncols_pad = round_up(ncols, COL_PAD);
-        int S = bigprod_row_splits(pl.tiles, pl.stages, num_cus);
-        if (ng > 0) S = out[0].S;
-        pl.S = S;
-        pl.nst = (pl.stages + S - 1) / S;
-        off += packed_bytes(storage, kg, len, nsplit);
-        out[ng] = pl;
-    }
-    for (int g = 0; g < ng; ++g) out[g].p_elems = (size_t)out[0].S * out[0].ncols_pad * pstride;
-    return ng;
-}
-
-BigProdPlan plan_bigprod(int storage, int k, i64 len, i64 ncols, int nsplit, int num_cus)
-{
-    BigProdPlan pl;
-    pl.storage = storage;
-    pl.kt = kt_of(k);
-    pl.k0 = 0; pl.kg = k; pl.pstride = kpp_of(k); pl.pack_offset = 0;
-    // fp32 storage: nsplit 3 selects the bf16x3 emulation (default), 1 the native fp32 MFMA
-    pl.nsplit = storage == STORE_BF16 ? nsplit : (nsplit >= 2 ? nsplit : 1);
-    if (nsplit == NSPLIT_F64) {            // the accurate form: fp64 matrix cores, 64 x 64 tiles
-        pl.nsplit = NSPLIT_F64;
-        pl.variant = 200;
-        pl.mb = 64; pl.nb = 64;
-        pl.stages = (len + 63) / 64;
-        pl.tiles = (ncols + 63) / 64;
-        pl.ncols_pad = round_up(ncols, COL_PAD);
-        int S = 1;
-        while (pl.tiles * S < 4 * (i64)num_cus && S < 64 && pl.stages / (2 * S) >= 4) S *= 2;
-        pl.S = S;
-        pl.nst = (pl.stages + S - 1) / S;
-        pl.len = len;
-        pl.p_elems = (size_t)S * pl.ncols_pad * pl.pstride;
-        return pl;
-    }
-    // measured best on MI355X: bf16 -> 64-row stages, 2-deep ring, 2 workgroups per CU (C3: 5.98 TB/s)
-    int v = (storage == STORE_BF16) ? 6 : 7;
-    // k in (32,64]: 8 compute waves (one k tile each) + 4 loader waves
-    if (pl.kt == 2) v = (storage == STORE_BF16) ? 18 : 21;
-    // fp32 A as bf16 planes: the second-generation kernels (power-bound at ~4.1 TB/s for k = 64)
-    if (storage == STORE_F32 && pl.nsplit >= 2) v = (pl.kt == 2) ? 108 : 115;
-    // fp16 two-term form: the two-workgroup kernel wins or ties at every shape measured (C2, 32768 x 8192 k = 32, both
-    // passes of a C4 shard); the pipelined ones stay selectable (110, 111, 115)
-    // The error of this form is the fp32 accumulation of the 22-bit hi * hi products (one rounding per MFMA), so it falls with
-    // the length of the fp32 chains (stages between two folds into fp64) and, relative to the result, with the number of
-    // folds: the fold interval follows the contraction length so that the product stays at 1e-8 .. 2e-8 of the exact one at
-    // every size (profiles/r04_fold_interval_sweep.txt, max over 512 entries against an fp64 host product: len 1500 9.2e-8
-    // with 8 stages per fold, 1.9e-8 with 1; len 8192 4.4e-8 -> 1.3e-8 with 2; len 65536 1.7e-8 and len 262144 1.0e-8 with 8).
-    // Short contractions are latency-bound, the extra folds cost nothing there; at C4 (len >= 65536) folding every 8 stages
-    // instead of 4 is worth 0 .. 2 %.
-    if (storage == STORE_F32 && pl.nsplit == NSPLIT_F16X2) v = len >= 65536 ? 125 : len >= 16384 ? 108 : len >= 4096 ? 128 : 129;
-    if (const auto env = sw::bp_variant(); env.set) v = env.v;
-    if (const auto env2 = sw::bp_variant_k64(); env2.set && pl.kt == 2) v = env2.v;       // only for k in (32, 64]
-    if (storage == STORE_F32 && pl.nsplit == 2 && v < 100) v = (pl.kt == 2) ? 108 : 115;   // the 2-term forms exist only there
-    if (pl.nsplit != NSPLIT_F16X2 && (v == 128 || v == 129)) v = 108;       // the short-chain variants exist for the fp16 form only
-    if (pl.nsplit == NSPLIT_F16X2 && v != 108 && v != 110 && v != 111 && v != 115 && v != 125 && v != 126 && v != 127 && v != 128 && v != 129) v = 125;
-    if (v >= 100 && storage == STORE_F32 && pl.nsplit >= 2) {
-        auto f3_fits = [&](int vv) {
-            if (vv < 100 || vv >= 100 + kNumF3) return false;
-            const F3Variant& f = kF3Variants[vv - 100];
-            const int stage = 128 * f.mb * 4 + (f.mb / 16) * pack_terms(pl.nsplit) * pl.kt * 1024;
-            const int ti = stage / 1024, nld = f.nwl > 0 ? f.nwl : 4;
-            return ti % nld == 0 && (ti / nld) * (f.nstage - 1) <= 63 && stage * f.nstage <= 160 * 1024;
-        };
-        if (!f3_fits(v)) v = (pl.nsplit == NSPLIT_F16X2) ? 125 : 108;
-        if (!f3_fits(v)) v = 115;
-        if (!f3_fits(v)) v = 110;
-        pl.variant = v;
-        const int MB = kF3Variants[v - 100].mb;
-        pl.mb = MB; pl.nb = 128;
-        pl.stages = (len + MB - 1) / MB;
-        pl.tiles = (ncols + 127) / 128;
-        pl.ncols_pad = round_up(ncols, COL_PAD);
-        const int S = bigprod_row_splits(pl.tiles, pl.stages, num_cus);
-        pl.S = S;
-        pl.nst = (pl.stages + S - 1) / S;
-        pl.p_elems = (size_t)S * pl.ncols_pad * pl.pstride;
-        return pl;
-    }
-    if (v < 0 || v >= kNumVariants) v = 6;
-    // variants that do not fit the 160 KiB LDS for this dtype / k fall back to variant 0
-    auto fits = [&](int vv) {
-        return bp_fits(storage == STORE_BF16 ? 2 : 4, pl.kt, pl.nsplit, kVariants[vv].mb, kVariants[vv].nstage,
-                       kVariants[vv].cw, kVariants[vv].wk, kVariants[vv].nwl);
-    };
-    if (!fits(v)) v = (pl.kt == 2) ? 11 : 0;
-    if (!fits(v) && pl.kt == 2) v = 13;
-    if (!fits(v)) v = 0;
-    if (!fits(v)) v = 7;
-    pl.variant = v;
-    const int MB = kVariants[v].mb;
-    const int NB = 128 * kVariants[v].cw;
-    pl.mb = MB; pl.nb = NB;
-    pl.stages = (len + MB - 1) / MB;
-    pl.tiles = (ncols + NB - 1) / NB;
-    pl.ncols_pad = round_up(ncols, COL_PAD);
-    const int S = bigprod_row_splits(pl.tiles, pl.stages, num_cus);
-    pl.S = S;
-    pl.nst = (pl.stages + S - 1) / S;
-    pl.p_elems = (size_t)S * pl.ncols_pad * pl.pstride;   // doubles
-    return pl;
+    if (storage == STORE_F32 ? (nsplit != NSPLIT_F16X2 && nsplit != 3) : (nsplit < 1 || nsplit > 3)) return -1;
+    return plan_groups(storage, k, len, ncols, nsplit, num_cus, true, out);
 }
 
 template <int EBYTES, int KT, int NSPLIT, int MB, int NSTAGE, int CW, int WK, int NWL, bool TRB = false>
@@ -2036,15 +1839,8 @@ static int launch_bigprod_t(const BigProdPlan& pl, const void* B, i64 ldb, const
         SMK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         once.done();
     }
-    int logS = 0;
-    while ((1 << logS) < pl.S) ++logS;
-    i64 grid;
-    if (pl.S <= 8) {
-        const i64 per = 8 >> logS;                       // tiles per group of 8 blocks
-        grid = (pl.tiles + per - 1) / per * 8;
-    } else {
-        grid = pl.tiles * pl.S;
-    }
+    int logS;
+    i64 grid = bigprod_grid(pl, &logS);
     InvRide ride;
     if (!TRB && pl.inv_ride.G && pl.inv_ride.k > 16 && pl.inv_ride.k <= 64) { ride = pl.inv_ride; grid += 8; }
     kern<<<(unsigned)grid, 64 * C::NW, lds, st>>>((const unsigned char*)B, ldb * EBYTES, (const unsigned char*)Xp, P,
@@ -2053,66 +1849,37 @@ static int launch_bigprod_t(const BigProdPlan& pl, const void* B, i64 ldb, const
     return ride.G ? 1 : 0;                       // 1: the launch carried the Gram inverse
 }
 
-constexpr bool bp_fits(int ebytes, int kt, int nsplit, int mb, int nstage, int cw, int wk, int nwl)
-{
-    if (kt % wk != 0) return false;
-    const int cpc = mb / (16 / ebytes);
-    const int qs = (ebytes == 2 || nsplit == 3) ? mb / 16 : cpc / 2;
-    if (qs < 1) return false;
-    const int stage = 128 * cw * mb * ebytes + qs * nsplit * kt * 1024;
-    const int ti = stage / 1024;
-    const int nw = nwl > 0 ? nwl : 4 * wk;
-    return (ti % nw == 0) && (ti / nw * (nstage - 1) <= 63) && (stage * nstage <= 160 * 1024);
-}
-
-template <int EBYTES, int KT, int NSPLIT, int MB, int NSTAGE, int CW, int WK, int NWL = 0>
+// row I of kVariants (bigprod_plan.h), built where it fits this storage, k and form
+template <int EBYTES, int KT, int NSPLIT, int I>
 static int launch_bigprod_if(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
 {
-    if constexpr (bp_fits(EBYTES, KT, NSPLIT, MB, NSTAGE, CW, WK, NWL))
-        return launch_bigprod_t<EBYTES, KT, NSPLIT, MB, NSTAGE, CW, WK, NWL>(pl, B, ldb, Xp, P, st);
+    constexpr BPRow r = kVariants[I];
+    if constexpr (bp_fits(EBYTES, KT, NSPLIT, r))
+        return launch_bigprod_t<EBYTES, KT, NSPLIT, r.mb, r.nstage, r.cw, r.wk, r.nwl>(pl, B, ldb, Xp, P, st);
     else {
         set_error("bigprod variant does not fit LDS");
         return -100;
     }
 }
 
+// a number outside the table takes row 0's shape
+template <int EBYTES, int KT, int NSPLIT, size_t... I>
+static int launch_bigprod_rows(std::index_sequence<I...>, const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
+{
+    static constexpr LaunchFn row[] = {&launch_bigprod_if<EBYTES, KT, NSPLIT, (int)I>...};
+    return row[pl.variant >= 0 && pl.variant < kNumVariants ? pl.variant : 0](pl, B, ldb, Xp, P, st);
+}
 template <int EBYTES, int KT, int NSPLIT>
 static int launch_bigprod_v(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
 {
-    switch (pl.variant) {
-        case 1: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 4, 1, 1>(pl, B, ldb, Xp, P, st);
-        case 2: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 5, 1, 1>(pl, B, ldb, Xp, P, st);
-        case 3: return launch_bigprod_if<EBYTES, KT, NSPLIT, 128, 2, 1, 1>(pl, B, ldb, Xp, P, st);
-        case 4: return launch_bigprod_if<EBYTES, KT, NSPLIT, 128, 3, 1, 1>(pl, B, ldb, Xp, P, st);
-        case 5: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 3, 2, 1>(pl, B, ldb, Xp, P, st);
-        case 6: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 2, 1, 1>(pl, B, ldb, Xp, P, st);
-        case 7: return launch_bigprod_if<EBYTES, KT, NSPLIT, 32, 2, 1, 1>(pl, B, ldb, Xp, P, st);
-        case 8: return launch_bigprod_if<EBYTES, KT, NSPLIT, 32, 3, 1, 1>(pl, B, ldb, Xp, P, st);
-        case 9: return launch_bigprod_if<EBYTES, KT, NSPLIT, 32, 4, 1, 1>(pl, B, ldb, Xp, P, st);
-        case 10: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 2, 1, 2>(pl, B, ldb, Xp, P, st);
-        case 11: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 3, 1, 2>(pl, B, ldb, Xp, P, st);
-        case 12: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 4, 1, 2>(pl, B, ldb, Xp, P, st);
-        case 13: return launch_bigprod_if<EBYTES, KT, NSPLIT, 32, 4, 1, 2>(pl, B, ldb, Xp, P, st);
-        case 14: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 2, 2, 2>(pl, B, ldb, Xp, P, st);
-        case 15: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 3, 1, 1, 4>(pl, B, ldb, Xp, P, st);
-        case 16: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 4, 1, 1, 4>(pl, B, ldb, Xp, P, st);
-        case 17: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 5, 1, 1, 4>(pl, B, ldb, Xp, P, st);
-        case 18: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 3, 1, 2, 4>(pl, B, ldb, Xp, P, st);
-        case 19: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 4, 1, 2, 4>(pl, B, ldb, Xp, P, st);
-        case 20: return launch_bigprod_if<EBYTES, KT, NSPLIT, 32, 4, 1, 1, 2>(pl, B, ldb, Xp, P, st);
-        case 21: return launch_bigprod_if<EBYTES, KT, NSPLIT, 32, 4, 1, 2, 4>(pl, B, ldb, Xp, P, st);
-        case 22: return launch_bigprod_if<EBYTES, KT, NSPLIT, 32, 5, 1, 2, 4>(pl, B, ldb, Xp, P, st);
-        case 23: return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 2, 1, 1, 4>(pl, B, ldb, Xp, P, st);
-        default: break;
-    }
-    return launch_bigprod_if<EBYTES, KT, NSPLIT, 64, 3, 1, 1>(pl, B, ldb, Xp, P, st);
+    return launch_bigprod_rows<EBYTES, KT, NSPLIT>(std::make_index_sequence<kNumVariants>{}, pl, B, ldb, Xp, P, st);
 }
 
 // transposed source: B = A (bf16), ldb = its column stride
 template <int KT, int NSPLIT, int MB, int NSTAGE, int WK, int NWL>
 static int launch_bigprod_if_tr(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
 {
-    if constexpr (bp_fits(2, KT, NSPLIT, MB, NSTAGE, 1, WK, NWL)) {
+    if constexpr (bp_fits(2, KT, NSPLIT, BPRow{MB, NSTAGE, 1, WK, NWL})) {
         BigProdPlan q = pl;                    // the plan was made for 64-column stages
         q.mb = MB;
         q.stages = (pl.len + MB - 1) / MB;
@@ -2123,32 +1890,41 @@ static int launch_bigprod_if_tr(const BigProdPlan& pl, const void* B, i64 ldb, c
         return -100;
     }
 }
+// row I of kVariants on the transposed source: the plan's own 64-column stages, or the row's
+template <int KT, int NSPLIT, int I>
+static int launch_bigprod_tr_row(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
+{
+    constexpr BPRow r = kVariants[I];
+    static_assert(r.cw == 1, "transposed source: 128-row tiles");
+    if constexpr (r.mb == 64) return launch_bigprod_t<2, KT, NSPLIT, 64, r.nstage, 1, r.wk, r.nwl, true>(pl, B, ldb, Xp, P, st);
+    else return launch_bigprod_if_tr<KT, NSPLIT, r.mb, r.nstage, r.wk, r.nwl>(pl, B, ldb, Xp, P, st);
+}
 template <int KT, int NSPLIT>
 static int launch_bigprod_tr_v(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
 {
-    // the kernel shapes built for the transposed source (numbers = the variants of kVariants; SMK_BP_TR_VARIANT picks one)
+    // the kernel shapes built for the transposed source (numbers up to 23 = the rows of kVariants; SMK_BP_TR_VARIANT picks one)
     const int v = sw::bp_tr_variant();
     if constexpr (KT == 1) {
         switch (v) {
-            case 0: return launch_bigprod_t<2, 1, NSPLIT, 64, 3, 1, 1, 0, true>(pl, B, ldb, Xp, P, st);
-            case 1: return launch_bigprod_t<2, 1, NSPLIT, 64, 4, 1, 1, 0, true>(pl, B, ldb, Xp, P, st);
-            case 15: return launch_bigprod_t<2, 1, NSPLIT, 64, 3, 1, 1, 4, true>(pl, B, ldb, Xp, P, st);
-            case 6: return launch_bigprod_t<2, 1, NSPLIT, 64, 2, 1, 1, 0, true>(pl, B, ldb, Xp, P, st);
-            case 17: return launch_bigprod_t<2, 1, NSPLIT, 64, 5, 1, 1, 4, true>(pl, B, ldb, Xp, P, st);
-            case 23: return launch_bigprod_t<2, 1, NSPLIT, 64, 2, 1, 1, 4, true>(pl, B, ldb, Xp, P, st);
-            case 20: return launch_bigprod_if_tr<1, NSPLIT, 32, 4, 1, 2>(pl, B, ldb, Xp, P, st);
+            case 0: return launch_bigprod_tr_row<1, NSPLIT, 0>(pl, B, ldb, Xp, P, st);
+            case 1: return launch_bigprod_tr_row<1, NSPLIT, 1>(pl, B, ldb, Xp, P, st);
+            case 15: return launch_bigprod_tr_row<1, NSPLIT, 15>(pl, B, ldb, Xp, P, st);
+            case 6: return launch_bigprod_tr_row<1, NSPLIT, 6>(pl, B, ldb, Xp, P, st);
+            case 17: return launch_bigprod_tr_row<1, NSPLIT, 17>(pl, B, ldb, Xp, P, st);
+            case 23: return launch_bigprod_tr_row<1, NSPLIT, 23>(pl, B, ldb, Xp, P, st);
+            case 20: return launch_bigprod_tr_row<1, NSPLIT, 20>(pl, B, ldb, Xp, P, st);
             case 24: return launch_bigprod_if_tr<1, NSPLIT, 32, 5, 1, 2>(pl, B, ldb, Xp, P, st);
             case 25: return launch_bigprod_if_tr<1, NSPLIT, 32, 6, 1, 2>(pl, B, ldb, Xp, P, st);
             case 26: return launch_bigprod_if_tr<1, NSPLIT, 32, 3, 1, 2>(pl, B, ldb, Xp, P, st);
             // 16: four loader waves and a 4-deep ring, one workgroup per CU.  The shape of the stored-transpose pass (6: 2-deep, two
             // workgroups per CU) runs 400 us on C3 against 339; with loader waves 354 - 363 (profiles/r05_single_copy_c3.txt)
-            default: return launch_bigprod_t<2, 1, NSPLIT, 64, 4, 1, 1, 4, true>(pl, B, ldb, Xp, P, st);
+            default: return launch_bigprod_tr_row<1, NSPLIT, 16>(pl, B, ldb, Xp, P, st);
         }
     } else {
         switch (v) {
-            case 11: return launch_bigprod_t<2, 2, NSPLIT, 64, 3, 1, 2, 0, true>(pl, B, ldb, Xp, P, st);
-            case 19: return launch_bigprod_t<2, 2, NSPLIT, 64, 4, 1, 2, 4, true>(pl, B, ldb, Xp, P, st);
-            default: return launch_bigprod_t<2, 2, NSPLIT, 64, 3, 1, 2, 4, true>(pl, B, ldb, Xp, P, st);      // 18
+            case 11: return launch_bigprod_tr_row<2, NSPLIT, 11>(pl, B, ldb, Xp, P, st);
+            case 19: return launch_bigprod_tr_row<2, NSPLIT, 19>(pl, B, ldb, Xp, P, st);
+            default: return launch_bigprod_tr_row<2, NSPLIT, 18>(pl, B, ldb, Xp, P, st);
         }
     }
 }
@@ -2160,27 +1936,26 @@ static int launch_bigprod_tr(const BigProdPlan& pl, const void* B, i64 ldb, cons
     return launch_bigprod_tr_v<KT, 1>(pl, B, ldb, Xp, P, st);
 }
 
-// transposed source, fp32 storage: bigprod_f3_kernel<..., TAIL = 2> in its two-workgroup shape, fold interval by variant
-template <int KT>
-static int launch_f3_tr(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
+// transposed source, fp32 storage: bigprod_f3_kernel<..., TAIL = 2> in its two-workgroup shape
+template <int KT, int FOLD>
+static int launch_f3_tr_fold(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
 {
-    if (pl.nsplit == NSPLIT_F16X2) {
-        if (!pl.oscale) { set_error("bigprod: the fp16 two-term form needs the output scales"); return -100; }
-        switch (pl.variant) {
-            case 125: return launch_f3_t<KT, 2, 32, 2, 0, 8, 2, 1, 2>(pl, B, ldb, Xp, P, st);
-            case 128: return launch_f3_t<KT, 2, 32, 2, 0, 2, 2, 1, 2>(pl, B, ldb, Xp, P, st);
-            case 129: return launch_f3_t<KT, 2, 32, 2, 0, 1, 2, 1, 2>(pl, B, ldb, Xp, P, st);
-            default: return launch_f3_t<KT, 2, 32, 2, 0, 4, 2, 1, 2>(pl, B, ldb, Xp, P, st);
-        }
-    }
+    if (pl.nsplit == NSPLIT_F16X2) return launch_f3_t<KT, 2, 32, 2, 0, FOLD, 2, 1, 2>(pl, B, ldb, Xp, P, st);
     // bf16x3: a stage is 16 KB of A + 6 KB (k <= 32) or 12 KB of operand fragments; 22 pieces do not split over four loading
     // waves, so k <= 32 takes the shape with two loader waves (variant 104's), k in (32, 64] the plain one
     constexpr int NWL = KT == 1 ? 2 : 0, WPS = KT == 1 ? 3 : 2;
-    switch (pl.variant) {
-        case 125: return launch_f3_t<KT, 3, 32, 2, NWL, 8, WPS, 0, 2>(pl, B, ldb, Xp, P, st);
-        case 128: return launch_f3_t<KT, 3, 32, 2, NWL, 2, WPS, 0, 2>(pl, B, ldb, Xp, P, st);
-        case 129: return launch_f3_t<KT, 3, 32, 2, NWL, 1, WPS, 0, 2>(pl, B, ldb, Xp, P, st);
-        default: return launch_f3_t<KT, 3, 32, 2, NWL, 4, WPS, 0, 2>(pl, B, ldb, Xp, P, st);
+    return launch_f3_t<KT, 3, 32, 2, NWL, FOLD, WPS, 0, 2>(pl, B, ldb, Xp, P, st);
+}
+// ... with the fold interval of the plan's variant: 8, 2 or 1 stages, else 4
+template <int KT>
+static int launch_f3_tr(const BigProdPlan& pl, const void* B, i64 ldb, const void* Xp, double* P, hipStream_t st)
+{
+    if (pl.nsplit == NSPLIT_F16X2 && !pl.oscale) { set_error("bigprod: the fp16 two-term form needs the output scales"); return -100; }
+    switch (is_f3_variant(pl.variant) ? kF3Variants[pl.variant - 100].fold : 4) {
+        case 8: return launch_f3_tr_fold<KT, 8>(pl, B, ldb, Xp, P, st);
+        case 2: return launch_f3_tr_fold<KT, 2>(pl, B, ldb, Xp, P, st);
+        case 1: return launch_f3_tr_fold<KT, 1>(pl, B, ldb, Xp, P, st);
+        default: return launch_f3_tr_fold<KT, 4>(pl, B, ldb, Xp, P, st);
     }
 }
 

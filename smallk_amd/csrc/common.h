@@ -7,6 +7,7 @@
 #include <functional>
 #include <cstddef>
 #include <string>
+#include "bigprod_plan.h"
 
 struct smk_matrix;
 
@@ -14,9 +15,7 @@ namespace smk {
 
 typedef int64_t i64;
 
-// Device storage of the big matrix A (and its transpose).
-enum Storage { STORE_F32 = 0, STORE_BF16 = 1 };
-
+// (Storage, the product forms NSPLIT_* and kt_of: bigprod_plan.h)
 inline int elem_size(int storage) { return storage == STORE_BF16 ? 2 : 4; }
 
 // Row padding of every stored big matrix (zero filled): lets the streaming
@@ -38,7 +37,6 @@ inline bool is_wide(int k) { return k > 128; }
 // block pivoting takes the tile kernels of wide.hip (and their scratch layout) from this rank on: everything above 128, and
 // k in (64, 128] unless SMK_NNLS_TILE128=0 asks for nnls_bpp_inv128_kernel
 bool nnls_uses_tiles(int k);
-// number of 32-wide k tiles of the streaming product
 // devmem.cpp: hipMalloc / hipFree with a per-device cache of freed blocks (solver, subset and sort workspaces come and go per
 // node of a clustering run); dev_trim returns the current device's cached blocks to the runtime
 hipError_t dev_malloc(void** p, size_t bytes);
@@ -46,7 +44,6 @@ template <typename T> inline hipError_t dev_malloc(T** p, size_t bytes) { return
 hipError_t dev_free(void* p);
 void dev_trim();
 void dev_cache_stats(unsigned long long* hits, unsigned long long* misses, size_t* cached_bytes);
-inline int kt_of(int k) { return (k + 31) / 32; }
 // "do this once" for things that are per DEVICE (hipFuncSetAttribute applies to the function on the current device): one
 // process may drive several devices (smk_nmf_dense_sharded, bench.py --single-process, HierNMF2 with SMK_CLUST_DEVICES), and a
 // process-wide flag would opt the kernel in on the first device only.  Usage:
@@ -141,12 +138,7 @@ int launch_csc_convert(const void* offsets, int idx_type, i64 width, i64 nnz, co
                        hipStream_t st);
 
 // packed MFMA operand of X (k x N): bytes needed
-// nsplit: 1..3 = bf16 terms of the skinny operand; NSPLIT_F16X2 = two fp16 terms with per-row power-of-two scales
-constexpr int NSPLIT_F16X2 = 4;
-// the accurate form: A's entries (exact in fp64) times the fp64 factor itself on the fp64 matrix cores (v_mfma_f64_16x16x4),
-// fp64 accumulation throughout -- no packed operand; Xp of launch_bigprod is then the factor (KP doubles per column, rows
-// from the plan's k0 on)
-constexpr int NSPLIT_F64 = 8;
+// nsplit: the product form (bigprod_plan.h)
 size_t packed_bytes(int storage, int k, i64 N, int nsplit);
 size_t packed_row_offset(int storage, int kg, int nsplit, i64 r0);
 // a row-sharded factor: X holds this rank's `nblocks` blocks of `blk` rows back to back (N valid rows, the rest packs as

@@ -181,53 +181,15 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
     s->n = a->n;
     s->st = a->st ? a->st : ctx().stream;
     const sw::Maybe<int> env = sw::nsplit();
-    // fp32 A: the fp16 two-term form (3 MFMAs per product, 2^-22 operand error) unless SMK_NSPLIT picks the bf16 forms
-    // (3 = bf16x3, 6 MFMAs, power-bound; 2 = two bf16 terms, 2^-16); bf16 A: three bf16 terms of the factor
-    // HALS amplifies the product error several thousand times (its W update is a difference of nearly equal terms per
-    // column, more so at high rank): the 24-bit bf16x3 operands stay inside the parity bar where the 22-bit fp16 ones
-    // do not always (tools/fuzz_parity.py: k = 117 .. 253 1e-4 .. 5e-4 against < 1e-4, one k = 62 case at 1.1e-4 after
-    // 17 iterations), so HALS keeps bf16x3; MU and BPP take the fp16 form
-    // The amplification grows with the rank for every algorithm (BPP k = 191 after 34 iterations: 1.26e-4 with the
-    // fp16 form), so above k = 64 the 24-bit operands are kept as well; C2 (k = 16) and C4 (k = 64) take the fp16 form.
-    const bool hals = opts->algorithm == SMK_ALG_HALS;
-    // HALS above k = 64: the 1e-8-class products of the 16-bit forms, amplified ~2x per five iterations at these ranks, leave
-    // the 1e-4 parity bar in runs of 30+ iterations (1.4e-4 .. 1.6e-4 at k = 100 .. 150 after 30) -- with either 16-bit form
-    // and with bf16 A alike, so it is the accumulation, not the operands.  Those runs take the ACCURATE form (NSPLIT_F64:
-    // the stored A against the fp64 factor on the fp64 matrix cores), ~3x the product time.  SMK_NSPLIT=8 selects it anywhere.
-    int nsplit_default = (a->storage == SMK_STORE_F32 && !hals && opts->k <= 64) ? NSPLIT_F16X2 : 3;
-    if (hals && opts->k > 64 && !a->sparse) nsplit_default = NSPLIT_F64;
-    // Block pivoting above k = 64 as well: the Gram matrix of a uniform start has condition ~3k, so 1e-8-class products are
-    // 2e-6 in the factors after ONE iteration at k = 100, and on data with sparse planted factors that grows ~1.3x per iteration
-    // (tools/wide_long_run.py: 1200 x 1000, k = 100, bf16x3: 1.2e-4 after 20 iterations, 1.1e-3 after 30; k = 160: 4e-5 after 25;
-    // the accurate form: 8.5e-12 after 30).  At k <= 64 the same data stays below 2e-5 over 30 iterations with the fp16 form.
-    if (opts->algorithm == SMK_ALG_BPP && opts->k > 64 && !a->sparse) nsplit_default = NSPLIT_F64;
-    // ... and at k in (32, 64] where the accurate form costs nothing measurable (A of at most 2^24 entries: the streaming pass
-    // is a 10 - 30 us launch next to a 100 us NNLS).  Block pivoting at these ranks amplifies the product error ~3000 x while
-    // the passive sets are still moving: on data with sparse planted factors (1500 x 1100, k = 64) the distance to the oracle's
-    // trajectory peaks at 0.4e-4 .. 2e-4 around iteration 100 with the fp16 form whatever its fold interval (3e-8 .. 9e-8
-    // products), 5e-6 with bf16x3, 2e-12 with the accurate form, and contracts to 4e-7 by iteration 500
-    // (profiles/r04_long_runs_500_iterations.txt).  Larger matrices keep the fp16 form (C4: 3 x the pass time otherwise);
-    // SMK_NSPLIT=8 / 3 select the other forms anywhere.
-    // (SMK_BPP_SMALL_ACCURATE=0 keeps the fp16 form: the test suite sets it, its small cases stand in for C4's path.)
-    const bool small_accurate = sw::bpp_small_accurate();           // read per solver, like SMK_NSPLIT
-    if (small_accurate && opts->algorithm == SMK_ALG_BPP && opts->k > 32 && !a->sparse && a->m * a->n_global <= ((i64)1 << 24))
-        nsplit_default = NSPLIT_F64;
-    // Dense RANK2 (every node factorisation of HierNMF2 / flatclust on dense A runs 100 .. 1000 iterations to a tight
-    // tolerance): the accurate form costs nothing at two factor rows -- bigprod_f64_k2_kernel does its 2 fp64 multiply-adds
-    // per stored entry on the vector ALUs at the streaming rate -- and leaves only summation order between this path and
-    // the reference's fp64 arithmetic (common/src/nmf.cpp:33).
-    if (opts->algorithm == SMK_ALG_RANK2 && !a->sparse) nsplit_default = NSPLIT_F64;
-    // Column scales of A more than 2^28 apart: the small columns fall below what fp32-class products resolve next to the
-    // large ones (HALS / BPP leave the bar at 2^+-20, tests/test_gpu_parity.py) -- the accurate form as well.
-    if (!env.set && !a->sparse && opts->algorithm != SMK_ALG_RANK2) {
-        if (a->col_spread_log2 < 0) { const int rc0 = matrix_measure_scale(a, a->st ? a->st : ctx().stream); if (rc0) { --ctx().live_solvers; delete s; return rc0; } }
-        if (a->col_spread_log2 > 28) nsplit_default = NSPLIT_F64;
+    static_assert(ALG_MU == SMK_ALG_MU && ALG_HALS == SMK_ALG_HALS && ALG_RANK2 == SMK_ALG_RANK2 && ALG_BPP == SMK_ALG_BPP, "bigprod_plan.h");
+    // the product form (bigprod_plan.h: default_product_form).  Its last rule needs the spread of A's column scales, measured once
+    // per matrix where the rule can apply
+    if (!env.set && !a->sparse && opts->algorithm != SMK_ALG_RANK2 && a->col_spread_log2 < 0) {
+        const int rc0 = matrix_measure_scale(a, a->st ? a->st : ctx().stream);
+        if (rc0) { --ctx().live_solvers; delete s; return rc0; }
     }
-    s->nsplit = env.set ? env.v : nsplit_default;
-    if (s->nsplit != NSPLIT_F64 && (s->nsplit < 1 || s->nsplit > NSPLIT_F16X2)) s->nsplit = nsplit_default;
-    if (s->nsplit == NSPLIT_F64 && a->sparse) s->nsplit = 3;      // sparse A: gather products in fp64 already
-    // the fp16 two-term form applies to fp32 storage; RANK2 keeps its Gram matrices inside its own solve kernel
-    if (s->nsplit == NSPLIT_F16X2 && (a->storage != SMK_STORE_F32 || a->sparse || opts->algorithm == SMK_ALG_RANK2)) s->nsplit = 3;
+    s->nsplit = resolve_product_form(opts->algorithm, opts->k, a->storage, a->sparse, a->m * a->n_global, a->col_spread_log2,
+                                     sw::bpp_small_accurate() /* read per solver, like SMK_NSPLIT */, {env.set, env.v});
     // (a single-copy matrix outside what the transposed-source kernels cover gets its stored transpose inside plan_products)
     int rc = plan_products(s);
     if (rc) { smk_solver_destroy(s); return rc; }
@@ -884,6 +846,15 @@ static int timed_bigprod(smk_solver* s, int which, const BigProdPlan& pl_in, con
     return rc;
 }
 
+// the routes of a gather product with a factor of ldx doubles per column (timed_spmm takes them, smk_solver_kernel_name names them):
+// the rank-2 product by row blocks, else the entry-balanced segments, else the column-per-lane-group kernel
+static bool blocked2_route(const smk_solver* s, int which, int ldx) { return ldx == 2 && (which == 0 ? s->a->bA : s->a->bAt).nb > 1; }
+static bool seg_route(const smk_solver* s, int which, int ldx, i64 ncols)
+{
+    const SegPlan& seg = (which == 0) ? s->a->segA : s->a->segAt;
+    return ldx == s->KP && s->k > 2 && !is_wide(s->k) && seg.ncols == ncols && seg.rowflag && !seg.uniform;
+}
+
 // R1 = W'A  (k x n, local columns)
 static int timed_spmm(smk_solver* s, int which, const i64* colptr, const unsigned* rowidx, const double* val, i64 ncols,
                       const double* X, int ldx, double* P)
@@ -901,17 +872,17 @@ static int timed_spmm(smk_solver* s, int which, const i64* colptr, const unsigne
     if (s->inv_ride[which]) { ride.G = which == 0 ? s->Gw : s->Gh; ride.k = s->k; ride.Ginv = inv_scratch(s, which); }
     s->inv_ride[which] = false;
     GramRide gram;                                                  // gram_factor: this factor's Gram matrix is due
-    const bool seg_route = ldx == s->KP && s->k > 2 && !is_wide(s->k) && seg.ncols == ncols && seg.rowflag && !seg.uniform;
+    const bool by_seg = seg_route(s, which, ldx, ncols);
     if (s->gram_ride[which]) {
         s->gram_ride[which] = false;
         const double* F = which == 0 ? s->Wt : s->H;
         const i64 FN = which == 0 ? s->m : s->n;
         double* G = which == 0 ? s->Gw : s->Gh;
-        if (seg_route) { gram.X = F; gram.N = FN; gram.max_blocks = GRAM_BLOCKS; gram.Gp = s->gram_scratch; gram.G = G; }
+        if (by_seg) { gram.X = F; gram.N = FN; gram.max_blocks = GRAM_BLOCKS; gram.Gp = s->gram_scratch; gram.G = G; }
         else { const int grc = launch_gram(F, s->k, FN, G, s->gram_scratch, GRAM_BLOCKS, s->st); if (grc) return grc; }
     }
-    if (ldx == 2 && blk.nb > 1) rc = launch_spmm_blocked2(blk, X, P, which == 0 ? s->pl1.ncols_pad : s->pl2.ncols_pad, s->st);
-    else if (seg_route) {
+    if (blocked2_route(s, which, ldx)) rc = launch_spmm_blocked2(blk, X, P, which == 0 ? s->pl1.ncols_pad : s->pl2.ncols_pad, s->st);
+    else if (by_seg) {
         // the partial sums of long columns live in the SOLVER (two solvers on one sparse matrix run on their own streams)
         if (seg.npieces > 0 && !s->seg_pieces[which] && s->own.dev(&s->seg_pieces[which], (size_t)seg.npieces * 128)) {
             set_error("no memory for the long-column partial sums");
@@ -2471,13 +2442,10 @@ int smk_solver_kernel_name(const smk_solver* s, int which, char* out, int cap)
             if (s->check_routes[r]) name += (name.empty() ? "" : "; ") + std::to_string(s->check_routes[r]) + " x " + route[r];
         if (name.empty()) name = "none formed yet";
     } else if (s->a->sparse) {
-        const BlockedCsc& blk = (which == 0) ? s->a->bA : s->a->bAt;
-        const SegPlan& seg = (which == 0) ? s->a->segA : s->a->segAt;
-        const i64 ncols = which == 0 ? s->n : s->m;
         const int ldx = s->Wc ? 2 : s->KP;
         if (s->r2p_sync && s->o.algorithm == SMK_ALG_RANK2) name = "smk::rank2_persist_kernel";
-        else if (ldx == 2 && blk.nb > 1) name = "smk::spmm_blocked2_kernel";
-        else if (ldx == s->KP && s->k > 2 && !is_wide(s->k) && seg.ncols == ncols && seg.rowflag && !seg.uniform) name = "smk::spmm_seg_kernel";
+        else if (blocked2_route(s, which, ldx)) name = "smk::spmm_blocked2_kernel";
+        else if (seg_route(s, which, ldx, which == 0 ? s->n : s->m)) name = "smk::spmm_seg_kernel";
         else name = "smk::spmm_gather_kernel";
     } else {
         const BigProdPlan& pl = which == 0 ? s->pl1 : s->pl2;

@@ -23,7 +23,7 @@ import make_golden as mg  # noqa: E402
 EPS = 1e-13
 EXACT_RTOL = 1e-14          # Tier A: three roundings of the device update + the host inversion, ten times over (<= 9e-16)
 
-# ---- the planner, restated (smallk_amd/csrc/bigprod.hip: kVariants, kF3Variants, bp_fits, plan_bigprod, plan_bigprod_groups_tr) ----
+# ---- the planner, restated (smallk_amd/csrc/bigprod_plan.h: kVariants, kF3Variants, bp_fits, f3_fits, choose_variant) ----
 # (rows per stage, ring depth, 128-column tiles per workgroup, k-tile waves, loader waves)
 KVARIANTS = [(64, 3, 1, 1, 0), (64, 4, 1, 1, 0), (64, 5, 1, 1, 0), (128, 2, 1, 1, 0), (128, 3, 1, 1, 0), (64, 3, 2, 1, 0),
              (64, 2, 1, 1, 0), (32, 2, 1, 1, 0), (32, 3, 1, 1, 0), (32, 4, 1, 1, 0), (64, 2, 1, 2, 0), (64, 3, 1, 2, 0),
