@@ -12,7 +12,8 @@
 //   Gw = W'W, Gh = HH' : KP x KP (KP = 8/16/32/64 padded)
 //   P1 : S1 slabs of n_pad x kpp fp64 = W'A partials,   P2 : S2 slabs of m_pad x kpp = (AH')' partials
 //   packW / packH : MFMA operand fragments of W' / H
-#include "state.h"
+#include "solver_internal.h"
+#include "check_ring.h"
 #include "comm.h"
 #include "switches.h"
 
@@ -21,29 +22,15 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
-#include <deque>
 #include <algorithm>
 #include <thread>
 
 extern "C" {
 
-static PartialView view1(const smk_solver* s)
-{
-    return PartialView{s->P1, s->pl1.S, (i64)s->pl1.ncols_pad * s->kpp, s->kpp, 1};
-}
-static inline bool is_dist(const smk_solver* s) { return s->ar != nullptr || s->comm != nullptr; }
 // BPP with a native communicator: every rank solves only its own blocks of W, so it needs only those rows of the summed
 // (AH')' -- a reduce-scatter instead of an all-reduce (half the bytes on the wire) -- and the other ranks receive the
 // packed streaming operand of those rows (4 B per entry in the fp16 form) instead of the fp64 values
 static inline bool w_rows_sharded(const smk_solver* s) { return s->w_sharded; }
-
-static PartialView view2(const smk_solver* s)
-{
-    if (is_dist(s)) return PartialView{s->R2red, 1, 0, s->kpp, s->red_f64 ? 1 : 0};
-    return PartialView{s->P2, s->pl2.S, (i64)s->pl2.ncols_pad * s->kpp, s->kpp, 1};
-}
-
-static PartialView view_own(const smk_solver* s) { return PartialView{s->R2own, 1, 0, s->kpp, s->red_f64 ? 1 : 0}; }
 
 // rows [r0, r1) of chunk j (clipped to the padded row count of the H*At pass) and this rank's block [a, b) of it
 // (valid rows only: b <= m; empty when b <= a)
@@ -334,8 +321,6 @@ int smk_solver_set_comm(smk_solver* s, int rank, int world, smk_allreduce_fn fn,
     return SMK_OK;
 }
 
-static int progress_prealloc(smk_solver* s);
-
 // Native path: every collective is issued from C on the solver's second stream (RCCL over xGMI, or the in-process
 // stand-in).  Call before set_factors().  The communicator must outlive the solver.
 int smk_solver_attach_comm(smk_solver* s, smk_comm* comm)
@@ -486,8 +471,7 @@ static int factors_end(smk_solver* s)
     s->inited = false;
     s->normalized = false;
     s->iter = 0;
-    s->pg0 = 1.0;
-    s->last_metric = 1.0;
+    s->pc.reset_estimator();
     return SMK_OK;
 }
 
@@ -670,7 +654,8 @@ static int wait_gh(smk_solver* s)
     return 0;
 }
 // the main stream joins the chunk exchanges of the last H*At pass (every consumer of the summed (AH')' calls this)
-static int wait_r2(smk_solver* s)
+// (extern "C++": progress.cpp calls it too, solver_internal.h -- as gather_w, sync_and_check and dist_agree below)
+extern "C++" int smk::wait_r2(smk_solver* s)
 {
     if (!s->r2_pending) return 0;
     // (the chunk exchanges were recorded on ONE in-order stream: the last event covers the others -- one barrier packet on the
@@ -718,29 +703,7 @@ static int start_inverse(smk_solver* s, int side, const double* G, hipEvent_t af
     s->inv_pending[side] = true;
     return 0;
 }
-// The checked iteration loop on latency-bound BPP problems (C2: 73 us per iteration, 16 us per check): the stopping rule's gradient
-// of iteration i is gradH_i = W_i'W_i H_i - W_i'A (gradW is the W-side NNLS's dual: projected-gradient sum exactly 0) -- and those
-// three operands are precisely the system matrix, the warm start and the right-hand side of iteration i + 1's H-side NNLS launch.
-// So that launch forms the sum on its way in (NnlsRiders::pg_part), both NNLS launches of an iteration store their result a second
-// time into the snapshot slot (NnlsRiders::snap_x), and a check costs ONE small launch (the totals, written into the pinned slot)
-// instead of a gradient pass over 16 slabs of W'A, a snapshot copy and a sum.  The driver already evaluates the rule one iteration
-// late; when no further iteration follows, progress_end forms the check the old way.  SMK_PROGRESS_DEFER=0: off.
 static bool guard_applies(const smk_solver* s);
-static bool check_rides_in_nnls(const smk_solver* s)
-{
-    if (!sw::progress_defer() || !sw::progress_fused() || sw::bpp_gradw() || sw::guard_every() > 0) return false;
-    if (s->o.algorithm != SMK_ALG_BPP || s->KP > 16 || s->o.prog_est_algorithm != SMK_PROG_PG_RATIO) return false;
-    if (is_dist(s) || s->comm || s->w_sharded) return false;
-    const i64 gpb = 256 / s->KP;
-    return (s->n + gpb - 1) / gpb <= (i64)s->pg_half;          // one partial per workgroup of the H-side launch
-}
-
-// the snapshot (W, H, W'W) of progress slot b, allocated when a check first needs it
-static inline int ensure_snapshot(smk_solver* s, int b)
-{
-    return s->snap[b] ? 0 : s->own.dev(&s->snap[b], snapshot_elems(s->k, s->m, s->n));
-}
-
 static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, PartialView R, const double* G)
 {
     if (s->inv_pending[side]) {
@@ -780,12 +743,13 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
     NnlsRiders rd;
     bool riders = false;
     const int k2 = (s->k + 1) / 2 * 2;
-    if (c0 == 0 && c1 == N && (X == s->H || X == s->Wt) && (s->pg_defer_slot >= 0 || s->iter_snap_slot >= 0) && check_rides_in_nnls(s)) {
-        if (side == 0 && s->pg_defer_slot >= 0) { rd.pg_part = s->pg_partials + s->pg_half; rd.pg_nblk = &s->pg_defer_nblk; riders = true; }
-        if (s->iter_snap_slot >= 0) {
-            const int b = s->iter_snap_slot;
+    ProgressCheck& pc = s->pc;
+    if (c0 == 0 && c1 == N && (X == s->H || X == s->Wt) && (pc.pg_defer_slot >= 0 || pc.iter_snap_slot >= 0) && check_rides_in_nnls(s)) {
+        if (side == 0 && pc.pg_defer_slot >= 0) { rd.pg_part = s->pg_partials + s->pg_half; rd.pg_nblk = &pc.pg_defer_nblk; riders = true; }
+        if (pc.iter_snap_slot >= 0) {
+            const int b = pc.iter_snap_slot;
             const int arc = ensure_snapshot(s, b); if (arc) return arc;
-            rd.snap_x = s->snap[b] + (side == 0 ? (size_t)s->m * k2 : 0);        // snapshot_kernel's layout: [W'][H][W'W]
+            rd.snap_x = pc.snap[b] + (side == 0 ? (size_t)s->m * k2 : 0);        // snapshot_kernel's layout: [W'][H][W'W]
             rd.k2 = k2;
             riders = true;
         }
@@ -796,9 +760,9 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
     if (!rc && rd.pg_part) {
         // the totals of the deferred check are due: they ride in the tail of the pass that follows (prod2), or go out as a launch
         // of their own right in front of it (check_totals)
-        if (s->pg_defer_nblk <= 0) { set_error("the deferred progress check was not carried by the NNLS launch"); return SMK_FAILURE; }
-        s->pg_totals_slot = s->pg_defer_slot;
-        s->pg_defer_slot = -1;
+        if (pc.pg_defer_nblk <= 0) { set_error("the deferred progress check was not carried by the NNLS launch"); return SMK_FAILURE; }
+        pc.pg_totals_slot = pc.pg_defer_slot;
+        pc.pg_defer_slot = -1;
     }
     if (!rc && (X == s->H || X == s->Wt)) {
         s->from_nnls[fx] = c0 == 0 && c1 == N;
@@ -973,44 +937,6 @@ static inline void take_tail(smk_solver* s, int side, BigProdPlan* pl)
     s->tail_nblk[side] = 0;
 }
 
-// The totals of a deferred progress check (nnls_side left the per-workgroup sums): W'W of the checked iteration is still in place
-// until the W-side solve of this iteration has run, so they may be formed anywhere in front of it.  pl != nullptr and the pass
-// carries a tail already: one more tail workgroup forms them (the caller records the slot's event behind the pass: returns 1);
-// otherwise a launch of their own, now.  SMK_PROGRESS_TAIL=0: always the launch.
-// The result of a check is awaited by polling its pinned slot (the kernel that writes the totals stores a tag behind them, system
-// scope) instead of an event: an event record between two launches of a 70 us iteration costs 3 - 4 us of idle stream (C2 checked:
-// 12 650 -> 13 350 it/s).  SMK_PROGRESS_POLL=0: the event.
-static bool progress_polls()
-{
-    return sw::progress_poll();
-}
-
-static int check_totals(smk_solver* s, BigProdPlan* pl)
-{
-    if (s->pg_totals_slot < 0) return 0;
-    const bool ride = sw::progress_tail();
-    const bool poll = progress_polls();
-    const int b = s->pg_totals_slot, k2 = (s->k + 1) / 2 * 2;
-    double* snap_g = s->pg_defer_snap ? s->snap[b] + (size_t)(s->m + s->n) * k2 : nullptr;
-    const double* part = s->pg_partials + s->pg_half;
-    const double tag = poll ? (double)(s->pg_defer_tag + 2) : 0.0;
-    s->poll_tag[b] = tag;
-    if (ride && pl && pl->tail_nblk > 0) {
-        BigProdPlan::TailCheck& tc = pl->tail_check;
-        tc.part = part;  tc.n = s->pg_defer_nblk;  tc.flag_slot = 5;  tc.tag_limit = s->pg_defer_tag;  tc.kk = s->KP * s->KP;
-        tc.out = s->scal;  tc.host_out = s->pin[b].h;  tc.flag = s->fail_flag;  tc.G = s->Gw;  tc.snap_g = snap_g;  tc.tag = tag;
-        ++s->check_routes[3];
-        return 1;
-    }
-    s->pg_totals_slot = -1;
-    ++s->check_routes[2];
-    const int rc = launch_pg_defer_sum(part, s->pg_defer_nblk, s->scal, s->pin[b].h, s->fail_flag, 5, s->pg_defer_tag, s->Gw, snap_g,
-                                       s->KP * s->KP, s->st, tag);
-    if (rc) return rc;
-    if (tag == 0.0) SMK_HIP(hipEventRecord(s->pev[b], s->st));
-    return 0;
-}
-
 static int prod1(smk_solver* s)
 {
     if (s->w_sharded) return prod1_sharded(s);
@@ -1045,7 +971,7 @@ static int prod2(smk_solver* s)
     begin_pass(s, 1);
     int rc = 0;
     const PartialView pv{s->P2, s->pl2.S, (i64)s->pl2.ncols_pad * s->kpp, s->kpp, 1};
-    if (s->pg_totals_slot >= 0 && (s->a->sparse || s->comm || s->ng != 1 || s->tail_nblk[1] <= 0)) {
+    if (s->pc.pg_totals_slot >= 0 && (s->a->sparse || s->comm || s->ng != 1 || s->tail_nblk[1] <= 0)) {
         rc = check_totals(s, nullptr);                  // no tail to ride in
         if (rc) return rc;
     }
@@ -1080,8 +1006,8 @@ static int prod2(smk_solver* s)
             rc = pl.tr ? timed_bigprod(s, 1, pl, s->a->A, s->a->ldA, xh(s->pg2[g]), s->P2 + s->pg2[g].k0)
                        : timed_bigprod(s, 1, pl, s->a->At, s->a->ldAt, xh(s->pg2[g]), s->P2 + s->pg2[g].k0);
             if (ride == 1 && !rc) {
-                if (s->poll_tag[s->pg_totals_slot] == 0.0) SMK_HIP(hipEventRecord(s->pev[s->pg_totals_slot], s->st));
-                s->pg_totals_slot = -1;
+                if (s->pc.poll_tag[s->pc.pg_totals_slot] == 0.0) SMK_HIP(hipEventRecord(s->pc.pev[s->pc.pg_totals_slot], s->st));
+                s->pc.pg_totals_slot = -1;
             }
         }
         if (rc) return rc;
@@ -1212,7 +1138,7 @@ static int gram_h(smk_solver* s)
 }
 
 // row-sharded W: bring every row of the fp64 W to every rank (results, DELTA_FNORM); one in-place all-gather per chunk
-static int gather_w(smk_solver* s)
+extern "C++" int smk::gather_w(smk_solver* s)
 {
     if (!s->w_sharded || s->w_full) return 0;
     int rc = comm_fork(s, s->ev_x);
@@ -1232,7 +1158,7 @@ static int solver_init(smk_solver* s)
     s->from_nnls[0] = s->from_nnls[1] = false;
     s->nnls_packed[0] = s->nnls_packed[1] = false;
     s->tail_nblk[0] = s->tail_nblk[1] = 0;
-    s->pg_defer_slot = s->iter_snap_slot = s->pg_totals_slot = -1;
+    s->pc.reset();
     if (s->o.algorithm == SMK_ALG_HALS) {
         rc = gram_h(s);  if (rc) return rc;
         rc = prod2(s);   if (rc) return rc;
@@ -1367,7 +1293,7 @@ static int resolve_events(smk_solver* s)
 }
 
 // wait for the stream; translate device-side failure flags into Result codes
-static int sync_and_check(smk_solver* s, int* fail_iter)
+extern "C++" int smk::sync_and_check(smk_solver* s, int* fail_iter)
 {
     int flag = INT_MAX;
     int rc = wait_r2(s);                 // chunk exchanges still on the second stream
@@ -1383,7 +1309,7 @@ static int sync_and_check(smk_solver* s, int* fail_iter)
 
 // sharded: sum the H-side scalar over the ranks and make the failure flag the same everywhere, so that every
 // rank takes the same branch of the driver loop (a rank that stopped alone would strand the others in a collective)
-static int dist_agree(smk_solver* s)
+extern "C++" int smk::dist_agree(smk_solver* s)
 {
     const int wpart = w_rows_sharded(s) ? 1 : 0;      // the W-side sum covers this rank's rows only
     int rc = launch_dist_scalars(s->scal, s->fail_flag, s->iter > 0 ? s->iter - 1 : 0, 0, wpart, s->st);
@@ -1391,225 +1317,6 @@ static int dist_agree(smk_solver* s)
     rc = dist_allreduce_now(s, s->scal + 5, 3, 1);
     if (rc) return rc;
     return launch_dist_scalars(s->scal, s->fail_flag, s->iter > 0 ? s->iter - 1 : 0, 1, wpart, s->st);
-}
-
-// progress_est->Update(iter, W, H, gradW, gradH): returns the metric (synchronises)
-// the kernels (and, sharded, the scalar all-reduce) of one progress evaluation; results land in s->scal
-static int enqueue_progress_kernels(smk_solver* s)
-{
-    int rc = wait_r2(s);
-    if (rc) return rc;
-    if (s->o.prog_est_algorithm == SMK_PROG_DELTA_FNORM) {
-        rc = gather_w(s);             // a row-sharded W: the norm runs over all of it (BPP's default rule is PG_RATIO)
-        if (rc) return rc;
-        rc = launch_delta_fnorm(s->Wt, s->Wprev, (i64)s->KP * s->m, s->pg_partials, s->scal + 2, s->st);
-        if (rc) return rc;
-    } else {
-        // gradW = W*HHt - AHt  (slot 0, replicated), gradH = WtW*H - WtA (slot 1, local shard)
-        if (w_rows_sharded(s)) {      // only this rank's rows of the summed (AH')' exist here: partial sum, joined in dist_agree
-            rc = s->n_own > 0 ? launch_grad_pg(s->Wown, s->k, s->n_own, view_own(s), s->Gh, nullptr, s->pg_partials, s->scal, 0, s->st, s->wide_tmp)
-                              : launch_zero_f64(s->scal, 1, s->st);
-        } else {
-            rc = launch_grad_pg(s->Wt, s->k, s->m, view2(s), s->Gh, nullptr, s->pg_partials, s->scal, 0, s->st, s->wide_tmp);
-        }
-        if (rc) return rc;
-        rc = launch_grad_pg(s->H, s->k, s->n, view1(s), s->Gw, nullptr, s->pg_partials + s->pg_half, s->scal, 1, s->st, s->wide_tmp);
-        if (rc) return rc;
-    }
-    if (is_dist(s)) { rc = dist_agree(s); if (rc) return rc; }
-    return 0;
-}
-
-// metric from the four scalars (PG sums for W and H, delta-Fnorm numerator / denominator)
-static int evaluate_progress(smk_solver* s, const double* h, int iter_index, double* metric)
-{
-    if (s->o.prog_est_algorithm == SMK_PROG_DELTA_FNORM) {
-        *metric = std::sqrt(h[2]) / std::sqrt(h[3]);
-    } else {
-        const double pg = std::sqrt(h[0] + h[1]);
-        if (std::isnan(pg)) { set_error("ProjectedGradientNorm: NaN"); return SMK_FAILURE; }   // reference throws
-        if (iter_index == 0) { s->pg0 = pg; *metric = 1.0; }
-        else *metric = pg / s->pg0;
-    }
-    s->last_metric = *metric;
-    return SMK_OK;
-}
-
-// progress_est->Update(iter, W, H, gradW, gradH): returns the metric (synchronises)
-static int update_progress(smk_solver* s, int iter_index, double* metric)
-{
-    int rc = enqueue_progress_kernels(s);
-    if (rc) return rc;
-    double h[4] = {0, 0, 0, 0};
-    SMK_HIP(hipMemcpyAsync(h, s->scal, 4 * sizeof(double), hipMemcpyDeviceToHost, s->st));
-    int fail_iter = INT_MAX;
-    rc = sync_and_check(s, &fail_iter);
-    if (rc) return rc;
-    return evaluate_progress(s, h, iter_index, metric);
-}
-
-// ---- the same evaluation, one iteration late ------------------------------------------------
-// the pinned result slots and their events, on first use
-static int ensure_progress_slots(smk_solver* s)
-{
-    if (s->pin) return 0;
-    int rc = s->own.pinned((void**)&s->pin, smk_solver::PROG_SLOTS * sizeof(smk_solver::ProgSlot));
-    for (int i = 0; i < smk_solver::PROG_SLOTS && !rc; ++i) rc = s->own.event(&s->pev[i], hipEventDisableTiming);
-    return rc;
-}
-// Enqueue the progress kernels of the iteration that has just been enqueued, copy their scalars and
-// the failure flag into pinned slot `b` and record an event; when `snapshot` is set also keep
-// (W, H, W'W) of this iteration so that the NEXT, speculatively enqueued iteration can be undone.
-// (sharded runs: everything a checked iteration needs, before the collectives start)
-static int progress_prealloc(smk_solver* s)
-{
-    int rc = ensure_progress_slots(s);
-    for (int b = 0; b < 2 && !rc; ++b) rc = ensure_snapshot(s, b);            // a sharded run keeps ONE check in flight (two slots)
-    return rc;
-}
-
-static int progress_begin(smk_solver* s, int b, bool snapshot, bool allow_defer = true)
-{
-    int rc = s->pin ? 0 : ensure_progress_slots(s);
-    if (!rc) rc = wait_r2(s);
-    if (rc) return rc;
-    s->poll_tag[b] = 0.0;
-    s->pin[b].h[7] = 0.0;
-    // deferred (check_rides_in_nnls): nothing is enqueued now -- the next H-side NNLS launch forms the sum; a snapshot can be
-    // promised only if this iteration's NNLS launches have been writing it (iter_snap_slot)
-    if (allow_defer && s->pg_defer_slot < 0 && (!snapshot || s->iter_snap_slot == b) && check_rides_in_nnls(s)) {
-        s->pg_defer_slot = b;
-        s->pg_defer_snap = snapshot;
-        s->pg_defer_tag = s->iter - 1;              // the iteration just enqueued
-        s->pin[b].fused = 1;
-        return 0;
-    }
-    ++s->check_routes[1];
-    if (s->o.algorithm == SMK_ALG_RANK2 && s->o.prog_est_algorithm == SMK_PROG_PG_RATIO && !is_dist(s)) {
-        // one launch: both gradient sums, the failure flag and the snapshot (rank2.hip)
-        if (snapshot) { rc = ensure_snapshot(s, b); if (rc) return rc; }
-        const size_t pe = rank2_progress_scratch_elems(s->m, s->n);
-        if (!s->pin_r2[b] && s->own.pinned((void**)&s->pin_r2[b], pe * sizeof(double))) return SMK_DEVICE_ERROR;
-        rc = launch_rank2_progress(s->Wt, s->m, view2(s), s->Gh, s->H, s->n, view1(s), s->Gw, s->r2_prog, s->fail_flag,
-                                   snapshot ? s->snap[b] : nullptr, s->st);
-        if (rc) return rc;
-        s->pin[b].fused = 2;             // per-workgroup partials: progress_end adds them up in index order
-        SMK_HIP(hipMemcpyAsync(s->pin_r2[b], s->r2_prog, pe * sizeof(double), hipMemcpyDeviceToHost, s->st));
-        SMK_HIP(hipEventRecord(s->pev[b], s->st));
-        return 0;
-    }
-    const bool fused_check = sw::progress_fused();
-    // BPP: gradW is the dual of the W-side NNLS (nmf_solver_bpp.hpp:362-366), whose projected-gradient sum is exactly zero after a
-    // solve that reached optimality (a solve that did not has raised the failure flag); SMK_BPP_GRADW=1 forms HH' W' - (AH')' anyway
-    const bool bpp_dual_is_gradient = !sw::bpp_gradw();
-    if (fused_check && s->o.prog_est_algorithm == SMK_PROG_PG_RATIO && !is_dist(s) && !is_wide(s->k) && !s->w_sharded) {
-        // round 6: gradients + snapshot in one launch, sums + failure flag written into the pinned slot by a second (kernels.hip:
-        // grad_pg2_snap_kernel, sum_partials2_host_kernel); SMK_PROGRESS_FUSED=0: the four stream operations of before
-        if (snapshot) { rc = ensure_snapshot(s, b); if (rc) return rc; }
-        const double tag = progress_polls() ? (double)(s->iter + 1) : 0.0;
-        rc = launch_grad_pg2_fused(s->Wt, s->m, view2(s), s->Gh, s->pg_partials, s->H, s->n, view1(s), s->Gw, s->pg_partials + s->pg_half,
-                                   s->k, s->scal, s->fail_flag, 5, snapshot ? s->snap[b] : nullptr, s->pin[b].h, s->st,
-                                   (s->o.algorithm == SMK_ALG_BPP && bpp_dual_is_gradient) ? 1 : 0, tag);
-        if (rc) return rc;
-        s->pin[b].fused = 1;
-        s->poll_tag[b] = tag;
-        if (tag == 0.0) SMK_HIP(hipEventRecord(s->pev[b], s->st));
-        return 0;
-    }
-    if (s->o.prog_est_algorithm == SMK_PROG_PG_RATIO && !is_dist(s) && !is_wide(s->k)) {
-        // both gradients in one launch, both sums + the failure flag in a second, one 64-byte read-back
-        rc = launch_grad_pg2(s->Wt, s->m, view2(s), s->Gh, s->pg_partials, s->H, s->n, view1(s), s->Gw,
-                             s->pg_partials + s->pg_half, s->k, s->scal, s->fail_flag, 5, s->st);
-        if (rc) return rc;
-        s->pin[b].fused = 1;
-        SMK_HIP(hipMemcpyAsync(s->pin[b].h, s->scal, 8 * sizeof(double), hipMemcpyDeviceToHost, s->st));
-    } else {
-        rc = enqueue_progress_kernels(s);
-        if (rc) return rc;
-        s->pin[b].fused = 0;
-        SMK_HIP(hipMemcpyAsync(s->pin[b].h, s->scal, 4 * sizeof(double), hipMemcpyDeviceToHost, s->st));
-        SMK_HIP(hipMemcpyAsync(&s->pin[b].flag, s->fail_flag, sizeof(int), hipMemcpyDeviceToHost, s->st));
-    }
-    if (snapshot) {
-        rc = ensure_snapshot(s, b); if (rc) return rc;
-        rc = s->w_sharded ? launch_snapshot(s->Wown, s->n_own, s->H, s->n, s->Gw, s->snap[b], s->k, 1, s->st)
-                          : launch_snapshot(s->Wt, s->m, s->H, s->n, s->Gw, s->snap[b], s->k, 1, s->st);
-        if (rc) return rc;
-    }
-    SMK_HIP(hipEventRecord(s->pev[b], s->st));
-    return 0;
-}
-
-// How many progress checks may be in flight.  ONE is the default, as in rounds 1 - 5: the host enqueues iteration i + 1, then waits
-// for the event of check i.  Round 6 suspected that wait of starving the device on small problems (C2: 13 500 it/s unchecked,
-// 11 000 checked) and generalised the loop to a ring of slots (pinned result, event, snapshot per in-flight check; the rule still
-// evaluated for every iteration in order, a run that converges at p restored from p's snapshot) -- measured with two and three
-// checks in flight: 10 980 / 11 100 it/s against 11 010 (profiles/r06_progress_check.txt).  The host is not the limit; what a
-// checked iteration costs is the gradient pass itself, which re-reads the S slabs of both right-hand sides (32 MB at C2).
-// SMK_PROGRESS_DEPTH=2|3 keeps the deeper pipeline selectable; sharded runs always use one (their checks carry collectives).
-static int progress_depth(const smk_solver* s)
-{
-    const int forced = sw::progress_depth();
-    if (is_dist(s) || s->comm || forced <= 1) return 1;
-    if (snapshot_elems(s->k, s->m, s->n) * sizeof(double) > ((size_t)1 << 30)) return 1;
-    return std::min(forced, smk_solver::PROG_SLOTS - 1);
-}
-
-// wait for slot b; SMK_FAILURE when the device flagged a solver failure up to that iteration
-static int progress_end(smk_solver* s, int b, int iter_index, double* metric)
-{
-    if (s->pg_defer_slot == b) {                    // no further iteration was enqueued: the check is formed the direct way now
-        s->pg_defer_slot = -1;
-        const int frc = progress_begin(s, b, false, false);
-        if (frc) return frc;
-    }
-    if (s->poll_tag[b] != 0.0) {
-        // the kernel that forms the totals stores the tag behind them (system scope); the stream going idle without it is an error
-        const volatile double* tagp = &s->pin[b].h[7];
-        const double want = s->poll_tag[b];
-        for (unsigned long spins = 1; *tagp != want; ++spins) {
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#endif
-            if ((spins & 0x3FFFF) == 0) {
-                const hipError_t q = hipStreamQuery(s->st);
-                if (q == hipErrorNotReady) continue;
-                if (q == hipSuccess && *tagp == want) break;
-                set_error(q == hipSuccess ? "the progress check's result never arrived in its pinned slot" : hipGetErrorString(q));
-                return q == hipSuccess ? SMK_FAILURE : SMK_DEVICE_ERROR;
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        s->poll_tag[b] = 0.0;
-    } else {
-        SMK_HIP(hipEventSynchronize(s->pev[b]));
-    }
-    if (s->pin[b].fused == 2) {
-        const int nb = rank2_progress_blocks(s->m, s->n);
-        const double* p = s->pin_r2[b];
-        double sw = 0.0, sh = 0.0;
-        for (int i = 0; i < nb; ++i) { sw += p[2 * i]; sh += p[2 * i + 1]; }
-        s->pin[b].h[0] = sw;
-        s->pin[b].h[1] = sh;
-        s->pin[b].flag = (int)p[2 * (size_t)nb];
-    } else if (s->pin[b].fused) s->pin[b].flag = (int)s->pin[b].h[5];
-    if (s->pin[b].flag != INT_MAX) return SMK_FAILURE;
-    return evaluate_progress(s, s->pin[b].h, iter_index, metric);
-}
-
-static int progress_restore(smk_solver* s, int b)
-{
-    int rc = s->w_sharded ? launch_snapshot(s->Wown, s->n_own, s->H, s->n, s->Gw, s->snap[b], s->k, 0, s->st)
-                          : launch_snapshot(s->Wt, s->m, s->H, s->n, s->Gw, s->snap[b], s->k, 0, s->st);
-    if (rc) return rc;
-    // whatever the undone iteration did to the failure flag is void; products / HH' are stale
-    const int big = INT_MAX;
-    SMK_HIP(hipMemcpyAsync(s->fail_flag, &big, sizeof(int), hipMemcpyHostToDevice, s->st));
-    SMK_HIP(hipStreamSynchronize(s->st));
-    s->inited = false;
-    s->wc_valid = false;
-    if (s->w_sharded) s->w_full = false;    // the snapshot holds this rank's own rows; the full copy is stale
-    return 0;
 }
 
 static int normalize_device(smk_solver* s)
@@ -1630,6 +1337,21 @@ static int normalize_device(smk_solver* s)
     return 0;
 }
 
+// what both fail-soft paths below end with: the initial factors again, a clean failure flag, a run from the start (returns 1)
+static int restart_from_initial_factors(smk_solver* s)
+{
+    const int big = INT_MAX;
+    (void)hipMemcpyAsync(s->Wt, s->W0c, (size_t)s->KP * s->m * sizeof(double), hipMemcpyDeviceToDevice, s->st);
+    (void)hipMemcpyAsync(s->H, s->H0c, (size_t)s->KP * s->n * sizeof(double), hipMemcpyDeviceToDevice, s->st);
+    (void)hipMemcpyAsync(s->fail_flag, &big, sizeof(int), hipMemcpyHostToDevice, s->st);
+    (void)hipStreamSynchronize(s->st);
+    s->inited = false;
+    s->normalized = false;
+    s->iter = 0;
+    s->pc.reset_estimator();
+    return 1;
+}
+
 // The fused HALS W sweep reported expired polls (-3: some workgroup was not resident): go back to the initial
 // factors and latch the one-launch-per-column path.  Returns 1 when the caller should repeat its work.
 static int hals_fail_soft(smk_solver* s)
@@ -1639,18 +1361,8 @@ static int hals_fail_soft(smk_solver* s)
     if (hipMemcpy(&flag, s->fail_flag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || flag != -3) return 0;
     fprintf(stderr, "smallk_amd: fused HALS W sweep could not keep its workgroups resident; repeating the run on the per-column path\n");
     s->hals_multi = true;
-    const int big = INT_MAX;
-    (void)hipMemcpyAsync(s->Wt, s->W0c, (size_t)s->KP * s->m * sizeof(double), hipMemcpyDeviceToDevice, s->st);
-    (void)hipMemcpyAsync(s->H, s->H0c, (size_t)s->KP * s->n * sizeof(double), hipMemcpyDeviceToDevice, s->st);
-    (void)hipMemcpyAsync(s->fail_flag, &big, sizeof(int), hipMemcpyHostToDevice, s->st);
     (void)hals_w_scratch_init(s->hals_scratch, s->k, s->m, s->st);
-    (void)hipStreamSynchronize(s->st);
-    s->inited = false;
-    s->normalized = false;
-    s->iter = 0;
-    s->pg0 = 1.0;
-    s->last_metric = 1.0;
-    return 1;
+    return restart_from_initial_factors(s);
 }
 
 // An NNLS launch that packs its own result (NnlsPack) met an entry beyond fp16's range after scaling (flag -4): the a-priori
@@ -1664,17 +1376,7 @@ static int pack_fail_soft(smk_solver* s)
     if (hipMemcpy(&flag, s->fail_flag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || flag != NNLS_PACK_OVERFLOW) return 0;
     fprintf(stderr, "smallk_amd: an NNLS launch could not pack its result inside fp16's range; repeating the run with the separate pack launch\n");
     s->pack_in_solve_off = true;
-    const int big = INT_MAX;
-    (void)hipMemcpyAsync(s->Wt, s->W0c, (size_t)s->KP * s->m * sizeof(double), hipMemcpyDeviceToDevice, s->st);
-    (void)hipMemcpyAsync(s->H, s->H0c, (size_t)s->KP * s->n * sizeof(double), hipMemcpyDeviceToDevice, s->st);
-    (void)hipMemcpyAsync(s->fail_flag, &big, sizeof(int), hipMemcpyHostToDevice, s->st);
-    (void)hipStreamSynchronize(s->st);
-    s->inited = false;
-    s->normalized = false;
-    s->iter = 0;
-    s->pg0 = 1.0;
-    s->last_metric = 1.0;
-    return 1;
+    return restart_from_initial_factors(s);
 }
 
 // ---- run-time guard of the product form ------------------------------------------------------------------------------
@@ -1841,6 +1543,18 @@ int smk_solver_iterate(smk_solver* s, int iters)
     return SMK_OK;
 }
 
+// One iteration of a checked loop (the "run one iteration" operation of check_ring.h).  snap_slot >= 0: the check that follows wants
+// a snapshot in that slot, and where the check rides in the NNLS launches (check_rides_in_nnls) those launches write it themselves;
+// progress_begin takes the promise back.
+static int checked_iteration(smk_solver* s, int snap_slot)
+{
+    s->pc.iter_snap_slot = (snap_slot >= 0 && check_rides_in_nnls(s)) ? snap_slot : -1;
+    int rc = solver_iteration(s);
+    if (!rc) rc = guard_step(s);
+    if (rc) s->pc.iter_snap_slot = -1;
+    return rc;
+}
+
 // `iters` iterations as NmfSolve<> runs them past min_iter (nmf_solve_generic.hpp:98-121): after every iteration the stopping rule's
 // metric is formed (gradients for PG_RATIO, nmf_solver_bpp.hpp:370-377 / nmf_solver_mu.hpp:151-164; W - Wprev for DELTA_FNORM) and
 // read back -- by the same one-iteration-late scheme as smk_solver_run (snapshot, pinned slot, event), with a tolerance that never
@@ -1852,34 +1566,18 @@ int smk_solver_iterate_checked(smk_solver* s, int iters, double* last_metric)
     int rc = 0;
     if (!s->inited) { rc = solver_init(s); if (rc) return rc; }
     if (s->o.algorithm == SMK_ALG_RANK2) { set_error("iterate_checked: MU / HALS / BPP"); return SMK_UNSUPPORTED; }
-    const int depth = progress_depth(s), NS = smk_solver::PROG_SLOTS;
-    const int base = s->iter;                       // the very first iteration of a run initialises the estimator (PG_RATIO: pg0)
-    std::deque<int> pend;                           // iterations whose check is outstanding, oldest first
-    double metric = 1.0;
-    for (int i = 0; i < iters; ++i) {
-        s->iter_snap_slot = check_rides_in_nnls(s) ? i % NS : -1;      // this iteration's NNLS launches also write its snapshot
-        rc = solver_iteration(s);
-        s->iter_snap_slot = rc ? -1 : s->iter_snap_slot;
-        if (rc) return rc;
-        rc = guard_step(s);
-        if (rc) { s->iter_snap_slot = -1; return rc; }
-        rc = progress_begin(s, i % NS, true);
-        s->iter_snap_slot = -1;
-        if (rc) return rc;
-        while ((int)pend.size() >= depth) {
-            rc = progress_end(s, pend.front() % NS, base + pend.front(), &metric);
-            if (rc) return rc;
-            pend.pop_front();
-        }
-        pend.push_back(i);
-    }
-    while (!pend.empty()) {
-        rc = progress_end(s, pend.front() % NS, base + pend.front(), &metric);
-        if (rc) return rc;
-        pend.pop_front();
-    }
-    if (last_metric) *last_metric = metric;
-    return SMK_OK;
+    check_ring::Params p;
+    p.depth = progress_depth(s);
+    p.max_iter = iters;
+    p.every = true;
+    p.base = s->iter;                               // the very first iteration of a run initialises the estimator (PG_RATIO: pg0)
+    const check_ring::Result r = check_ring::drive(p,
+        [s](int, int snap_slot) { return checked_iteration(s, snap_slot); },
+        [s](int, int b, bool snapshot) { return progress_begin(s, b, snapshot); },
+        [s](int i, int b, double* metric) { return progress_end(s, b, i, metric); },
+        [](int, int) { return 0; }, [](const char*) {});
+    if (!r.code && last_metric) *last_metric = r.metric;
+    return r.code;
 }
 
 // which product form the solver is using now (SMK_NSPLIT numbering; 8 = the accurate form), how often the run-time guard has
@@ -2000,8 +1698,8 @@ static int rank2_persist_run(smk_solver* s, int* status, int* count)
     }
     if (*status == R2P_CONVERGED || *status == R2P_EXHAUSTED) {
         s->iter += (int)s->r2p_pin[2];
-        s->pg0 = s->r2p_pin[3];
-        s->last_metric = s->r2p_pin[4];
+        s->pc.pg0 = s->r2p_pin[3];
+        s->pc.last_metric = s->r2p_pin[4];
         s->normalized = false;
         s->inited = false;             // HH' and the stored products were never materialised: a later run starts from solver.Init
         s->wc_valid = false;
@@ -2018,7 +1716,7 @@ static int solver_run_once(smk_solver* s, smk_stats* stats)
     const double t0 = wall_us();
     int rc = 0, result = SMK_OK;
     bool success = false;
-    int iter = 0, success_count = 0, fail_iter = INT_MAX;
+    int iter = 0, fail_iter = INT_MAX;
     static std::mutex r2p_device_mu[64];
     std::unique_lock<std::mutex> r2p_lock;
 
@@ -2053,77 +1751,24 @@ static int solver_run_once(smk_solver* s, smk_stats* stats)
             fprintf(stderr, "smallk_amd: the resident RANK2 kernel could not synchronise its workgroups on device %d; this process continues on the launch-per-kernel path there\n", smk_current_device());
     }
 
-    // The stopping rule of iteration i (NmfSolve, nmf_solve_generic.hpp:81-121) is evaluated AFTER
-    // iteration i+1 has been enqueued: the host never leaves the GPU idle waiting for a scalar.  When
-    // the rule fires for i, the state of i is restored from its snapshot and i+1 is discarded, so
-    // results and iteration counts are those of the check-every-iteration loop (SMK_SYNC_PROGRESS=1
-    // runs that loop instead).
+    // The stopping rule of iteration i (NmfSolve, nmf_solve_generic.hpp:81-121) is evaluated AFTER iteration i + 1 has been enqueued
+    // and i is restored from its snapshot when it fires (check_ring.h); SMK_SYNC_PROGRESS=1 runs the check-every-iteration loop.
     {
-        const bool sync_mode = sw::sync_progress();
-        const int depth = progress_depth(s), NS = smk_solver::PROG_SLOTS;
-        std::deque<int> pend;                          // iterations whose check is outstanding, oldest first (at most `depth`)
-        auto resolve = [&](int p, bool speculated) -> int {      // 0: go on, 1: converged at p, < 0: error
-            double metric = 1.0;
-            int prc = progress_end(s, p % NS, p, &metric);
-            if (prc) { result = prc; return -1; }
-            if (p < o.min_iter) return 0;              // iteration 0 only initialises the estimator
-            if (o.verbose && ((p + 1 < 10) || ((p + 1) % 10 == 0)))
-                printf("%d:\tprogress metric:\t%g\n", p + 1, metric);     // nmf_progress_estimation.hpp:22-33
-            if (metric <= o.tol) {
-                if (++success_count >= o.tolcount) {
-                    if (o.verbose) printf("\nSolution converged after %d iterations.\n\n", p + 1);
-                    if (speculated) { prc = progress_restore(s, p % NS); if (prc) { result = prc; return -1; } s->iter = p + 1; }
-                    return 1;
-                }
-            } else {
-                success_count = 0;
-            }
-            return 0;
-        };
-        for (iter = 0; iter < o.max_iter; ++iter) {
-            // (an iteration whose check will want a snapshot lets its NNLS launches write it: check_rides_in_nnls)
-            s->iter_snap_slot = (!sync_mode && iter >= o.min_iter && check_rides_in_nnls(s)) ? iter % NS : -1;
-            rc = solver_iteration(s);
-            if (rc) { s->iter_snap_slot = -1; result = rc; goto done; }
-            rc = guard_step(s);
-            if (rc) { s->iter_snap_slot = -1; result = rc; goto done; }
-            const bool check = (iter == 0) || (iter >= o.min_iter);
-            if (sync_mode) {
-                if (!check) { if (o.verbose) printf("%d:\tprogress metric: \t(min_iter)\n", iter + 1); continue; }
-                rc = progress_begin(s, iter % NS, false);
-                if (rc) { result = rc; goto done; }
-                const int r = resolve(iter, false);
-                if (r < 0) goto failed_check;
-                if (iter < o.min_iter && o.verbose) printf("%d:\tprogress metric: \t(min_iter)\n", iter + 1);
-                if (r == 1) { success = true; break; }
-                continue;
-            }
-            if (check) {
-                rc = progress_begin(s, iter % NS, iter >= o.min_iter);
-                s->iter_snap_slot = -1;
-                if (rc) { result = rc; goto done; }
-            }
-            s->iter_snap_slot = -1;
-            // the oldest outstanding checks, once `depth` of them are in flight (depth 1: the check of the previous iteration,
-            // as in rounds 1 - 5); an unchecked iteration (0 < iter < min_iter) leaves nothing behind, as before
-            while (!pend.empty() && ((int)pend.size() >= depth || !check)) {
-                const int p = pend.front();
-                pend.pop_front();
-                const int r = resolve(p, true);
-                if (r < 0) goto failed_check;
-                if (r == 1) { success = true; iter = p; pend.clear(); break; }
-            }
-            if (success) break;
-            if (iter < o.min_iter && o.verbose) printf("%d:\tprogress metric: \t(min_iter)\n", iter + 1);
-            if (check) pend.push_back(iter);
-        }
-        while (!success && !pend.empty()) {            // what is still outstanding when the iterations are used up
-            const int p = pend.front();
-            pend.pop_front();
-            const int r = resolve(p, !pend.empty());   // the very last one: nothing ran after it
-            if (r < 0) goto failed_check;
-            if (r == 1) { success = true; iter = p; pend.clear(); }
-        }
+        check_ring::Params p;
+        p.depth = progress_depth(s);
+        p.min_iter = o.min_iter;  p.max_iter = o.max_iter;  p.tol = o.tol;  p.tolcount = o.tolcount;
+        p.sync = sw::sync_progress();
+        p.verbose = o.verbose != 0;
+        bool in_check = false;                   // the error came out of a check, not out of an iteration
+        const check_ring::Result r = check_ring::drive(p,
+            [s](int, int snap_slot) { return checked_iteration(s, snap_slot); },
+            [s](int, int b, bool snapshot) { return progress_begin(s, b, snapshot); },
+            [&](int i, int b, double* metric) { const int e = progress_end(s, b, i, metric); in_check |= e != 0; return e; },
+            [&](int i, int b) { const int e = progress_restore(s, b); in_check |= e != 0; if (!e) s->iter = i + 1; return e; },
+            [](const char* line) { fputs(line, stdout); });
+        iter = r.iterations;
+        success = r.converged;
+        if (r.code) { result = r.code; if (in_check) goto failed_check; goto done; }
     }
 
 finish:
@@ -2234,7 +1879,7 @@ int smk_solver_project_h(smk_solver* s)
     s->from_nnls[0] = s->from_nnls[1] = false;
     s->nnls_packed[0] = s->nnls_packed[1] = false;
     s->tail_nblk[0] = s->tail_nblk[1] = 0;
-    s->pg_defer_slot = s->iter_snap_slot = s->pg_totals_slot = -1;
+    s->pc.reset();
     s->normalized = false;          // H is about to change
     rc = gram_w(s);
     if (!rc) rc = prod1(s);
@@ -2439,7 +2084,7 @@ int smk_solver_kernel_name(const smk_solver* s, int which, char* out, int cap)
                                              "sums in the next H-side NNLS launch, totals as one launch",
                                              "sums in the next H-side NNLS launch, totals in the tail of the pass behind it"};
         for (int r = 3; r >= 1; --r)
-            if (s->check_routes[r]) name += (name.empty() ? "" : "; ") + std::to_string(s->check_routes[r]) + " x " + route[r];
+            if (s->pc.check_routes[r]) name += (name.empty() ? "" : "; ") + std::to_string(s->pc.check_routes[r]) + " x " + route[r];
         if (name.empty()) name = "none formed yet";
     } else if (s->a->sparse) {
         const int ldx = s->Wc ? 2 : s->KP;

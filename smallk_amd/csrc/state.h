@@ -1,4 +1,4 @@
-// smallk_amd/csrc/state.h -- host state shared by context.cpp, matrix.cpp and solver.cpp: the per-thread device
+// smallk_amd/csrc/state.h -- host state shared by context.cpp, matrix.cpp, solver.cpp and progress.cpp: the per-thread device
 // context, the resident matrix and the solver handle behind the opaque types of include/smallk_amd.h, and the
 // few functions that cross those files.
 #pragma once
@@ -79,6 +79,28 @@ struct smk_matrix {
     mutable smk::Owned own;                          // every device block above (the lazily built stored transpose included); the blocked CSC and the segment plans free themselves
 };
 
+// The stopping rule's check (progress.cpp), evaluated one iteration late on the schedule of check_ring.h: per slot of the ring a
+// pinned result, an event and a snapshot of (W, H, W'W), so that a speculative iteration can be undone.  Everything lives in the
+// solver's Owned.
+struct ProgressCheck {
+    static constexpr int PROG_SLOTS = 4;         // array bound: the largest depth + 1 (a run uses depth + 1 of them)
+    struct ProgSlot { double h[8]; int flag; int fused; };     // fused: the flag travels in h[5]
+    ProgSlot* pin = nullptr;
+    hipEvent_t pev[PROG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+    double poll_tag[PROG_SLOTS] = {0, 0, 0, 0};      // != 0: the kernel stores this into h[7] behind the result; progress_end polls the slot (no event)
+    double* snap[PROG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+    double* pin_r2[PROG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};      // RANK2: pinned copies of the progress partials (the host sums them)
+    // deferred check (BPP, k <= 16; check_rides_in_nnls): the slot whose totals the NEXT H-side NNLS launch produces, the
+    // iteration tag up to which a failure counts for it, whether its snapshot is being written by this iteration's NNLS launches
+    int pg_defer_slot = -1, pg_defer_tag = 0, pg_defer_nblk = 0, iter_snap_slot = -1;
+    bool pg_defer_snap = false;
+    int pg_totals_slot = -1;                 // >= 0: the H-side launch has left the partial sums of this slot's check; its totals are due
+    unsigned check_routes[4] = {0, 0, 0, 0}; // checks formed so far by route (smk_solver_kernel_name(2)): 1 own launches, 2 NNLS riders + totals launch, 3 riders + pass tail
+    double pg0 = 1.0, last_metric = 1.0;     // the estimator: PG_RATIO's first norm, the metric last read
+    void reset() { pg_defer_slot = iter_snap_slot = pg_totals_slot = -1; }      // nothing deferred, nothing promised, no totals due
+    void reset_estimator() { pg0 = last_metric = 1.0; }                         // a run from the start
+};
+
 struct smk_solver {
     smk_options o;
     const smk_matrix* a = nullptr;
@@ -94,8 +116,6 @@ struct smk_solver {
     // RANK2 (rank2.hip): scratch of the fused solve / progress kernels (ticket + partial sums), W'W of the W just solved
     // (before its normalisation), and -- sparse A -- compact N x 2 copies of the factors for the gather products
     double *r2_scratch = nullptr, *r2_prog = nullptr, *Graw = nullptr, *Hc = nullptr, *Wc = nullptr;
-    static constexpr int PROG_SLOTS = 4;         // progress checks in flight + 1 (solver_run_once / smk_solver_iterate_checked)
-    double* pin_r2[PROG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};      // pinned copies of the progress partials (the host sums them)
     // the whole RANK2 factorisation as one resident launch (rank2_persist.hip): second H buffer, the rows of (AH')', partial
     // sums, barrier words, result slots (device + pinned); latched off after an aborted launch
     double *r2p_hc1 = nullptr, *r2p_r2c = nullptr, *r2p_part = nullptr, *r2p_out = nullptr, *r2p_pin = nullptr;
@@ -115,12 +135,6 @@ struct smk_solver {
     double* nnls_scratch = nullptr;       // BPP: inverses of W'W and HH' + path selectors (k > 32), two halves
     unsigned* nnls_defer = nullptr;       // BPP, k in (32, 64]: work list between nnls_bpp_g16_kernel and the wave-per-column kernel
     int hals_ep_blocks = 0;               // HALS, k <= 32: Gram partials the sweeps' epilogues may write into gram_scratch (0: epilogues off)
-    // deferred progress check (BPP, k <= 16; check_rides_in_nnls): the slot whose totals the NEXT H-side NNLS launch produces, the
-    // iteration tag up to which a failure counts for it, whether its snapshot is being written by this iteration's NNLS launches
-    int pg_defer_slot = -1, pg_defer_tag = 0, pg_defer_nblk = 0, iter_snap_slot = -1;
-    bool pg_defer_snap = false;
-    unsigned check_routes[4] = {0, 0, 0, 0}; // progress checks formed so far by route (smk_solver_kernel_name(2)): 1 own launches, 2 NNLS riders + totals launch, 3 riders + pass tail
-    int pg_totals_slot = -1;                 // >= 0: the H-side launch has left the partial sums of this slot's check; its totals are due
     hipStream_t st_inv = nullptr;         // the 0.1 ms single-workgroup inversions run here, beside the streaming products
     hipEvent_t ev_g[2] = {nullptr, nullptr}, ev_inv[2] = {nullptr, nullptr};
     bool inv_pending[2] = {false, false};
@@ -151,7 +165,7 @@ struct smk_solver {
     int* fail_flag = nullptr;
     int iter = 0;
     bool have_factors = false, inited = false, normalized = false;
-    double pg0 = 1.0, last_metric = 1.0;
+    ProgressCheck pc;                     // the stopping rule's check (progress.cpp)
     size_t pg_half = 2048;
     // comm: a native communicator (RCCL or the in-process stand-in, comm.cpp) or -- test hook -- a host callback
     int rank = 0, world = 1;
@@ -182,13 +196,6 @@ struct smk_solver {
     bool gh_pending = false;
     bool r2_pending = false;              // the chunk exchanges of the last H*At pass have not been joined by the main stream yet
     bool inv_done[2] = {false, false};    // the inverse of this side's current Gram matrix is in place (ordered before the main stream)
-    // stopping rule evaluated one iteration late (smk_solver_run): pinned result slots, events, and a
-    // snapshot of (W, H, W'W) per checked iteration so that a speculative iteration can be undone
-    struct ProgSlot { double h[8]; int flag; int fused; };     // fused: the flag travels in h[5]
-    ProgSlot* pin = nullptr;
-    hipEvent_t pev[PROG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
-    double poll_tag[PROG_SLOTS] = {0, 0, 0, 0};      // != 0: the kernel stores this into h[7] behind the result; progress_end polls the slot (no event)
-    double* snap[PROG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
     // timing
     bool timing = false;
     // a pair of event records around a launch costs ~11 us of idle time (5.7 us in front of the kernel, 5.8 behind it: measured
