@@ -560,6 +560,42 @@ int smk_preprocess_result_matrix(const smk_preprocess_result* r, smk_matrix** ou
  * SMK_OK, or SMK_FAILURE when the file cannot be written */
 int smk_preprocess_write_mtx(const smk_preprocess_result* r, const char* path, unsigned precision);
 
+/* ---- a fitted vocabulary: new documents into the term space of a fit --------------------------------
+ * A vocabulary is what a fit leaves behind for documents that arrive later: the input's term count (height_in), the surviving
+ * terms (original indices, strictly ascending), their idf = log(width_fit / df) exactly as the fit computed them, and the fit's
+ * boolean_mode; all on the device, with the scattered map old term -> new term.  Applying it to a CSC term-count matrix in
+ * the ORIGINAL term numbering gives the matrix smk_transform needs: entries of pruned terms removed, the rest renumbered with
+ * their order kept, scored (1 + log(count)) * idf[term] and every column normalised, operation for operation as the fit scores
+ * its own columns -- a fit's own documents come out with the fit's bits. */
+typedef struct smk_vocabulary smk_vocabulary;
+/* the vocabulary of a fit; SMK_FAILURE on a failed fit and on an applied result (which keeps no idf: its vocabulary is the one
+ * that was applied) */
+int smk_preprocess_result_vocabulary(const smk_preprocess_result* r, smk_vocabulary** out);
+/* from host arrays of `height` elements (a saved vocabulary).  Checked before anything is launched (SMK_BAD_PARAM +
+ * smk_last_error): height >= 1, non-null arrays, term_indices strictly ascending and below height_in.  idf is taken as given */
+int smk_vocabulary_create(unsigned height_in, unsigned height, const unsigned* term_indices, const double* idf, int boolean_mode,
+                          smk_vocabulary** out);
+void smk_vocabulary_destroy(smk_vocabulary* v);
+int smk_vocabulary_sizes(const smk_vocabulary* v, unsigned* height_in, unsigned* height, int* boolean_mode);
+/* term_indices and idf: height elements each; either may be NULL */
+int smk_vocabulary_download(const smk_vocabulary* v, unsigned* term_indices, double* idf);
+typedef struct smk_apply_options {
+    unsigned min_terms; /* a document with fewer surviving entries is dropped; 0 keeps every document, empty ones included */
+    int boolean_mode;   /* -1: the fit's */
+} smk_apply_options;
+/* The input is checked as smk_preprocess checks its own (rows < height_in; they need not be sorted inside a column).  *out is
+ * an ordinary result: height and term_indices are the vocabulary's, doc_indices the input columns that were kept (ascending),
+ * the log is empty, iterations 0, both timings filled in.  SMK_FAILURE when every column was dropped (*out then holds the
+ * vocabulary's height, the input's width and the number of entries in surviving terms). */
+int smk_vocabulary_apply(const smk_vocabulary* v, const smk_apply_options* opts, unsigned width, unsigned nnz,
+                         const unsigned* col_offsets, const unsigned* row_indices, const double* data, smk_preprocess_result** out);
+/* the same with the input in device memory, by the conventions of smk_matrix_create_sparse_device: offsets from 0, SMK_IDX_I32 /
+ * SMK_IDX_I64 indices, SMK_DT_F64 / SMK_DT_F32 values, the caller's stream, the index arrays checked by a kernel before anything
+ * reads through them.  The result has the bits smk_vocabulary_apply gives on the same arrays; its upload time is 0. */
+int smk_vocabulary_apply_device(const smk_vocabulary* v, const smk_apply_options* opts, unsigned width, unsigned nnz,
+                                const void* col_offsets, int idx_type, const void* row_indices, int row_idx_type, const void* values,
+                                int dtype, void* stream, smk_preprocess_result** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,16 +15,16 @@ from . import flatclust
 from .hierclust import hier_nmf2, TreeResults
 
 __all__ = ["DenseMatrix", "SparseMatrix", "nmf_sparse", "load_matrix_market", "NmfSolver", "NmfResult", "nmf", "nmf_device", "initialize", "finalize", "is_initialized",
-           "make_options", "uniform_host", "nnls_blockpivot", "nmf_sharded", "Comm", "set_stream", "thread_context_begin", "thread_context_end", "trim_device_cache", "SmallkAPI", "hierclust", "flatclust", "hier_nmf2", "TreeResults", "Residual", "relative_error", "labels_device", "top_terms_device", "transform", "NNDSVD_VARIANTS", "_lib"]
+           "make_options", "uniform_host", "nnls_blockpivot", "nmf_sharded", "Comm", "set_stream", "thread_context_begin", "thread_context_end", "trim_device_cache", "SmallkAPI", "hierclust", "flatclust", "hier_nmf2", "TreeResults", "Residual", "relative_error", "labels_device", "top_terms_device", "transform", "NNDSVD_VARIANTS", "Vocabulary", "_lib"]
 
 
 def __getattr__(name):
     """``smallk_amd.Hierclust`` / ``smallk_amd.Flatclust`` / ``smallk_amd.pyclust`` (pysmallk's clustering classes,
-    pysmallk/interface/smallk_lib.pyx:924-1420) and ``smallk_amd.Preprocessor`` (:1643-1815), loaded on first use."""
-    if name in ("Preprocessor", "preprocess"):
+    pysmallk/interface/smallk_lib.pyx:924-1420) and ``smallk_amd.Preprocessor`` (:1643-1815) with ``smallk_amd.Vocabulary``, loaded on first use."""
+    if name in ("Preprocessor", "preprocess", "Vocabulary"):
         import importlib
         mod = importlib.import_module(".preprocess", __name__)
-        return mod if name == "preprocess" else mod.Preprocessor
+        return mod if name == "preprocess" else getattr(mod, name)
     if name in ("Hierclust", "Flatclust", "pyclust"):
         import importlib
         mod = importlib.import_module(".pyclust", __name__)

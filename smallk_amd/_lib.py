@@ -54,6 +54,11 @@ class PreprocessOptions(C.Structure):
     _fields_ = [("max_iter", C.c_uint), ("docs_per_term", C.c_uint), ("terms_per_doc", C.c_uint), ("boolean_mode", C.c_int)]
 
 
+class ApplyOptions(C.Structure):
+    """struct smk_apply_options (Vocabulary.apply: min_terms, boolean_mode with -1 for the fit's)."""
+    _fields_ = [("min_terms", C.c_uint), ("boolean_mode", C.c_int)]
+
+
 class SvdOptions(C.Structure):
     """struct smk_svd_options: rank, oversampling, power iterations, seed and the optional caller's test matrix (a device view)."""
     _fields_ = [("k", C.c_int), ("oversample", C.c_int), ("power_iters", C.c_int), ("seed", C.c_uint64), ("omega", C.c_void_p),
@@ -261,6 +266,16 @@ SYMBOLS = {
                                                  C.POINTER(C.c_uint), _dp]),
     "smk_preprocess_result_matrix": (C.c_int, [_vp, C.POINTER(_vp)]),
     "smk_preprocess_write_mtx": (C.c_int, [_vp, C.c_char_p, C.c_uint]),
+    # a fitted vocabulary and its application to new documents (vocabulary.cpp)
+    "smk_preprocess_result_vocabulary": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "smk_vocabulary_create": (C.c_int, [C.c_uint, C.c_uint, C.POINTER(C.c_uint), _dp, C.c_int, C.POINTER(_vp)]),
+    "smk_vocabulary_destroy": (None, [_vp]),
+    "smk_vocabulary_sizes": (C.c_int, [_vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int)]),
+    "smk_vocabulary_download": (C.c_int, [_vp, C.POINTER(C.c_uint), _dp]),
+    "smk_vocabulary_apply": (C.c_int, [_vp, C.POINTER(ApplyOptions), C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint),
+                                       _dp, C.POINTER(_vp)]),
+    "smk_vocabulary_apply_device": (C.c_int, [_vp, C.POINTER(ApplyOptions), C.c_uint, C.c_uint, _vp, C.c_int, _vp, C.c_int, _vp,
+                                              C.c_int, _vp, C.POINTER(_vp)]),
 }
 
 _lib = None

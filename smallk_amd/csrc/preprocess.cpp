@@ -18,22 +18,7 @@
 #include "common.h"
 #include "owned.h"
 #include "preprocess.h"
-
-struct smk_preprocess_result {
-    unsigned height = 0, width = 0, nnz = 0, iterations = 0;
-    bool failed = false;
-    std::vector<unsigned> log;                       // height, width, nonzeros per iteration
-    unsigned *cp = nullptr, *term = nullptr, *doc = nullptr;
-    uint2* ent = nullptr;
-    double* score = nullptr;
-    double upload_ms = 0.0, device_ms = 0.0;
-    ~smk_preprocess_result()
-    {
-        void* ptrs[] = {cp, term, doc, ent, score};
-        for (void* p : ptrs)
-            if (p) (void)smk::dev_free(p);
-    }
-};
+#include "preprocess_result.h"
 
 namespace {
 
@@ -136,6 +121,8 @@ int run(const smk_preprocess_options& o, unsigned height, unsigned width, unsign
 {
     Work w;
     w.st = st;
+    res->height_in = height;
+    res->boolean_mode = o.boolean_mode;
     const unsigned base = col_offsets[0];
     std::vector<unsigned> cp_host((size_t)width + 1);
     for (size_t c = 0; c <= width; ++c) cp_host[c] = col_offsets[c] - base;
@@ -240,13 +227,11 @@ int run(const smk_preprocess_options& o, unsigned height, unsigned width, unsign
     PP_TRY(fetch(w, 0, w.cp[w.a] + width, 1));
     nnz = w.host[0];
 
-    // scores on the final matrix; the result takes the current halves
-    smk::Scratch<double> idf;
-    PP_TRY(alloc(idf.put(), (size_t)height + 1));
+    // scores on the final matrix; the result takes the current halves and keeps the idf (smk_preprocess_result_vocabulary)
+    PP_TRY(alloc(&res->idf, (size_t)height + 1));
     PP_TRY(alloc(&res->score, nnz));
-    const int rc_sc = smk::pp_scores(w.cp[w.a], w.ent[w.a], width, w.stat[w.a], height, idf, res->score, w.st);
+    const int rc_sc = smk::pp_scores(w.cp[w.a], w.ent[w.a], width, w.stat[w.a], height, res->idf, res->score, w.st);
     const hipError_t e = hipStreamSynchronize(w.st);
-    idf.reset();
     if (rc_sc) return SMK_DEVICE_ERROR;
     if (e != hipSuccess) { smk::set_error(std::string("preprocess scores: ") + hipGetErrorString(e)); return SMK_DEVICE_ERROR; }
     res->device_ms = now_ms() - t1;

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from smallk_amd import _lib as L
-from smallk_amd.solver import SparseMatrix, initialize, is_initialized, load_matrix_market
+from smallk_amd.solver import SparseMatrix, initialize, is_initialized, load_matrix_market, _is_tensor, _stream_of, _tensor_view
 
 _up = C.POINTER(C.c_uint)
 
@@ -71,6 +71,13 @@ class PreprocessResult:
     def write_mtx(self, path, precision=4):
         L.check(L.lib().smk_preprocess_write_mtx(self._h, str(path).encode(), int(precision)), "smk_preprocess_write_mtx")
 
+    def vocabulary(self) -> "Vocabulary":
+        """What the fit leaves for documents that arrive later: its surviving terms, their idf and its boolean_mode, on the
+        device.  Only a fit has one: an applied result raises SmallkError(FAILURE)."""
+        h = C.c_void_p()
+        L.check(L.lib().smk_preprocess_result_vocabulary(self._h, C.byref(h)), "smk_preprocess_result_vocabulary")
+        return Vocabulary._from_handle(h)
+
     def close(self):
         if self._h:
             L.lib().smk_preprocess_result_destroy(self._h)
@@ -99,6 +106,129 @@ def preprocess(height, width, col_offsets, row_indices, data, *, max_iter=1000, 
     if rc not in (L.OK, L.FAILURE):
         L.check(rc, "smk_preprocess")
     return PreprocessResult(h, rc)
+
+
+class Vocabulary:
+    """A fitted term set on the device: ``term_indices`` (the surviving terms' original indices, ascending), ``idf`` (fp64, as
+    the fit computed it), ``height_in`` (the term count of the fit's input) and the fit's ``boolean_mode``.  ``apply`` turns raw
+    term counts of new documents, in the original term numbering, into the tf-idf matrix of the fit's term space."""
+
+    def __init__(self, term_indices, idf, height_in, boolean_mode=0):
+        if not is_initialized():
+            initialize(-1)
+        term = _u32(term_indices)
+        w = np.ascontiguousarray(idf, dtype=np.float64)
+        if term.ndim != 1 or w.shape != term.shape:
+            raise ValueError("Vocabulary: term_indices and idf are 1-D arrays of one length")
+        self._h = C.c_void_p()
+        L.check(L.lib().smk_vocabulary_create(int(height_in), int(term.size), term.ctypes.data_as(_up),
+                                              w.ctypes.data_as(C.POINTER(C.c_double)), int(boolean_mode), C.byref(self._h)),
+                "smk_vocabulary_create")
+        self._read_sizes()
+
+    @classmethod
+    def _from_handle(cls, handle):
+        self = cls.__new__(cls)
+        self._h = handle
+        self._read_sizes()
+        return self
+
+    def _read_sizes(self):
+        hi, h, b = C.c_uint(), C.c_uint(), C.c_int()
+        L.check(L.lib().smk_vocabulary_sizes(self._h, C.byref(hi), C.byref(h), C.byref(b)), "smk_vocabulary_sizes")
+        self.height_in, self.height, self.boolean_mode = hi.value, h.value, b.value
+
+    def _download(self):
+        term = np.zeros(self.height, dtype=np.uint32)
+        idf = np.zeros(self.height, dtype=np.float64)
+        L.check(L.lib().smk_vocabulary_download(self._h, term.ctypes.data_as(_up), idf.ctypes.data_as(C.POINTER(C.c_double))),
+                "smk_vocabulary_download")
+        return term, idf
+
+    @property
+    def term_indices(self):
+        return self._download()[0]
+
+    @property
+    def idf(self):
+        return self._download()[1]
+
+    def save(self, path):
+        """The vocabulary as an .npz file (term_indices, idf, height_in, boolean_mode) for a later process."""
+        term, idf = self._download()
+        with open(path, "wb") as f:
+            np.savez(f, term_indices=term, idf=idf, height_in=np.uint32(self.height_in), boolean_mode=np.int32(self.boolean_mode))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(z["term_indices"], z["idf"], int(z["height_in"]), int(z["boolean_mode"]))
+
+    def apply(self, col_offsets, row_indices=None, data=None, width=None, *, min_terms=0, boolean_mode=-1) -> PreprocessResult:
+        """Score new documents.  The input is a CSC term-count matrix with ``height_in`` rows: host arrays ``(col_offsets,
+        row_indices, data, width)``, one scipy CSC matrix, or torch CSC tensors in GPU memory (1-D ``ccol_indices``,
+        ``row_indices``, ``values``, or one ``torch.sparse_csc_tensor``), which never leave the device.  ``min_terms`` drops a
+        document with fewer surviving entries (0 keeps all, empty ones included); ``boolean_mode`` -1 is the fit's.  The
+        result's ``ok`` is False when every document was dropped."""
+        o = L.ApplyOptions(int(min_terms), int(boolean_mode))
+        h = C.c_void_p()
+        first = col_offsets
+        if _is_tensor(first):
+            import torch
+            if first.layout == torch.sparse_csc:
+                if first.dim() != 2 or first.shape[0] != self.height_in:
+                    raise ValueError(f"Vocabulary.apply: expected a sparse tensor with {self.height_in} rows, got shape {tuple(first.shape)}")
+                col_offsets, row_indices, data, width = first.ccol_indices(), first.row_indices(), first.values(), first.shape[1]
+            if row_indices is None or data is None:
+                raise TypeError("Vocabulary.apply: ccol_indices, row_indices and values, or one sparse CSC tensor")
+            width = int(col_offsets.numel() - 1 if width is None else width)
+            if col_offsets.numel() != width + 1 or row_indices.numel() != data.numel():
+                raise ValueError("Vocabulary.apply: ccol_indices needs width + 1 entries, row_indices as many as values")
+            nnz = int(data.numel())
+            views = []
+            for t, what, kinds in ((col_offsets, "ccol_indices", "index"), (row_indices, "row_indices", "index"), (data, "values", "factor")):
+                if nnz == 0 and what != "ccol_indices":
+                    views.append((t, C.c_void_p(), L.IDX_I32 if kinds == "index" else L.DT_F64))
+                else:
+                    t = t.contiguous()
+                    views.append((t,) + _tensor_view(t, f"Vocabulary.apply({what})", ndim=1, kinds=kinds)[:2])
+            (co, co_p, co_t), (ri, ri_p, ri_t), (va, va_p, va_t) = views
+            rc = L.lib().smk_vocabulary_apply_device(self._h, C.byref(o), width, nnz, co_p, co_t, ri_p, ri_t, va_p, va_t,
+                                                     _stream_of(co), C.byref(h))
+            where = "smk_vocabulary_apply_device"
+        else:
+            if hasattr(first, "tocsc"):
+                A = first.tocsc()
+                if A.shape[0] != self.height_in:
+                    raise ValueError(f"Vocabulary.apply: expected a matrix with {self.height_in} rows, got shape {A.shape}")
+                col_offsets, row_indices, data, width = A.indptr, A.indices, A.data, A.shape[1]
+            if row_indices is None or data is None:
+                raise TypeError("Vocabulary.apply: col_offsets, row_indices, data and width, or one scipy sparse matrix")
+            co, ri = _u32(col_offsets), _u32(row_indices)
+            va = np.ascontiguousarray(data, dtype=np.float64)
+            width = int(co.size - 1 if width is None else width)
+            if co.size != width + 1:
+                raise ValueError("Vocabulary.apply: col_offsets needs width + 1 entries")
+            nnz = int(co[-1]) - int(co[0])
+            if ri.size < int(co[-1]) or va.size < int(co[-1]):
+                raise ValueError("Vocabulary.apply: row_indices and data are shorter than col_offsets says")
+            rc = L.lib().smk_vocabulary_apply(self._h, C.byref(o), width, nnz, co.ctypes.data_as(_up), ri.ctypes.data_as(_up),
+                                              va.ctypes.data_as(C.POINTER(C.c_double)), C.byref(h))
+            where = "smk_vocabulary_apply"
+        if rc not in (L.OK, L.FAILURE):
+            L.check(rc, where)
+        return PreprocessResult(h, rc)
+
+    def close(self):
+        if self._h:
+            L.lib().smk_vocabulary_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _write_strings(path, strings, indices, n):
@@ -174,6 +304,12 @@ class Preprocessor:
         if self._res is None:
             raise RuntimeError("preprocess() has not produced a result")
         return self._res.matrix()
+
+    def vocabulary(self) -> Vocabulary:
+        """The fitted vocabulary of the last ``preprocess()``, for documents that arrive later (``Vocabulary.apply``)."""
+        if self._res is None:
+            raise RuntimeError("preprocess() has not produced a result")
+        return self._res.vocabulary()
 
     def write_output(self, matrix_filepath, dict_filepath, docs_filepath, precision=4):
         self._res.write_mtx(matrix_filepath, precision)
