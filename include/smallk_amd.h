@@ -277,6 +277,36 @@ int smk_solver_set_factors_nndsvd(smk_solver* s, const smk_svd_options* opts, in
  * and the host time those decompositions took (tools/svd_rate.py) */
 int smk_svd_last_profile(int* host_trips, double* host_ms);
 
+/* ---- regularised NMF by cyclic coordinate descent: scikit-learn's solver="cd" without the shuffle, on the device -----------------
+ * Minimises  1/2 ||A - W H||_F^2 + n alpha_w rho ||W||_1 + m alpha_h rho ||H||_1 + 1/2 n alpha_w (1 - rho) ||W||_F^2
+ *            + 1/2 m alpha_h (1 - rho) ||H||_F^2                  (A m x n, W m x k, H k x n, rho = l1_ratio)
+ * which is sklearn.decomposition.NMF on X = A' with alpha_W = alpha_h, alpha_H = alpha_w, W_sklearn = H', components_ = W'.
+ * One iteration sweeps H (G = W'W, R = W'A), then W with the new H (G = HH', R = (AH')'), every coordinate in order; its violation
+ * is the sum of |projected gradient| over both sweeps.  Stop when violation_init (that of iteration 1) is 0 or
+ * violation / violation_init <= tol, else after max_iter iterations.  No normalisation.  update_w = 0: W stays as given, W'W and
+ * W'A are formed once and only the H sweep repeats (fold-in of new columns).  fp64 against the stored values of A (dense: the
+ * accurate-form product); the same bits on every call.  The host reads the violation once per iteration.
+ * SMK_BAD_PARAM: a null pointer, k < 1, k > min(m, n), a negative alpha, l1_ratio outside [0, 1], tol < 0, max_iter < 1, a bad
+ * view.  SMK_UNSUPPORTED: k > 128, a column shard, a single-copy dense matrix (its transpose is NOT built behind the caller's
+ * back).  On an error W and H are untouched. */
+typedef struct smk_cd_options { double alpha_w, alpha_h, l1_ratio, tol; int max_iter; int update_w; } smk_cd_options;
+typedef struct smk_cd_stats   { int iterations; int converged; double violation_init, violation; } smk_cd_stats;
+/* W (m x k) and H (k x ncols) are in/out views in device memory (SMK_DT_F64 / SMK_DT_F32, strides in elements, the caller's stream) */
+int smk_nmf_cd_device(const smk_matrix* a, int k, const smk_cd_options* o, void* W, int dtW, int64_t rsW, int64_t csW,
+                      void* H, int dtH, int64_t rsH, int64_t csH, void* stream, smk_cd_stats* stats);
+/* one sweep by itself, host fp64 arrays, as smk_nnls_blockpivot stands by itself: G k x k (G[t, r] at G[r * ldG + t]), R k x ncols,
+ * X k x ncols in/out, column-major; for every column and t = 0 .. k-1 in order, with G' = G + l2 I and R' = R - l1:
+ * grad = sum_r G'[t, r] x[r] - R'[t]; *violation += |x[t] == 0 ? min(0, grad) : grad|; x[t] = max(x[t] - grad / G'[t, t], 0)
+ * unless G'[t, t] == 0.  k <= 128. */
+int smk_cd_sweep(int k, int64_t ncols, const double* G, int64_t ldG, const double* R, int64_t ldR, double* X, int64_t ldX,
+                 double l1, double l2, double* violation);
+/* diagnostics of the calling thread's last smk_nmf_cd_device call: passes over A and sweeps launched */
+int smk_cd_last_profile(int* products, int* sweeps);
+/* measurement (tools/cd_rate.py): the average time in ms of `reps` launches of one sweep kernel on synthetic data, k x ncols, R
+ * read as `slabs` partial products.  which: 0 the coordinate-descent sweep, 1 its maintained-gradient form, 2 the HALS H sweep,
+ * 3 the reduction of the partial products alone.  *checksum: the violation of the last launch (which 0 / 1), else 0. */
+int smk_cd_sweep_time(int which, int k, int64_t ncols, int slabs, int reps, double* ms, double* checksum);
+
 /* ---- labels, memberships, top terms and fold-in, on the device (the device twins of smk_compute_assignments,
  * smk_compute_fuzzy_assignments and smk_top_terms below: the same comparisons in the same order, so the same integers and the
  * same membership bits; no k <= n and no height >= width requirement) -----------------------------------------------------

@@ -492,6 +492,16 @@ int sum_entries_blocks(i64 cols);
 int launch_sum_entries_dense(const void* A, int storage, i64 ld, i64 rows, i64 cols, double* part, double* out, hipStream_t st);
 int launch_sum_entries_sparse(const double* val, i64 nnz, double* part, double* out, hipStream_t st);
 
+// cd.hip: one sweep of cyclic coordinate descent over the columns of X (KP x N, pitch KP = kp_of(k), k <= 128) for
+// G' = G + l2 I (G: KP x KP, pitch KP) and R' = R - l1; the violation of the sweep as cd_sweep_blocks(k, N) partial sums in
+// viol_partials.  Rows >= k of X, G and R are not relied on; X's are written as zeros.  maintained != 0: the maintained-gradient
+// form of the inner loop (takes G as symmetric).  launch_cd_violation: out[0] (and host_out[0] when not null, pinned host
+// memory) = the sum of n partials.  Fixed summation orders throughout: the same bits on every run.
+int cd_sweep_blocks(int k, i64 N);
+int launch_cd_sweep(double* X, int k, i64 N, PartialView R, const double* G, double l1, double l2, double* viol_partials, hipStream_t st,
+                    int maintained = 0);
+int launch_cd_violation(const double* partials, int n, double* out, double* host_out, hipStream_t st);
+
 // assign.hip: labels / memberships of the columns of H and the top terms of the columns of W, the factors fp64 or fp32 (DT_*) in
 // their k-contiguous layout: column c of H at H + c * ldc, row i of W at W + i * ld (elements).  The host functions' comparisons in
 // the host functions' order: the same integers, the same membership bits.  memb: k * n floats (document c at c * k) or null.

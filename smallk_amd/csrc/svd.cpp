@@ -6,6 +6,7 @@
 // and is released on every path; no field of the matrix handle and no buffer of a solver is written here (the solver entry
 // hands its finished start to smk_solver_set_factors_device).
 #include "state.h"
+#include "factor_product.h"
 #include "svd_host.h"
 
 #include <cmath>
@@ -23,10 +24,9 @@ struct SvdRun {
     hipStream_t st = nullptr;
     Owned* own = nullptr;
     double *Fm = nullptr, *Fn = nullptr;          // the two factors: KP x m and KP x n
-    double *G = nullptr, *gscratch = nullptr, *Md = nullptr, *P = nullptr, *pieces[2] = {nullptr, nullptr};
+    double *G = nullptr, *gscratch = nullptr, *Md = nullptr;
     double* Gp = nullptr;                         // Gram partials left by the fused apply (null: this padded rank has none)
-    BigProdPlan over_m[2], over_n[2];             // dense: the contraction runs over the rows of A (B = A) / over its columns (B = A')
-    int ng = 0;
+    FactorProduct fp;                             // the passes over A (factor_product.h)
     std::vector<double> hG, lambda, E, M;
     int host_trips = 0;
     double host_us = 0.0;                         // the host's own work in those trips (eigendecomposition + M), without the copies
@@ -49,62 +49,16 @@ static int svd_alloc(SvdRun& r)
     const int fused = svd_apply_gram_blocks(r.KP, a->m > a->n ? a->m : a->n, ctx().cus);
     if (!rc && fused > 0) rc = own.dev(&r.Gp, (size_t)fused * kk);
     if (rc) { set_error("svd: no memory for the factor workspace"); return SMK_DEVICE_ERROR; }
-    if (!a->sparse) {
-        // one P layout for both directions and all groups: KP doubles per column, so the summed product IS a factor
-        r.ng = plan_bigprod_groups(a->storage, r.l, a->m, a->n, NSPLIT_F64, ctx().cus, r.over_m);
-        const int ng2 = plan_bigprod_groups(a->storage, r.l, a->n, a->m, NSPLIT_F64, ctx().cus, r.over_n);
-        if (ng2 != r.ng || r.ng < 1 || r.ng > 2) { set_error("svd: unexpected product plan"); return SMK_FAILURE; }
-        size_t pe = 0;
-        for (BigProdPlan* pl : {r.over_m, r.over_n})
-            for (int g = 0; g < r.ng; ++g) {
-                pl[g].ldx = r.KP;
-                pl[g].pstride = r.KP;
-                pl[g].p_elems = (size_t)pl[0].S * pl[0].ncols_pad * r.KP;
-                if (pl[g].p_elems > pe) pe = pl[g].p_elems;
-            }
-        if (own.dev(&r.P, pe)) { set_error("svd: no memory for the partial products"); return SMK_DEVICE_ERROR; }
-        SMK_HIP(hipMemsetAsync(r.P, 0, pe * sizeof(double), r.st));      // rows of P no group writes (l <= 96 in a 128-row column) stay zero
-    } else {
-        ensure_seg_plans(a);             // read-only use, as the residual
-        const SegPlan* sp[2] = {&a->segA, &a->segAt};
-        for (int i = 0; i < 2; ++i)
-            if (sp[i]->rowflag && sp[i]->npieces > 0 && own.dev(&r.pieces[i], (size_t)sp[i]->npieces * 128)) {
-                set_error("svd: no memory for the long-column partial sums");
-                return SMK_DEVICE_ERROR;
-            }
-    }
-    return 0;
+    r.fp.a = a;
+    r.fp.l = r.l;
+    r.fp.KP = r.KP;
+    r.fp.st = r.st;
+    return factor_product_alloc(r.fp, own, "svd");
 }
 
 // over_rows: out (KP x n) = (A' X')' for X = KP x m, the contraction over the rows of A; else out (KP x m) = (A X')' for X = KP x n
-static int svd_product(SvdRun& r, bool over_rows, const double* X, double* out)
-{
-    const smk_matrix* a = r.a;
-    const i64 N = over_rows ? a->n : a->m;
-    if (!a->sparse) {
-        const BigProdPlan* pl = over_rows ? r.over_m : r.over_n;
-        for (int g = 0; g < r.ng; ++g) {
-            const int rc = over_rows ? launch_bigprod(pl[g], a->A, a->ldA, X + pl[g].k0, r.P + pl[g].k0, r.st)
-                                     : launch_bigprod(pl[g], a->At, a->ldAt, X + pl[g].k0, r.P + pl[g].k0, r.st);
-            if (rc < 0) return rc;
-        }
-        const PartialView pv{r.P, pl[0].S, (i64)pl[0].ncols_pad * r.KP, r.KP, 1};
-        return launch_reduce_partials(pv, r.l, 0, N, out, 1, r.st);
-    }
-    // sparse: column j of the output gathers the rows of X named by column j of CSC(A) (over_rows) or of CSC(A')
-    const i64* colptr = over_rows ? a->colptr : a->colptr_t;
-    const unsigned* rowidx = over_rows ? a->rowidx : a->rowidx_t;
-    const double* val = over_rows ? a->val : a->val_t;
-    const SegPlan& seg = over_rows ? a->segA : a->segAt;
-    int rc;
-    if (r.l > 2 && seg.rowflag && seg.ncols == N && !seg.uniform)
-        rc = launch_spmm_seg(seg, colptr, val, X, r.l, out, r.KP, r.st, r.pieces[over_rows ? 0 : 1]);
-    else {
-        if (r.l <= 2) SMK_HIP(hipMemsetAsync(out, 0, (size_t)r.KP * N * sizeof(double), r.st));    // the rank-2 gather writes two rows
-        rc = launch_spmm_gather(colptr, rowidx, val, N, a->nnz, X, r.KP, r.l, out, r.KP, r.st);
-    }
-    return rc < 0 ? rc : 0;
-}
+// (factor_product.h: the product cd.cpp runs too)
+static int svd_product(SvdRun& r, bool over_rows, const double* X, double* out) { return factor_product(r.fp, over_rows, X, out); }
 
 // the Gram matrix of F (KP x N) -> host -> eigendecomposition (r.lambda, r.E).  partials > 0: the fused apply has left that many
 // partial sums of it in r.Gp, F is not read.

@@ -760,6 +760,76 @@ def transform(A, W, *, H0=None):
         solver.close()
 
 
+@dataclass
+class CdResult:
+    """What ``nmf_cd`` returns: the factors (numpy arrays, or torch tensors on the GPU when the start was tensors), the iterations
+    run (sklearn's ``n_iter_``), whether the stopping rule ended them, and the violation of iteration 1 and of the last one."""
+    W: object
+    H: object
+    n_iter: int
+    converged: bool
+    violation_init: float
+    violation: float
+
+
+def nmf_cd(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True, inplace=False) -> CdResult:
+    """Regularised NMF by cyclic coordinate descent -- scikit-learn's ``solver="cd"`` with ``shuffle=False`` -- on a resident
+    ``DenseMatrix`` / ``SparseMatrix`` A (m, n), from the start W0 (m, k), H0 (k, n): both numpy arrays, or both float64 / float32
+    torch tensors in GPU memory (any strides).  Minimises
+
+        1/2 ||A - W H||_F^2 + n alpha_W l1_ratio ||W||_1 + m alpha_H l1_ratio ||H||_1
+                            + 1/2 n alpha_W (1 - l1_ratio) ||W||_F^2 + 1/2 m alpha_H (1 - l1_ratio) ||H||_F^2
+
+    which is ``sklearn.decomposition.NMF`` on X = A' with sklearn's ``alpha_W`` = this ``alpha_H`` and its ``alpha_H`` = this
+    ``alpha_W``, W_sklearn = H' and ``components_`` = W'.  ``alpha_H="same"`` takes ``alpha_W``.  ``update_W=False``: W stays, only H is
+    fitted (fold-in).  The start is not modified unless ``inplace`` (tensors only): then W0 / H0 receive the result."""
+    if not isinstance(A, DenseMatrix):
+        raise ValueError(f"nmf_cd: A must be a resident DenseMatrix / SparseMatrix, got {type(A).__name__}")
+    on_device, k = _residual_factors(W0, H0, A.height, A.ncols, "nmf_cd")
+    if inplace and not on_device:
+        raise ValueError("nmf_cd: inplace needs torch tensors")
+    import torch
+    if alpha_H == "same":
+        alpha_H = alpha_W
+    o = L.CdOptions(float(alpha_W), float(alpha_H), float(l1_ratio), float(tol), int(max_iter), int(bool(update_W)))
+    if on_device:
+        W, H = (W0, H0) if inplace else (W0.clone(), H0.clone())
+    else:
+        dev = torch.device("cuda", L.lib().smk_current_device())
+        W = torch.from_numpy(np.ascontiguousarray(W0, dtype=np.float64)).to(dev)
+        H = torch.from_numpy(np.ascontiguousarray(H0, dtype=np.float64)).to(dev)
+    wp, wt, (wrs, wcs) = _tensor_view(W, "nmf_cd(W0)", kinds="factor")
+    hp, ht, (hrs, hcs) = _tensor_view(H, "nmf_cd(H0)", kinds="factor")
+    st = L.CdStats()
+    L.check(L.lib().smk_nmf_cd_device(A._h, k, C.byref(o), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), C.byref(st)),
+            "smk_nmf_cd_device")
+    if not on_device:
+        W, H = W.cpu().numpy(), H.cpu().numpy()
+    return CdResult(W, H, st.iterations, bool(st.converged), st.violation_init, st.violation)
+
+
+def cd_last_profile():
+    """(passes over A, sweeps launched) of this thread's last ``nmf_cd``"""
+    p, s = C.c_int(0), C.c_int(0)
+    L.check(L.lib().smk_cd_last_profile(C.byref(p), C.byref(s)), "smk_cd_last_profile")
+    return p.value, s.value
+
+
+def cd_sweep(G, R, X, l1=0.0, l2=0.0):
+    """One coordinate-descent sweep on the device, by itself (``smk_cd_sweep``): G (k, k), R (k, ncols), X (k, ncols) numpy
+    arrays.  For every column x and t = 0 .. k-1 in order, with G' = G + l2 I and R' = R - l1: grad = G'[t] . x - R'[t],
+    the violation grows by |min(0, grad)| where x[t] == 0 and by |grad| elsewhere, x[t] = max(x[t] - grad / G'[t, t], 0) unless
+    G'[t, t] == 0.  Returns (X_new, violation); X is not modified."""
+    G, R = _f(G), _f(R)
+    X = _f(X).copy(order="F")
+    k, ncols = R.shape
+    if G.shape != (k, k) or X.shape != (k, ncols):
+        raise ValueError(f"cd_sweep: G {G.shape} / R {R.shape} / X {X.shape} do not match (k, k) / (k, ncols) / (k, ncols)")
+    v = C.c_double(0)
+    L.check(L.lib().smk_cd_sweep(k, ncols, _p(G), k, _p(R), k, _p(X), k, float(l1), float(l2), C.byref(v)), "smk_cd_sweep")
+    return X, v.value
+
+
 def nnls_blockpivot(LHS, RHS, Xinit):
     """``NnlsBlockpivot`` (common/include/nnls.hpp:144-244) on the device, by itself.
 
