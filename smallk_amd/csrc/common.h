@@ -34,8 +34,7 @@ constexpr int MAX_K_BPP = MAX_K;               // block pivoting: the Gram-inver
                                                // KP = 2048: (num_cus x workgroups per CU + 2) x KP^2 doubles = about 8.6 GB per solver (nnls_wide_scratch_elems)
 constexpr int MAX_GROUPS = MAX_K / 64;         // the streaming product takes 64 factor rows per pass over A
 inline bool is_wide(int k) { return k > 128; }
-// block pivoting takes the tile kernels of wide.hip (and their scratch layout) from this rank on: everything above 128, and
-// k in (64, 128] unless SMK_NNLS_TILE128=0 asks for nnls_bpp_inv128_kernel
+// block pivoting takes the tile kernels of wide.hip (and their scratch layout) from this rank on: k > 64
 bool nnls_uses_tiles(int k);
 // devmem.cpp: hipMalloc / hipFree with a per-device cache of freed blocks (solver, subset and sort workspaces come and go per
 // node of a clustering run); dev_trim returns the current device's cached blocks to the runtime
@@ -308,7 +307,7 @@ int launch_hals_w_update(double* Wt, int k, i64 M, PartialView R, const double* 
 int hals_w_scratch_init(double* scratch, int k, i64 M, hipStream_t st);
 size_t hals_w_scratch_elems(int k, i64 M);
 // BPP / NNLS block principal pivoting over all columns
-// scratch: nnls_scratch_elems(k) doubles (k > 32: inverse of G + path selector), may be NULL (slow path only)
+// scratch: nnls_scratch_elems(k) doubles (k in (16, 64]: inverse of G + path selector), may be NULL (slow path only)
 // gram_partials / gram_nblk (optional): k in (8, 16], all columns from 0, at most NNLS_GRAM_MAX workgroups: the launch also
 // leaves partial Gram matrices X X' of the solved columns ([*gram_nblk][16 * 16], for launch_gram_reduce); *gram_nblk = 0 otherwise
 constexpr int NNLS_GRAM_MAX = 1024;
@@ -340,19 +339,17 @@ struct NnlsRiders {
 int launch_nnls_bpp(double* X, double* Y, int k, i64 col_begin, i64 col_end, PartialView R, const double* G,
                     int* fail_flag, int iter_tag, double* scratch, int inverse_ready, int num_cus, hipStream_t st,
                     double* gram_partials = nullptr, int* gram_nblk = nullptr, const NnlsPack* pack = nullptr,
-                    unsigned* defer_ws = nullptr, const NnlsRiders* riders = nullptr);
+                    const NnlsRiders* riders = nullptr);
 // totals of a deferred check: out / host_out [0] = 0 (side 1: BPP's dual), [1] = sum of the n partials, [flag_slot] = the failure
 // flag if it names an iteration <= tag_limit (else "none"); also copies the kk doubles of G into snap_g (may be NULL)
 int launch_pg_defer_sum(const double* part, int n, double* out, double* host_out, const int* flag, int flag_slot, int tag_limit,
                         const double* G, double* snap_g, int kk, hipStream_t st, double host_tag = 0.0);
-// k in (32, 64]: work list of the four-columns-per-wave kernel (nnls_g16.hip), nnls_defer_elems(ncols) unsigneds per launch
-// in flight; without it launch_nnls_bpp keeps the wave-per-column kernel for every column
-inline size_t nnls_defer_elems(i64 ncols) { return (size_t)ncols + 4; }
+// k in (16, 32]: four columns per wave (nnls_g16.hip); 1: issued, and the launch solves by masked elimination itself when the
+// inverse was rejected / 0: not applicable (another rank, SMK_NNLS_G16=0) / < 0: error
 int launch_nnls_bpp_g16(double* X, double* Y, int k, i64 col_begin, i64 col_end, PartialView R, const double* G, const double* Ginv,
-                        const int* status, int* fail_flag, int iter_tag, unsigned* defer, int num_cus, hipStream_t st,
-                        unsigned long long* stats);
+                        const int* status, int* fail_flag, int iter_tag, int num_cus, hipStream_t st, unsigned long long* stats);
 unsigned long long* nnls_stats_ptr();
-// k > 32: the inverse of G into scratch, ahead of launch_nnls_bpp(..., inverse_ready = 1, ...) (any stream)
+// k in (16, 64]: the inverse of G into scratch, ahead of launch_nnls_bpp(..., inverse_ready = 1, ...) (any stream)
 int launch_gram_inverse(const double* G, int k, double* scratch, hipStream_t st);
 size_t nnls_scratch_elems(int k);
 // diagnostics: the 256 counters of nnls.hip (SMK_NNLS_STATS=1), -1 when the counters are off

@@ -19,7 +19,7 @@ namespace smk {
 // each: 113 us for k = 64, half of a block-pivoting iteration on an 8192 x 4096 matrix; now 47 us (k = 40: 83 -> 37 us;
 // profiles/r04_gram_inverse.txt).  The division is not what is left (rcp + Newton steps instead: 47.2 us): a step is an LDS
 // round trip, sixteen multiply-adds, the publication of the next row / column and a barrier.
-// Same operations in the same order as gram_inverse_kernel<64>: the result is bit-identical.
+// Same operations in the same order as the kernel with the run-time index (last in 97e83fd): the result is bit-identical.
 template <int KP>
 __device__ __forceinline__ void gram_inverse64_body(const double* __restrict__ G, int k, double* __restrict__ Ginv,
                                                     int* __restrict__ status, double* __restrict__ lds /* GRAM_INVERSE_LDS(KP) doubles, 16-byte aligned */)

@@ -62,91 +62,11 @@ __global__ __launch_bounds__(256, (KP == 64 ? 3 : 1)) void nnls_bpp_kernel(doubl
 // cheaper; both are the same "compact solve + accumulate" on (M, T, s) = (Ginv, Z, -v) or (G, F, r) with
 // t = min(|F|, |Z|) <= 32 rows in the first t lanes of the wave.  One wave per column; the set is
 // wave-uniform, so index lists, loop bounds and pivot broadcasts are scalar.
-// The inverse is taken only when every Gauss-Jordan pivot of G is positive and not tiny (gram_inverse_kernel
+// The inverse is taken only when every Gauss-Jordan pivot of G is positive and not tiny (gram_inverse64_kernel
 // sets status = 1); otherwise nnls_bpp_kernel<64> above runs and reproduces the reference's non-SPD failure.
 // --------------------------------------------------------------------------
-// Ginv = G^-1 (k x k live, 64 x 64 storage, pads zero) by in-place Gauss-Jordan, one workgroup of 256 threads:
-// thread (r, cq) keeps the 16 entries a[r][16 cq .. 16 cq + 15] in registers; per pivot only the pivot row and
-// column travel through LDS (double buffered: one barrier per step).  (KP = 64 runs gram_inverse64_kernel below: in this
-// form the compiler indexes a[] at run time for the pivot column and keeps it in scratch memory, 113 us at k = 64.)
+// Ginv = G^-1 (k x k live, KP x KP storage, pads zero) by in-place Gauss-Jordan, one workgroup of 256 threads.
 // status = 1 when every pivot p_j satisfies p_j > 1e-9 * G[j][j] (SPD and usable), else 0.
-template <int KP>
-__global__ __launch_bounds__(256) void gram_inverse_kernel(const double* __restrict__ G, int k,
-                                                           double* __restrict__ Ginv, int* __restrict__ status)
-{
-    static_assert(KP == 64 || KP == 128, "256 threads x (KP * KP / 256) entries");
-    constexpr int CQ = 256 / KP;                 // threads per matrix row
-    constexpr int EPT = KP / CQ;                 // entries per thread: a[r][EPT cq .. EPT cq + EPT - 1]
-    __shared__ __attribute__((aligned(16))) double rowj[2][KP];
-    __shared__ double colj[2][KP];
-    __shared__ double diag0[KP];
-    __shared__ int bad;
-    const int tid = threadIdx.x;
-    const int r = tid / CQ, cq = tid % CQ;
-    if (tid == 0) bad = 0;
-    if (tid < KP) diag0[tid] = (tid < k) ? G[tid * KP + tid] : 1.0;
-    double a[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-        const int c = cq * EPT + e;
-        a[e] = (r < k && c < k) ? G[c * KP + r] : ((r == c) ? 1.0 : 0.0);
-    }
-    auto publish = [&](int j) {                 // row j and column j of the current matrix -> LDS buffer j & 1
-        const int buf = j & 1, jq = j / EPT, je = j % EPT;
-        if (r == j) {
-#pragma unroll
-            for (int e = 0; e < EPT; ++e) rowj[buf][cq * EPT + e] = a[e];
-        }
-        if (cq == jq) {
-            double v = a[0];
-#pragma unroll
-            for (int e = 1; e < EPT; ++e) v = (e == je) ? a[e] : v;
-            colj[buf][r] = v;
-        }
-    };
-    publish(0);
-    __syncthreads();
-    for (int j = 0; j < k; ++j) {
-        const int buf = j & 1;
-        const double piv = rowj[buf][j];
-        if (tid == 0 && !(piv > 1.0e-9 * diag0[j])) bad = 1;
-        const double ip = 1.0 / piv;
-        const double f = colj[buf][r] * ip;
-#pragma unroll
-        for (int e = 0; e < EPT; e += 2) {
-            const f64x2_t rr = *(const f64x2_t*)&rowj[buf][cq * EPT + e];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int c = cq * EPT + e + u;
-                double val;
-                if (r == j) val = (c == j) ? ip : rr[u] * ip;
-                else val = (c == j) ? -f : __builtin_fma(-f, rr[u], a[e + u]);
-                a[e + u] = val;
-            }
-        }
-        if (j + 1 < k) publish(j + 1);
-        __syncthreads();
-    }
-    // symmetrise: write the matrix out, then average each entry with its transposed partner
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-        const int c = cq * EPT + e;
-        Ginv[c * KP + r] = (r < k && c < k) ? a[e] : 0.0;
-    }
-    __syncthreads();
-    __threadfence_block();
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) {
-        const int c = cq * EPT + e;
-        const double up = Ginv[c * KP + r], lo = Ginv[r * KP + c];
-        a[e] = 0.5 * (up + lo);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) Ginv[(cq * EPT + e) * KP + r] = a[e];
-    if (tid == 0) *status = bad ? 0 : 1;
-}
-
 // (the elimination itself: gram_inverse.h -- it also rides in the sparse product launch)
 template <int KP>
 __global__ __launch_bounds__(256) void gram_inverse64_kernel(const double* __restrict__ G, int k, double* __restrict__ Ginv,
@@ -156,7 +76,7 @@ __global__ __launch_bounds__(256) void gram_inverse64_kernel(const double* __res
     gram_inverse64_body<KP>(G, k, Ginv, status, lds);
 }
 
-template <int KP, int NT, int WPS, bool FINE = true>
+template <int KP, int NT, int WPS>
 __global__ __launch_bounds__(NT, WPS) void nnls_bpp_inv_kernel(double* __restrict__ X, double* __restrict__ Y, int k, i64 N,
                                                           PartialView R, const double* __restrict__ G,
                                                           const double* __restrict__ Ginv,
@@ -168,8 +88,11 @@ __global__ __launch_bounds__(NT, WPS) void nnls_bpp_inv_kernel(double* __restric
     static_assert(KP == 64 || KP == 32, "one wave per column, one lane per component");
     constexpr int NW = NT / 64;
     if (*status == 0) return;
-    // worklist != nullptr: only the columns nnls_bpp_g16_kernel handed over (worklist[0] of them, col_begin + worklist[1 + i]);
-    // usually few or none, so the count is read before the matrices are copied
+    // worklist != nullptr: only the columns of a work list (worklist[0] of them, col_begin + worklist[1 + i]); the count is read
+    // before the matrices are copied.  Its one producer, the four-columns-per-wave kernel at KP = 64, was removed after 97e83fd
+    // and launch_nnls_bpp passes nullptr.  The walk through the list stays on purpose: with the plain column walk in its place
+    // the KP = 64 instance goes from 127 to 128 VGPRs and from 148 to 156 bytes of scratch per lane, and its launches measure
+    // 2 - 10 % longer (16384 x 8192, k = 64: 2.07 -> 2.14 ms over twelve iterations; profiles/variant_cut_ab.txt)
     const i64 nwork = worklist ? (i64)worklist[0] : 0;
     if (worklist && (i64)blockIdx.x * NW >= nwork) return;
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -303,15 +226,15 @@ __global__ __launch_bounds__(NT, WPS) void nnls_bpp_inv_kernel(double* __restric
             const double sc = (lane < t) ? sv[tl] : 0.0;
             const double base = comp ? v : -rhs;
             double u = 0.0, out;
-            // the elimination costs ~TB^2 / 2 broadcast + FMA pairs: bounds in steps of 4 (FINE) waste a quarter less
+            // the elimination costs ~TB^2 / 2 broadcast + FMA pairs: bounds in steps of 4 waste a quarter less
             // than steps of 8 on the |Z| = 6 .. 20 of noise-like data
-            if (FINE && t <= 4) out = compact(std::integral_constant<int, 4>{}, M, t, tl, sc, base, u);
+            if (t <= 4) out = compact(std::integral_constant<int, 4>{}, M, t, tl, sc, base, u);
             else if (t <= 8) out = compact(std::integral_constant<int, 8>{}, M, t, tl, sc, base, u);
-            else if (FINE && t <= 12) out = compact(std::integral_constant<int, 12>{}, M, t, tl, sc, base, u);
+            else if (t <= 12) out = compact(std::integral_constant<int, 12>{}, M, t, tl, sc, base, u);
             else if (t <= 16) out = compact(std::integral_constant<int, 16>{}, M, t, tl, sc, base, u);
-            else if (FINE && t <= 20) out = compact(std::integral_constant<int, 20>{}, M, t, tl, sc, base, u);
+            else if (t <= 20) out = compact(std::integral_constant<int, 20>{}, M, t, tl, sc, base, u);
             else if (t <= 24) out = compact(std::integral_constant<int, 24>{}, M, t, tl, sc, base, u);
-            else if (FINE && t <= 28) out = compact(std::integral_constant<int, 28>{}, M, t, tl, sc, base, u);
+            else if (t <= 28) out = compact(std::integral_constant<int, 28>{}, M, t, tl, sc, base, u);
             else out = compact(std::integral_constant<int, 32>{}, M, t, tl, sc, base, u);
             // u back to component positions
             if (lane < t) sv[tl] = u;
@@ -359,183 +282,14 @@ __global__ __launch_bounds__(NT, WPS) void nnls_bpp_inv_kernel(double* __restric
     if (failed_any && lane == 0) atomicMin(fail_flag, iter_tag);
 }
 
-// k in (64, 128]: the same algorithm with two components per lane (lane i owns i and 64 + i), passive sets as two
-// 64-bit words, Ginv (128 KiB) in LDS and G read through the caches (it is needed only by the direct form, i.e. for
-// solutions with more zeros than positives).  The compact dimension min(|F|, |Z|) is at most 64 = one row per lane.
-// There is no masked Gauss-Jordan fallback at this width: a Gram matrix that is not (numerically) positive definite
-// reports failure for the whole launch -- the reference fails only when a passive block it actually meets is not
-// SPD (normal_eq.hpp:35-50), which for a rank-deficient factor is the usual case.
-template <int NT>
-__global__ __launch_bounds__(NT) void nnls_bpp_inv128_kernel(double* __restrict__ X, double* __restrict__ Y, int k, i64 N,
-                                                             PartialView R, const double* __restrict__ G,
-                                                             const double* __restrict__ Ginv,
-                                                             const int* __restrict__ status,
-                                                             int* __restrict__ fail_flag, int iter_tag, i64 col_begin)
-{
-    constexpr int KP = 128;
-    constexpr int NW = NT / 64;
-    if (*status == 0) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicMin(fail_flag, iter_tag);
-        return;
-    }
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    double* gis = lds;                              // gis[c*KP + i] = Ginv[i][c]
-    for (int t = threadIdx.x; t < KP * KP; t += NT) gis[t] = Ginv[t];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double* sv = lds + KP * KP + wave * (KP + KP / 2);          // wave-private: 128 doubles of values
-    int* sidx = (int*)(sv + KP);                                //               128 ints of indices
-    __syncthreads();
-
-    const int k1 = k - 64;                                       // live components in the upper word (k > 64 here)
-    const unsigned long long m0 = ~0ull, m1 = (k1 >= 64) ? ~0ull : ((1ull << k1) - 1ull);
-    const bool ok0 = true, ok1 = lane < k1;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const int max_iter = 5 * k;
-    int failed_any = 0;
-
-    for (i64 col = col_begin + (i64)blockIdx.x * NW + wave; col < N; col += (i64)gridDim.x * NW) {
-        const double r0 = rhs_elem(R, col, lane), r1 = ok1 ? rhs_elem(R, col, 64 + lane) : 0.0;
-        double x0 = X[col * KP + lane], x1 = ok1 ? X[col * KP + 64 + lane] : 0.0;
-        double y0 = 0.0, y1 = 0.0;
-        unsigned long long F0 = __ballot(ok0 && x0 > 0.0) & m0, F1 = __ballot(ok1 && x1 > 0.0) & m1;
-
-        sv[lane] = r0;
-        sv[64 + lane] = r1;
-        double v0 = 0.0, v1 = 0.0;
-#pragma unroll 4
-        for (int c = 0; c < KP; c += 2) {
-            const f64x2_t rr = *(const f64x2_t*)(sv + c);
-            v0 = __builtin_fma(gis[c * KP + lane], rr[0], v0);
-            v1 = __builtin_fma(gis[c * KP + 64 + lane], rr[0], v1);
-            v0 = __builtin_fma(gis[(c + 1) * KP + lane], rr[1], v0);
-            v1 = __builtin_fma(gis[(c + 1) * KP + 64 + lane], rr[1], v1);
-        }
-
-        int failed = 0;
-        auto compact = [&](auto tb_tag, const double* M, int t, int tl, double sc, double b0, double b1, double& u_out,
-                           double& o0, double& o1) {
-            constexpr int TB = decltype(tb_tag)::value;
-            const bool live = lane < t;
-            double a[TB];
-#pragma unroll
-            for (int b = 0; b < TB; ++b) {
-                const int tb = __builtin_amdgcn_readlane(tl, b);
-                const double mv = M[tb * KP + tl];
-                a[b] = (live && b < t) ? mv : ((b == lane) ? 1.0 : 0.0);
-            }
-            double d = 1.0;
-#pragma unroll
-            for (int j = 0; j < TB; ++j) {
-                const double piv = readlane_f64(a[j], j);
-                if (!(piv > 0.0)) failed = 1;
-                const double ip = fast_rcp(piv);
-                if (lane == j) d = a[j];
-                const double f = (lane == j) ? 0.0 : a[j] * ip;
-#pragma unroll
-                for (int c = j + 1; c < TB; ++c) a[c] = __builtin_fma(-f, readlane_f64(a[c], j), a[c]);
-                sc = __builtin_fma(-f, readlane_f64(sc, j), sc);
-            }
-            const double u = live ? sc * fast_rcp(d) : 0.0;
-            o0 = b0;
-            o1 = b1;
-#pragma unroll
-            for (int b = 0; b < TB; ++b) {
-                const int tb = __builtin_amdgcn_readlane(tl, b);
-                const double ub = readlane_f64(u, b);
-                o0 = __builtin_fma(M[tb * KP + lane], ub, o0);
-                o1 = __builtin_fma(M[tb * KP + 64 + lane], ub, o1);
-            }
-            u_out = u;
-        };
-        auto solve = [&](unsigned long long Fa, unsigned long long Fb) {
-            const unsigned long long Za = ~Fa & m0, Zb = ~Fb & m1;
-            const int p = __popcll(Fa) + __popcll(Fb), q = __popcll(Za) + __popcll(Zb);
-            const bool inF0 = (Fa >> lane) & 1ull, inF1 = (Fb >> lane) & 1ull;
-            if (q == 0) { x0 = v0; x1 = v1; y0 = y1 = 0.0; return; }
-            if (p == 0) { x0 = x1 = 0.0; y0 = -r0; y1 = ok1 ? -r1 : 0.0; return; }
-            const bool comp = q <= p;
-            const unsigned long long Ta = comp ? Za : Fa, Tb = comp ? Zb : Fb;
-            const int t = comp ? q : p;
-            const double* M = comp ? gis : G;
-            const bool inT0 = (Ta >> lane) & 1ull, inT1 = (Tb >> lane) & 1ull;
-            const int rank0 = __popcll(Ta & below), rank1 = __popcll(Ta) + __popcll(Tb & below);
-            if (inT0) sidx[rank0] = lane;
-            if (inT1) sidx[rank1] = 64 + lane;
-            sv[lane] = comp ? -v0 : r0;
-            sv[64 + lane] = comp ? -v1 : r1;
-            const int tl = (lane < t) ? sidx[lane] : 0;
-            const double sc = (lane < t) ? sv[tl] : 0.0;
-            double u = 0.0, o0 = 0.0, o1 = 0.0;
-            const double b0 = comp ? v0 : -r0, b1 = comp ? v1 : -r1;
-            if (t <= 8) compact(std::integral_constant<int, 8>{}, M, t, tl, sc, b0, b1, u, o0, o1);
-            else if (t <= 16) compact(std::integral_constant<int, 16>{}, M, t, tl, sc, b0, b1, u, o0, o1);
-            else if (t <= 32) compact(std::integral_constant<int, 32>{}, M, t, tl, sc, b0, b1, u, o0, o1);
-            else compact(std::integral_constant<int, 64>{}, M, t, tl, sc, b0, b1, u, o0, o1);
-            if (lane < t) sv[tl] = u;
-            const double ut0 = inT0 ? sv[lane] : 0.0, ut1 = inT1 ? sv[64 + lane] : 0.0;
-            if (comp) { x0 = inF0 ? o0 : 0.0; x1 = inF1 ? o1 : 0.0; y0 = ut0; y1 = ut1; }
-            else      { x0 = ut0; x1 = ut1; y0 = !inF0 ? o0 : 0.0; y1 = (ok1 && !inF1) ? o1 : 0.0; }
-        };
-
-        solve(F0, F1);
-        auto sets = [&](unsigned long long& no0, unsigned long long& no1, unsigned long long& in0, unsigned long long& in1) {
-            const bool pa = (F0 >> lane) & 1ull, pb = (F1 >> lane) & 1ull;
-            no0 = __ballot(ok0 && !pa && (y0 < 0.0));
-            no1 = __ballot(ok1 && !pb && (y1 < 0.0));
-            in0 = __ballot(ok0 && pa && (x0 < 0.0));
-            in1 = __ballot(ok1 && pb && (x1 < 0.0));
-        };
-        unsigned long long no0, no1, in0, in1;
-        sets(no0, no1, in0, in1);
-        int ng = __popcll(no0) + __popcll(no1) + __popcll(in0) + __popcll(in1);
-        int Pc = 3, Ninf = k + 1;
-        int iter = 0;
-        while (ng > 0) {
-            if (iter >= max_iter) { failed = 1; break; }
-            if (ng < Ninf) { Pc = 3; Ninf = ng; F0 = (F0 | no0) & ~in0; F1 = (F1 | no1) & ~in1; }
-            else if (Pc >= 1) { Pc -= 1; F0 = (F0 | no0) & ~in0; F1 = (F1 | no1) & ~in1; }
-            else {
-                // backup rule: the largest index among the non-optimal / infeasible components changes sides
-                const unsigned long long hi = no1 | in1, lo = no0 | in0;
-                if (hi) F1 ^= 1ull << (63 - __clzll(hi));
-                else F0 ^= 1ull << (63 - __clzll(lo));
-            }
-            F0 &= m0;
-            F1 &= m1;
-            solve(F0, F1);
-            if (fabs(x0) < 1.0e-12) x0 = 0.0;
-            if (fabs(x1) < 1.0e-12) x1 = 0.0;
-            if (fabs(y0) < 1.0e-12) y0 = 0.0;
-            if (fabs(y1) < 1.0e-12) y1 = 0.0;
-            sets(no0, no1, in0, in1);
-            ng = __popcll(no0) + __popcll(no1) + __popcll(in0) + __popcll(in1);
-            ++iter;
-        }
-        if (fabs(x0) < 1.0e-12) x0 = 0.0;            // columns that never pivot are zeroized too (nnls_bpp_kernel's note)
-        if (fabs(x1) < 1.0e-12) x1 = 0.0;
-        if (fabs(y0) < 1.0e-12) y0 = 0.0;
-        if (fabs(y1) < 1.0e-12) y1 = 0.0;
-        X[col * KP + lane] = x0;
-        if (ok1) X[col * KP + 64 + lane] = x1;
-        if (Y) {
-            Y[col * KP + lane] = y0;
-            if (ok1) Y[col * KP + 64 + lane] = y1;
-        }
-        failed_any |= failed;
-    }
-    if (failed_any && lane == 0) atomicMin(fail_flag, iter_tag);
-}
-
 bool nnls_uses_tiles(int k)
 {
-    // default: from k = 65 (measured on 16384 x 8192, 12 iterations: k = 80 / 100 / 128 3.96 / 4.53 / 5.27 -> 2.39 / 2.84 / 3.12 ms per
-    // iteration against nnls_bpp_inv128_kernel); SMK_NNLS_TILE128=0 keeps that kernel, =2 also sends k in (32, 64] here (A/B)
-    const int level = sw::nnls_tile128();
-    return is_wide(k) || (level >= 1 && k > 64) || (level >= 2 && k > 32);
+    // from k = 65 (measured on 16384 x 8192, 12 iterations: k = 80 / 100 / 128 took 3.96 / 4.53 / 5.27 ms per iteration on the
+    // two-components-per-lane kernel that served k in (64, 128] before, 2.39 / 2.84 / 3.12 ms on the tile kernel)
+    return k > 64;
 }
 
-size_t nnls_scratch_elems(int k) { return (size_t)kp_of(k) * kp_of(k) + 8; }     // k <= 128; above: nnls_wide_scratch_elems
+size_t nnls_scratch_elems(int k) { return (size_t)kp_of(k) * kp_of(k) + 8; }     // k <= 64; above: nnls_wide_scratch_elems
 // k in (16, 32] also solves through the inverse of the Gram matrix (round 4; SMK_NNLS_INV32=0: the masked elimination, as before)
 // Workgroups of the inverse-based kernels = resident workgroups x rounds.  Every workgroup first copies G and Ginv into LDS (16 /
 // 64 KB) and a wave prefetches its next column, so few columns per wave waste both: one round up to 65536 columns (s_reuters 159 ->
@@ -552,28 +306,25 @@ bool nnls_inverse_at_32()
     return sw::nnls_inv32();
 }
 
-// k > 32: Ginv and the path selector into `scratch` (nnls_scratch_elems(k) doubles).  One workgroup, ~0.1 ms: the
+// k in (16, 64]: Ginv and the path selector into `scratch` (nnls_scratch_elems(k) doubles).  One workgroup, ~0.05 ms: the
 // solver runs it on a side stream beside the streaming product that separates the Gram matrix from its NNLS.
 int launch_gram_inverse(const double* G, int k, double* scratch, hipStream_t st)
 {
     const int KPv = kp_of(k);
-    if (KPv < 32 || KPv > 128 || !scratch) return 0;
+    if ((KPv != 32 && KPv != 64) || !scratch) return 0;
     if (KPv == 32 && !nnls_inverse_at_32()) return 0;
-    const bool old64 = sw::gram_inverse_old();
     if (KPv == 32) gram_inverse64_kernel<32><<<1, 256, 0, st>>>(G, k, scratch, (int*)(scratch + 32 * 32));
-    else if (KPv == 64 && !old64) gram_inverse64_kernel<64><<<1, 256, 0, st>>>(G, k, scratch, (int*)(scratch + 64 * 64));
-    else if (KPv == 64) gram_inverse_kernel<64><<<1, 256, 0, st>>>(G, k, scratch, (int*)(scratch + 64 * 64));
-    else gram_inverse_kernel<128><<<1, 256, 0, st>>>(G, k, scratch, (int*)(scratch + 128 * 128));
+    else gram_inverse64_kernel<64><<<1, 256, 0, st>>>(G, k, scratch, (int*)(scratch + 64 * 64));
     SMK_HIP(hipGetLastError());
     return 0;
 }
 
 // solves columns [col_begin, col_end) of X (col_end <= N); other columns are untouched.
-// `scratch`: nnls_scratch_elems(k) doubles (the inverse of G and the path selector for k > 32);
+// `scratch`: nnls_scratch_elems(k) doubles (the inverse of G and the path selector for k > 16);
 // inverse_ready != 0: launch_gram_inverse(G, ...) has already been ordered before this call.
 int launch_nnls_bpp(double* X, double* Y, int k, i64 col_begin, i64 col_end, PartialView R, const double* G,
                     int* fail_flag, int iter_tag, double* scratch, int inverse_ready, int num_cus, hipStream_t st,
-                    double* gram_partials, int* gram_nblk, const NnlsPack* pack, unsigned* defer_ws, const NnlsRiders* riders)
+                    double* gram_partials, int* gram_nblk, const NnlsPack* pack, const NnlsRiders* riders)
 {
     if (gram_nblk) *gram_nblk = 0;
     if (riders && riders->pg_nblk) *riders->pg_nblk = 0;
@@ -586,20 +337,6 @@ int launch_nnls_bpp(double* X, double* Y, int k, i64 col_begin, i64 col_end, Par
     const i64 N = col_end;
     const int inv_mode = sw::nnls_inv();
     const int* skip_if = nullptr;
-    if (KPv == 128) {
-        if (!scratch) { set_error("nnls: k > 64 needs the scratch buffer"); return -100; }
-        constexpr int NT = 1024;
-        double* Ginv = scratch;
-        int* status = (int*)(scratch + 128 * 128);
-        if (!inverse_ready) { int irc = launch_gram_inverse(G, k, scratch, st); if (irc) return irc; }
-        const int lds = (128 * 128 + (NT / 64) * (128 + 64)) * (int)sizeof(double);
-        SMK_HIP(hipFuncSetAttribute((const void*)nnls_bpp_inv128_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        i64 g2 = (ncols + NT / 64 - 1) / (NT / 64);
-        if (g2 > (i64)num_cus * 4) g2 = (i64)num_cus * 4;
-        nnls_bpp_inv128_kernel<NT><<<(unsigned)g2, NT, lds, st>>>(X, Y, k, N, R, G, Ginv, status, fail_flag, iter_tag, col_begin);
-        SMK_HIP(hipGetLastError());
-        return 0;
-    }
     if (KPv == 32 && inv_mode && scratch && nnls_inverse_at_32()) {
         // k in (16, 32]: the same kernel, one wave per column with its upper half idle.  The masked elimination costs a full
         // 32-step Gauss-Jordan per exchange and column (99 us per launch on 8192 x 4096 at k = 32, two thirds of the iteration);
@@ -612,11 +349,11 @@ int launch_nnls_bpp(double* X, double* Y, int k, i64 col_begin, i64 col_end, Par
         i64 g2 = (ncols + NT / 64 - 1) / (NT / 64);
         const i64 cap = (i64)num_cus * 2 * nnls_rounds(ncols);
         if (g2 > cap) g2 = cap;
-        // round 6: four columns per wave (nnls_g16.hip); SMK_NNLS_G16=0 keeps the wave-per-column kernel
-        const int g16 = launch_nnls_bpp_g16(X, Y, k, col_begin, col_end, R, G, Ginv, status, fail_flag, iter_tag, nullptr, num_cus, st, nnls_stats_ptr());
-        if (g16 < 0) return g16;
-        if (g16 == 2) return 0;                   // that launch solves by masked elimination itself when the inverse was rejected
-        if (g16 == 0) nnls_bpp_inv_kernel<32, 512, 4><<<(unsigned)g2, NT, lds, st>>>(X, Y, k, N, R, G, Ginv, status, fail_flag, iter_tag, col_begin, nnls_stats_ptr(), nullptr);
+        // round 6: four columns per wave (nnls_g16.hip), a launch that solves by masked elimination itself when the inverse was
+        // rejected; SMK_NNLS_G16=0 keeps the wave-per-column kernel
+        const int g16 = launch_nnls_bpp_g16(X, Y, k, col_begin, col_end, R, G, Ginv, status, fail_flag, iter_tag, num_cus, st, nnls_stats_ptr());
+        if (g16 != 0) return g16 < 0 ? g16 : 0;
+        nnls_bpp_inv_kernel<32, 512, 4><<<(unsigned)g2, NT, lds, st>>>(X, Y, k, N, R, G, Ginv, status, fail_flag, iter_tag, col_begin, nnls_stats_ptr(), nullptr);
         SMK_HIP(hipGetLastError());
         skip_if = status;
     }
@@ -624,30 +361,14 @@ int launch_nnls_bpp(double* X, double* Y, int k, i64 col_begin, i64 col_end, Par
         double* Ginv = scratch;
         int* status = (int*)(scratch + 64 * 64);
         if (!inverse_ready) { int irc = launch_gram_inverse(G, k, scratch, st); if (irc) return irc; }
-        // round 6: the columns whose exchanges stay at t <= 16 are solved four per wave (nnls_g16.hip); the others arrive here
-        // through the work list
-        const unsigned* worklist = nullptr;
-        if (defer_ws && inv_mode == 1) {
-            const int g16 = launch_nnls_bpp_g16(X, Y, k, col_begin, col_end, R, G, Ginv, status, fail_flag, iter_tag, defer_ws, num_cus, st, nnls_stats_ptr());
-            if (g16 < 0) return g16;
-            if (g16 > 0) worklist = defer_ws;
-        }
-        auto run = [&](auto kern, int NT, int wg_per_cu) -> int {
-            const int lds = (2 * 64 * 64 + (NT / 64) * 128) * (int)sizeof(double);
-            SMK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            i64 g2 = (ncols + NT / 64 - 1) / (NT / 64);
-            const i64 cap = (i64)num_cus * wg_per_cu * nnls_rounds(ncols);
-            if (g2 > cap) g2 = cap;
-            kern<<<(unsigned)g2, NT, lds, st>>>(X, Y, k, N, R, G, Ginv, status, fail_flag, iter_tag, col_begin, nnls_stats_ptr(), worklist);
-            SMK_HIP(hipGetLastError());
-            return 0;
-        };
-        int rc;
-        if (inv_mode == 2) rc = run(nnls_bpp_inv_kernel<64, 768, 3>, 768, 1);
-        else if (inv_mode == 3) rc = run(nnls_bpp_inv_kernel<64, 512, 2>, 512, 1);
-        else if (inv_mode == 4) rc = run(nnls_bpp_inv_kernel<64, 512, 4, false>, 512, 2);   // solve bounds in steps of 8 (A/B)
-        else rc = run(nnls_bpp_inv_kernel<64, 512, 4>, 512, 2);
-        if (rc) return rc;
+        constexpr int NT = 512;
+        const int lds = (2 * 64 * 64 + (NT / 64) * 128) * (int)sizeof(double);
+        SMK_HIP(hipFuncSetAttribute((const void*)nnls_bpp_inv_kernel<64, 512, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        i64 g2 = (ncols + NT / 64 - 1) / (NT / 64);
+        const i64 cap = (i64)num_cus * 2 * nnls_rounds(ncols);
+        if (g2 > cap) g2 = cap;
+        nnls_bpp_inv_kernel<64, 512, 4><<<(unsigned)g2, NT, lds, st>>>(X, Y, k, N, R, G, Ginv, status, fail_flag, iter_tag, col_begin, nnls_stats_ptr(), nullptr);
+        SMK_HIP(hipGetLastError());
         skip_if = status;
     }
     int grid1 = grid;

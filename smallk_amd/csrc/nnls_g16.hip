@@ -1,5 +1,5 @@
 // smallk_amd/csrc/nnls_g16.hip -- NnlsBlockpivot (nnls.hpp:144-244, src/nnls.cpp:18-74, nmf_solver_bpp.hpp:146-219) for
-// k in (16, 64] with FOUR columns per wave: a column per 16-lane DPP row (round 6).
+// k in (16, 32] with FOUR columns per wave: a column per 16-lane DPP row (round 6).
 //
 // Why: the wave-per-column kernel (nnls.hip: nnls_bpp_inv_kernel) is bound by VALU issue, not by memory or LDS -- counters on the
 // 10^6-column solves of `s_1m` (k = 32): 557 vector instructions per column, SQ_ACTIVE_INST_VALU = 97 % of the launch, 0.13 of the
@@ -10,11 +10,12 @@
 // apply: 33 - 100 % of the columns of a launch have a set of their own (profiles/r06_nnls_passive_sets.md).
 //
 // Here a 16-lane DPP row owns a column: lane l holds components l, l + 16, ... (E = KP / 16 of them), the compact system
-// (t <= 16 rows: t <= KP / 2 always, so every solve at KP = 32 and the t <= 16 ones at KP = 64) sits one row per lane of the
+// (t <= 16 rows: t <= KP / 2 always, so every solve at KP = 32) sits one row per lane of the
 // row, and pivot-row values travel by `v_mov_b64_dpp row_newbcast` -- one instruction per fp64 value, the one DPP control
-// gfx90a+ keeps for 64-bit data.  (Default at KP = 32; KP = 64 is selectable, SMK_NNLS_G16=2 -- see g16_level below.)  The four columns of a wave run the same unrolled elimination (bound TB = the largest t of the
-// four, rounded up to 4), each on its own system, form (complement on Ginv / direct on G) and state machine.  A column of KP = 64
-// whose exchange needs t > 16 is handed over untouched to the wave-per-column kernel through a work list.
+// gfx90a+ keeps for 64-bit data.  The four columns of a wave run the same unrolled elimination (bound TB = the largest t of the
+// four, rounded up to 2), each on its own system, form (complement on Ginv / direct on G) and state machine.
+// (The same kernel at KP = 64, where a column whose exchange needs t > 16 went to the wave-per-column kernel through a work list,
+// was built and measured a wash, and was removed after 97e83fd: DESIGN.md 5.3, profiles/r06_nnls_g16_k64.txt.)
 // Arithmetic and order of operations are those of nnls_bpp_inv_kernel (same compact elimination, same accumulation order of
 // Ginv r and of M[:, T] u): the results are bit-identical to that kernel's (tests/test_gpu_nnls.py compares them).
 #include "devutil.h"
@@ -55,31 +56,28 @@ __device__ __forceinline__ int row_bcast(int v, int J)
     }
 }
 
-template <int KP> struct G16Mask { typedef unsigned type; };
-template <> struct G16Mask<64> { typedef unsigned long long type; };
 __device__ __forceinline__ int g16_popc(unsigned m) { return __popc(m); }
-__device__ __forceinline__ int g16_popc(unsigned long long m) { return __popcll(m); }
 __device__ __forceinline__ int g16_top(unsigned m) { return m ? 31 - __clz((int)m) : 0; }
-__device__ __forceinline__ int g16_top(unsigned long long m) { return m ? 63 - __clzll((long long)m) : 0; }
 
 // S1: the right-hand side is one fp64 slab (every full-size launch: C4 whole, the sparse workloads), so the loads of the NEXT four
 // columns are issued before the current four are touched; otherwise the slabs are summed on arrival (rhs_elem's order)
-template <int KP, int NT, int WGS, bool S1, bool FINE = false>
-__global__ __launch_bounds__(NT, WGS) void nnls_bpp_g16_kernel(double* __restrict__ X, double* __restrict__ Y, int k, i64 N, PartialView R,
+// 256 threads, three workgroups per CU at <= 168 registers
+template <bool S1>
+__global__ __launch_bounds__(256, 3) void nnls_bpp_g16_kernel(double* __restrict__ X, double* __restrict__ Y, int k, i64 N, PartialView R,
                                                           const double* __restrict__ G, const double* __restrict__ Ginv,
                                                           const int* __restrict__ status, int* __restrict__ fail_flag, int iter_tag,
-                                                          i64 col_begin, unsigned* __restrict__ defer,
-                                                          unsigned long long* __restrict__ stats)
+                                                          i64 col_begin, unsigned long long* __restrict__ stats)
 {
-    static_assert(KP == 16 || KP == 32 || KP == 64, "a column per 16-lane row, KP / 16 components per lane");
-    constexpr int E = KP / 16;
+    constexpr int KP = 32;                                      // a column per 16-lane row, KP / 16 components per lane
+    constexpr int E = KP / 16;                                  // 2: the `E == 1` branches below never compile; there is no KP = 16 instance
+    constexpr int NT = 256;
     constexpr int NW = NT / 64;
-    typedef typename G16Mask<KP>::type mask_t;
+    typedef unsigned mask_t;                                    // bit c = component c of a column
     if (*status == 0) {
-        // the inverse is not usable: the masked elimination solves.  At KP = 32 with 256-thread workgroups it runs right here (the
-        // body of nnls_bpp_kernel<32>, nnls_masked.h) -- the decision is the device's, and a separate launch that returns at once
-        // in every ordinary run cost 4 - 6 us per solve (8 % of an iteration on the Reuters shape); otherwise that launch follows
-        if constexpr (KP == 32 && NT == 256) nnls_bpp_body<32>(X, Y, k, N, R, G, fail_flag, iter_tag, col_begin, nullptr, NnlsPack(), stats, NnlsRiders());
+        // the inverse is not usable: the masked elimination solves, right here (the body of nnls_bpp_kernel<32>, nnls_masked.h)
+        // -- the decision is the device's, and a separate launch that returns at once in every ordinary run cost 4 - 6 us per
+        // solve (8 % of an iteration on the Reuters shape)
+        nnls_bpp_body<32>(X, Y, k, N, R, G, fail_flag, iter_tag, col_begin, nullptr, NnlsPack(), stats, NnlsRiders());
         return;
     }
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -159,7 +157,6 @@ __global__ __launch_bounds__(NT, WGS) void nnls_bpp_g16_kernel(double* __restric
         mask_t F = group_mask(pr) & kmask;                      // passive_set = (X > 0), nnls.hpp:157
 
         bool have_v = false;                                    // wave-uniform
-        bool deferred = false;                                  // per column
         int failed = 0;
         int nsolve = 0;                                         // diagnostics only
 
@@ -260,9 +257,6 @@ __global__ __launch_bounds__(NT, WGS) void nnls_bpp_g16_kernel(double* __restric
                 nnls_stat(stats, q == 0 ? 179 : p == 0 ? 180 : comp ? 176 : 177);
             }
             ++nsolve;
-            if constexpr (KP == 64) {
-                if (t > 16) { deferred = true; act = false; t = 0; }           // this column goes to the wave-per-column kernel
-            }
             if (!have_v && __ballot(act && comp) != 0ull) need_v();
             // the largest compact system of the four columns bounds the unrolled elimination
             const int tmax = max(max(__builtin_amdgcn_readlane(t, 0), __builtin_amdgcn_readlane(t, 16)),
@@ -293,15 +287,15 @@ __global__ __launch_bounds__(NT, WGS) void nnls_bpp_g16_kernel(double* __restric
                 for (int e = 0; e < E; ++e) base[e] = comp ? v[e] : -rhs[e];
                 const int mbase = comp ? KP * KP : 0;
                 double u;
-                // bounds in steps of 2 (SMK_NNLS_G16_FINE=0: steps of 4): the elimination costs ~TB^2 / 2 broadcast + FMA pairs and the
-                // bound is the LARGEST system of the four columns
-                if (FINE && tmax <= 2) u = compact(std::integral_constant<int, 2>{}, mbase, t, tl, sc, base, out);
+                // bounds in steps of 2: the elimination costs ~TB^2 / 2 broadcast + FMA pairs and the bound is the LARGEST system
+                // of the four columns
+                if (tmax <= 2) u = compact(std::integral_constant<int, 2>{}, mbase, t, tl, sc, base, out);
                 else if (tmax <= 4) u = compact(std::integral_constant<int, 4>{}, mbase, t, tl, sc, base, out);
-                else if (FINE && tmax <= 6) u = compact(std::integral_constant<int, 6>{}, mbase, t, tl, sc, base, out);
+                else if (tmax <= 6) u = compact(std::integral_constant<int, 6>{}, mbase, t, tl, sc, base, out);
                 else if (tmax <= 8) u = compact(std::integral_constant<int, 8>{}, mbase, t, tl, sc, base, out);
-                else if (FINE && tmax <= 10) u = compact(std::integral_constant<int, 10>{}, mbase, t, tl, sc, base, out);
+                else if (tmax <= 10) u = compact(std::integral_constant<int, 10>{}, mbase, t, tl, sc, base, out);
                 else if (tmax <= 12) u = compact(std::integral_constant<int, 12>{}, mbase, t, tl, sc, base, out);
-                else if (FINE && tmax <= 14) u = compact(std::integral_constant<int, 14>{}, mbase, t, tl, sc, base, out);
+                else if (tmax <= 14) u = compact(std::integral_constant<int, 14>{}, mbase, t, tl, sc, base, out);
                 else u = compact(std::integral_constant<int, 16>{}, mbase, t, tl, sc, base, out);
                 // u back to component positions
                 __builtin_amdgcn_wave_barrier();
@@ -372,7 +366,7 @@ __global__ __launch_bounds__(NT, WGS) void nnls_bpp_g16_kernel(double* __restric
                 if (ng == 0) active = false;
             }
         }
-        if (col_ok && !deferred) {
+        if (col_ok) {
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 if (fabs(x[e]) < 1.0e-12) x[e] = 0.0;              // columns that never pivot are zeroized too (nnls_bpp_kernel's note)
@@ -385,73 +379,29 @@ __global__ __launch_bounds__(NT, WGS) void nnls_bpp_g16_kernel(double* __restric
             if (stats && l == 0) { nnls_stat(stats, iter < 15 ? iter : 15); nnls_stat(stats, 178); }
             failed_any |= failed;
         }
-        if constexpr (KP == 64) {
-            if (deferred && l == 0) defer[1 + atomicAdd(&defer[0], 1u)] = (unsigned)(col - col_begin);
-        }
     }
     if (failed_any && l == 0) atomicMin(fail_flag, iter_tag);
 }
 
-// SMK_NNLS_G16: 0 = off (a wave per column everywhere), 1 = k in (16, 32] (default), 2 = also k in (32, 64].
-// At KP = 64 the kernel is built and bit-identical but NOT the default: measured against the wave-per-column kernel on one box
-// (profiles/r06_nnls_g16_k64.txt) it gains 1.5 % on a C4 shard in steady state (W-side launch 460 -> 295 us), nothing on C4 whole or
-// on rank 0 of an emulated 8, and LOSES 2 % over the first twenty iterations of a cold start (every column's first exchange has
-// t ~ 26 > 16 and is handed over after a wasted first solve) and 5 - 10 % on 16384 x 8192 (three more launches per side on a
-// launch-bound iteration).
-static int g16_level()
-{
-    return sw::nnls_g16();
-}
-
-// the four-columns-per-wave launch; returns 1 when it was issued, 2 when it was issued AND carries the masked-elimination fallback
-// itself (no separate fallback launch needed) (0: not applicable, < 0: error).  KP = 64: `defer` receives the
-// columns that must still be solved by nnls_bpp_inv_kernel (defer[0] = count, zeroed here; defer[1 ..] = column - col_begin)
+// The four-columns-per-wave launch for k in (16, 32]; SMK_NNLS_G16=0 switches it off (a wave per column, nnls.hip).  Returns 1 when
+// it was issued -- it carries the masked-elimination fallback itself, no launch follows -- 0 when not applicable, < 0 on an error.
+// Launch shape (A/B on `s_1m`, it/s on one box): 256 threads x 3 workgroups per CU with elimination bounds in steps of 2: 441; the
+// same with bounds in steps of 4: 428; 512 threads at <= 128 registers (144 bytes of scratch per lane): 395; 512 threads, two
+// waves per SIMD: 408.  The three losing shapes were removed after 97e83fd.
 int launch_nnls_bpp_g16(double* X, double* Y, int k, i64 col_begin, i64 col_end, PartialView R, const double* G, const double* Ginv,
-                        const int* status, int* fail_flag, int iter_tag, unsigned* defer, int num_cus, hipStream_t st,
-                        unsigned long long* stats)
+                        const int* status, int* fail_flag, int iter_tag, int num_cus, hipStream_t st, unsigned long long* stats)
 {
-    const int KPv = kp_of(k);
-    if (g16_level() < 1 || (KPv != 32 && KPv != 64)) return 0;
-    if (KPv == 64 && (g16_level() < 2 || !defer)) return 0;
+    if (!sw::nnls_g16() || kp_of(k) != 32) return 0;
     const i64 ncols = col_end - col_begin;
     if (ncols <= 0) return 0;
-    const bool s1 = R.S == 1 && R.f64;
+    constexpr int NT = 256;
+    const int lds = (2 * 32 * 32 + (NT / 64) * 4 * 48) * (int)sizeof(double);
     const i64 nquads = (ncols + 3) / 4;
-    const int wgs = sw::nnls_g16_wgs();
-    if (KPv == 32) {
-        // shapes (SMK_NNLS_G16_SHAPE, A/B; s_1m it/s on one box): 3 = 256 threads, three workgroups per CU at <= 168 registers (no
-        // spills), elimination bounds in steps of 2 (default: 441); 0 = the same with bounds in steps of 4 (428); 1 = 512 threads at
-        // <= 128 registers (four waves per SIMD, 144 bytes of scratch per lane: 395); 2 = 512 threads, two waves per SIMD (408)
-        const int shape = sw::nnls_g16_shape();
-        auto run = [&](auto kern, int NT, int wg_per_cu) -> int {
-            const int lds = (2 * 32 * 32 + (NT / 64) * 4 * 48) * (int)sizeof(double);
-            i64 g2 = (nquads + NT / 64 - 1) / (NT / 64);
-            const i64 cap = (i64)num_cus * (wgs > 0 ? wgs : wg_per_cu);
-            if (g2 > cap) g2 = cap;
-            kern<<<(unsigned)g2, NT, lds, st>>>(X, Y, k, col_end, R, G, Ginv, status, fail_flag, iter_tag, col_begin, nullptr, stats);
-            return 0;
-        };
-        if (shape == 1) { if (s1) run(nnls_bpp_g16_kernel<32, 512, 4, true>, 512, 2); else run(nnls_bpp_g16_kernel<32, 512, 4, false>, 512, 2); }
-        else if (shape == 2) { if (s1) run(nnls_bpp_g16_kernel<32, 512, 2, true>, 512, 1); else run(nnls_bpp_g16_kernel<32, 512, 2, false>, 512, 1); }
-        else if (shape == 0) { if (s1) run(nnls_bpp_g16_kernel<32, 256, 3, true>, 256, 3); else run(nnls_bpp_g16_kernel<32, 256, 3, false>, 256, 3); }
-        else { if (s1) run(nnls_bpp_g16_kernel<32, 256, 3, true, true>, 256, 3); else run(nnls_bpp_g16_kernel<32, 256, 3, false, true>, 256, 3); }
-        SMK_HIP(hipGetLastError());
-        return (shape == 1 || shape == 2) ? 1 : 2;
-    } else {
-        constexpr int NT = 512;
-        const int lds = (2 * 64 * 64 + (NT / 64) * 4 * 96) * (int)sizeof(double);
-        SMK_HIP(hipMemsetAsync(defer, 0, sizeof(unsigned), st));
-        i64 g2 = (nquads + NT / 64 - 1) / (NT / 64);
-        const i64 cap = (i64)num_cus * (wgs > 0 ? wgs : 1);
-        if (g2 > cap) g2 = cap;
-        if (s1) {
-            SMK_HIP(hipFuncSetAttribute((const void*)nnls_bpp_g16_kernel<64, NT, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            nnls_bpp_g16_kernel<64, NT, 1, true><<<(unsigned)g2, NT, lds, st>>>(X, Y, k, col_end, R, G, Ginv, status, fail_flag, iter_tag, col_begin, defer, stats);
-        } else {
-            SMK_HIP(hipFuncSetAttribute((const void*)nnls_bpp_g16_kernel<64, NT, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            nnls_bpp_g16_kernel<64, NT, 1, false><<<(unsigned)g2, NT, lds, st>>>(X, Y, k, col_end, R, G, Ginv, status, fail_flag, iter_tag, col_begin, defer, stats);
-        }
-    }
+    i64 g2 = (nquads + NT / 64 - 1) / (NT / 64);
+    const i64 cap = (i64)num_cus * 3;
+    if (g2 > cap) g2 = cap;
+    if (R.S == 1 && R.f64) nnls_bpp_g16_kernel<true><<<(unsigned)g2, NT, lds, st>>>(X, Y, k, col_end, R, G, Ginv, status, fail_flag, iter_tag, col_begin, stats);
+    else nnls_bpp_g16_kernel<false><<<(unsigned)g2, NT, lds, st>>>(X, Y, k, col_end, R, G, Ginv, status, fail_flag, iter_tag, col_begin, stats);
     SMK_HIP(hipGetLastError());
     return 1;
 }

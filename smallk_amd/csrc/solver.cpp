@@ -248,10 +248,9 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
         rc |= s->own.dev(&s->H0c, (size_t)s->KP * s->n);
     }
     if (opts->algorithm == SMK_ALG_BPP) {
-        // k <= 128: two (inverse + selector) halves; above: one Cholesky panel per resident workgroup (wide.hip)
+        // k <= 64: two (inverse + selector) halves; above: one Cholesky panel per resident workgroup (wide.hip)
         rc |= s->own.dev(&s->nnls_scratch, nnls_uses_tiles(s->k) ? nnls_wide_scratch_elems(s->k, ctx().cus, std::max(s->m, s->n)) : 2 * nnls_scratch_elems(s->k));
-        if (s->KP == 64 && !nnls_uses_tiles(s->k)) rc |= s->own.dev(&s->nnls_defer, nnls_defer_elems(std::max(s->m, s->n)));
-        // (above k = 128 the inverse stays in stream order: beside the product it gained 1-2 % -- measured -- and the two sides
+        // (above k = 64 the inverse stays in stream order: beside the product it gained 1-2 % -- measured -- and the two sides
         // share one scratch there)
         // The second stream pays two event hops per solve (~8 us each way on the main stream): worth it where it hides the 47 us
         // inversion of k in (32, 64] behind a dense pass; at k in (16, 32] (13 us) stream order is as fast or faster (4096 x 2048,
@@ -259,7 +258,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
         // rides in the gather product's launch (start_inverse).  SMK_INV_STREAM=1: the second stream everywhere, =0: nowhere.
         const int inv_env = sw::inv_stream();
         const bool inv_beside = inv_env >= 0 ? inv_env != 0 : (!a->sparse && s->KP >= 64);
-        if (inv_beside && (s->KP >= 64 || (s->KP == 32 && nnls_inverse_at_32())) && !nnls_uses_tiles(s->k)) {
+        if (inv_beside && (s->KP == 64 || (s->KP == 32 && nnls_inverse_at_32()))) {
             rc |= s->own.stream(&s->st_inv, hipStreamNonBlocking);
             for (int i = 0; i < 2 && !rc; ++i) {
                 rc |= s->own.event(&s->ev_g[i], hipEventDisableTiming);
@@ -686,7 +685,7 @@ static int start_inverse(smk_solver* s, int side, const double* G, hipEvent_t af
         // us per iteration beside the product, 118 in stream order, 91 riding; dense 4096 x 2048, k = 32: 115 / 92 / 70).  A launch
         // that cannot carry it leaves it to launch_nnls_bpp, in stream order, or to the second stream.  SMK_INV_RIDE=0: never rides.
         const bool ride = sw::inv_ride();
-        const bool route = !nnls_uses_tiles(s->k) && (s->KP == 64 || (s->KP == 32 && nnls_inverse_at_32()));
+        const bool route = s->KP == 64 || (s->KP == 32 && nnls_inverse_at_32());
         const bool carrier = s->a->sparse ? true : (s->ng == 1 && bigprod_supports_ride(side == 0 ? s->pg1[0] : s->pg2[0]));
         if (ride && route && carrier && !after && !is_dist(s) && !s->comm && !s->w_sharded) { s->inv_ride[side] = true; return 0; }
     }
@@ -755,7 +754,7 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
         }
     }
     const int rc = launch_nnls_bpp(X, nullptr, s->k, c0, c1, R, G, s->fail_flag, s->iter, inv_scratch(s, side), s->inv_done[side] ? 1 : 0, ctx().cus, s->st,
-                                   want ? s->gram_scratch : nullptr, want ? &s->nnls_gram_nblk[side] : nullptr, pack ? &pk : nullptr, s->nnls_defer,
+                                   want ? s->gram_scratch : nullptr, want ? &s->nnls_gram_nblk[side] : nullptr, pack ? &pk : nullptr,
                                    riders ? &rd : nullptr);
     if (!rc && rd.pg_part) {
         // the totals of the deferred check are due: they ride in the tail of the pass that follows (prod2), or go out as a launch
@@ -1911,14 +1910,12 @@ int smk_nnls_blockpivot(int k, int64_t ncols, const double* LHS, int64_t ldL, co
         }
     Scratch<double> dg, dr, dx, dy, dscratch;
     Scratch<int> dflag;
-    Scratch<unsigned> ddefer;
     int rc = dg.alloc(hg.size());
     rc |= dr.alloc(hr.size());
     rc |= dx.alloc(hx.size());
     rc |= dy.alloc(hx.size());
     rc |= dscratch.alloc(nnls_uses_tiles(k) ? nnls_wide_scratch_elems(k, ctx().cus, ncols) : nnls_scratch_elems(k));
     rc |= dflag.alloc(1);
-    if (KP == 64 && !nnls_uses_tiles(k)) rc |= ddefer.alloc(nnls_defer_elems(ncols));
     if (rc) return SMK_DEVICE_ERROR;
     const int big = INT_MAX;
     SMK_HIP(hipMemcpyAsync(dg, hg.data(), hg.size() * sizeof(double), hipMemcpyHostToDevice, ctx().stream));
@@ -1927,7 +1924,7 @@ int smk_nnls_blockpivot(int k, int64_t ncols, const double* LHS, int64_t ldL, co
     SMK_HIP(hipMemsetAsync(dy, 0, hx.size() * sizeof(double), ctx().stream));
     SMK_HIP(hipMemcpyAsync(dflag, &big, sizeof(int), hipMemcpyHostToDevice, ctx().stream));
     const PartialView pv{dr, 1, 0, KP, 1};
-    rc = launch_nnls_bpp(dx, dy, k, 0, ncols, pv, dg, dflag, 0, dscratch, 0, ctx().cus, ctx().stream, nullptr, nullptr, nullptr, ddefer);
+    rc = launch_nnls_bpp(dx, dy, k, 0, ncols, pv, dg, dflag, 0, dscratch, 0, ctx().cus, ctx().stream);
     if (rc) return rc;
     int flag = INT_MAX;
     SMK_HIP(hipMemcpyAsync(hx.data(), dx, hx.size() * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));

@@ -132,8 +132,7 @@ struct smk_solver {
     bool guard_pending = false, guard_off = false;
     double guard_last = 0.0;               // cond * delta of the last check
     bool wc_valid = false;
-    double* nnls_scratch = nullptr;       // BPP: inverses of W'W and HH' + path selectors (k > 32), two halves
-    unsigned* nnls_defer = nullptr;       // BPP, k in (32, 64]: work list between nnls_bpp_g16_kernel and the wave-per-column kernel
+    double* nnls_scratch = nullptr;       // BPP: inverses of W'W and HH' + path selectors (k in (16, 64]), two halves
     int hals_ep_blocks = 0;               // HALS, k <= 32: Gram partials the sweeps' epilogues may write into gram_scratch (0: epilogues off)
     hipStream_t st_inv = nullptr;         // the 0.1 ms single-workgroup inversions run here, beside the streaming products
     hipEvent_t ev_g[2] = {nullptr, nullptr}, ev_inv[2] = {nullptr, nullptr};

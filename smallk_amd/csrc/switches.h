@@ -1,7 +1,11 @@
 // smallk_amd/csrc/switches.h -- every environment switch the library reads, in one table.
 //
-// The switches are the project's A/B record and its test surface: the older routes stay selectable, and the tests select them
-// by name.  A row states a switch's accessor, its environment name, how the text is parsed (with the default for "unset"), when
+// The switches are the project's test surface.  A route other than the default stays selectable when a test selects it by name
+// as a reference (the wave-per-column kernel the four-per-wave one must match bit for bit, the direct form) or as a recovery path
+// (the one-launch-per-column W sweep), or when it is an override of a computed choice.  A variant that lost its A/B is deleted,
+// code and switch, once its numbers are in profiles/ and DESIGN.md.
+//
+// A row states a switch's accessor, its environment name, how the text is parsed (with the default for "unset"), when
 // it is read, and what it means.  No other file under csrc calls getenv (preprocess.cpp reads OMP_NUM_THREADS, which is not
 // ours).  The measurements behind a switch stay in the comment at the site that uses it; tools/README.md lists the values.
 //
@@ -53,14 +57,10 @@ SMK_SW_LIVE(nnls_pack,          "SMK_NNLS_PACK",            on_unless_0(e))     
 SMK_SW_ONCE(gram_ride,          "SMK_GRAM_RIDE",            on_unless_0(e))         // sparse A, k in (8, 32]: the Gram matrix rides in the gather product's launches
 SMK_SW_ONCE(inv_ride,           "SMK_INV_RIDE",             on_unless_0(e))         // BPP, k in (16, 64]: the Gram inverse rides in the product launch; 0: a launch of its own
 SMK_SW_ONCE(inv_stream,         "SMK_INV_STREAM",           int_or(e, -1))          // that launch on a second stream: 0 nowhere / non-zero everywhere (< 0: dense and k > 32)
-SMK_SW_ONCE(gram_inverse_old,   "SMK_GRAM_INVERSE_OLD",     on_if_nonzero(e))       // the 64 x 64 inversion kernel that kept its registers in scratch
-SMK_SW_ONCE(nnls_inv,           "SMK_NNLS_INV",             int_or(e, 1))           // block pivoting through the Gram inverse: 0 the direct form only / 3, 4 older tilings of the k = 64 kernel
+SMK_SW_ONCE(nnls_inv,           "SMK_NNLS_INV",             int_or(e, 1))           // block pivoting through the Gram inverse; 0: the direct form only
 SMK_SW_ONCE(nnls_inv32,         "SMK_NNLS_INV32",           on_unless_0(e))         // k in (16, 32] solves through the inverse too; 0: the masked elimination
-SMK_SW_ONCE(nnls_tile128,       "SMK_NNLS_TILE128",         int_or(e, 1))           // tile kernel from k = 65 (1); 0: nnls_bpp_inv128_kernel up to 128; 2: also k in (32, 64]
 SMK_SW_ONCE(nnls_rounds,        "SMK_NNLS_ROUNDS",          int_or(e, 0))           // workgroups of the inverse-based kernels = resident workgroups x rounds (<= 0: 1 up to 65536 columns, 4 above)
-SMK_SW_ONCE(nnls_g16,           "SMK_NNLS_G16",             int_or(e, 1))           // four columns per wave: 0 off / 1 at k in (16, 32] / 2 also at k in (32, 64]
-SMK_SW_ONCE(nnls_g16_shape,     "SMK_NNLS_G16_SHAPE",       int_or(e, 3))           // its launch shape at k in (16, 32]: 3 / 0 / 1 / 2 (A/B)
-SMK_SW_ONCE(nnls_g16_wgs,       "SMK_NNLS_G16_WGS",         int_or(e, 0))           // its workgroups per CU (<= 0: the shape's own)
+SMK_SW_ONCE(nnls_g16,           "SMK_NNLS_G16",             int_or(e, 1))           // four columns per wave at k in (16, 32]; 0: a wave per column
 SMK_SW_ONCE(wide_nw,            "SMK_WIDE_NW",              int_or(e, 0))           // tile kernel: 1 a wave per column / other non-zero: the workgroup per column (0: by LDS fit)
 SMK_SW_ONCE(nnls_stats,         "SMK_NNLS_STATS",           on_if_nonzero(e))       // 256 device counters of block pivoting's work (smk_debug_nnls_stats)
 SMK_SW_ONCE(bpp_gradw,          "SMK_BPP_GRADW",            starts_with(e, '1'))    // BPP: form the W-side gradient although it is the dual of the W-side NNLS
@@ -71,7 +71,6 @@ SMK_SW_ONCE(hals_w_blocked,     "SMK_HALS_W_BLOCKED",       on_unless_0(e))     
 SMK_SW_ONCE(hals_w_multi,       "SMK_HALS_W",               starts_with(e, 'm'))    // "multi": the one-launch-per-column W sweep instead of the persistent kernel
 SMK_SW_ONCE(hals_spin,          "SMK_HALS_SPIN",            int_or(e, 0))           // bound of the persistent sweep's exchange polls (<= 0: 2^22; tests set 1 to force the fallback)
 SMK_SW_ONCE(hals_nt,            "SMK_HALS_NT",              int_or(e, 256))         // smallest workgroup size of the persistent W sweep
-SMK_SW_ONCE(hals_exchange,      "SMK_HALS_EXCHANGE",        int_or(e, 1))           // 2: the two-level exchange of the persistent sweep (measured slower, kept as the record)
 
 // ---- stopping rule and timing (solver.cpp) ---------------------------------------------------------------------------------------
 SMK_SW_ONCE(sync_progress,      "SMK_SYNC_PROGRESS",        on_if_nonzero(e))       // check the stopping rule synchronously every iteration

@@ -737,7 +737,7 @@ __device__ __forceinline__ bool chol_solve_panel(double* Mp, int t, double* zs, 
 // in LDS (every workgroup for itself; workgroup 0 stores it in a side buffer -- not in place, the others may still be reading
 // the block -- which `chol_diag_store_kernel` moves into L at the end) and solves its 256 rows of the panel against it;
 // `chol_trail_kernel` subtracts the panel's outer product from the trailing lower triangle in 64 x 64 tiles.  *status stays
-// non-zero when every pivot exceeds 1e-9 of its diagonal entry (the guard of gram_inverse_kernel); a smaller pivot clears it,
+// non-zero when every pivot exceeds 1e-9 of its diagonal entry (the guard of gram_inverse64_body); a smaller pivot clears it,
 // which every later launch and the block-pivoting kernels read.
 constexpr int CH_NB = 32;
 

@@ -150,15 +150,13 @@ def test_hard_problems_use_backup_rule(gpu, k):
 
 
 def test_four_columns_per_wave_is_bit_identical_to_a_wave_per_column(tmp_path):
-    """nnls_g16.hip (round 6: a column per 16-lane row, four per wave; columns of k > 32 whose exchange needs more than 16 rows go
-    to the wave-per-column kernel through a work list) against nnls.hip's wave-per-column kernel on 63 problems: same operations in
-    the same order, so the same bits -- and tools/nnls_g16_check.py's family covers both forms, t = 0 .. 32 and ragged column counts."""
+    """nnls_g16.hip (round 6: a column per 16-lane row, four per wave, at k in (16, 32]) against nnls.hip's wave-per-column kernel
+    on 63 problems: same operations in the same order, so the same bits -- and tools/nnls_g16_check.py's family covers both forms,
+    t = 0 .. 32 and ragged column counts (its k > 32 cases take the wave-per-column kernel in both runs)."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
-    # SMK_NNLS_G16=2: the four-columns-per-wave kernel at k in (32, 64] as well (default: k <= 32 only)
-    for tag, env in (("wave", {"SMK_NNLS_G16": "0"}), ("g16", {"SMK_NNLS_G16": "2"}), ("g16_shape1", {"SMK_NNLS_G16": "2", "SMK_NNLS_G16_SHAPE": "1"}), ("g16_shape0", {"SMK_NNLS_G16_SHAPE": "0"}),
-                     ("default", {})):
+    for tag, env in (("wave", {"SMK_NNLS_G16": "0"}), ("default", {})):
         f = str(tmp_path / f"{tag}.npz")
         r = subprocess.run([sys.executable, os.path.join(root, "tools", "nnls_g16_check.py"), f], capture_output=True, text=True,
                            env=dict(os.environ, **env), cwd=root, timeout=600)

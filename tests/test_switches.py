@@ -63,14 +63,10 @@ EXPECTED = {
     "SMK_GRAM_RIDE": [("gram_ride", ONCE, ON_UNLESS_0)],
     "SMK_INV_RIDE": [("inv_ride", ONCE, ON_UNLESS_0)],
     "SMK_INV_STREAM": [("inv_stream", ONCE, NUM(-1))],
-    "SMK_GRAM_INVERSE_OLD": [("gram_inverse_old", ONCE, ON_IF_NONZERO)],
     "SMK_NNLS_INV": [("nnls_inv", ONCE, NUM(1))],
     "SMK_NNLS_INV32": [("nnls_inv32", ONCE, ON_UNLESS_0)],
-    "SMK_NNLS_TILE128": [("nnls_tile128", ONCE, NUM(1))],
     "SMK_NNLS_ROUNDS": [("nnls_rounds", ONCE, NUM(0))],
     "SMK_NNLS_G16": [("nnls_g16", ONCE, NUM(1))],
-    "SMK_NNLS_G16_SHAPE": [("nnls_g16_shape", ONCE, NUM(3))],
-    "SMK_NNLS_G16_WGS": [("nnls_g16_wgs", ONCE, NUM(0))],
     "SMK_WIDE_NW": [("wide_nw", ONCE, NUM(0))],
     "SMK_NNLS_STATS": [("nnls_stats", ONCE, ON_IF_NONZERO)],
     "SMK_BPP_GRADW": [("bpp_gradw", ONCE, FIRST_IS_1)],              # true = the W-side gradient is formed; "2": not formed
@@ -79,7 +75,6 @@ EXPECTED = {
     "SMK_HALS_W": [("hals_w_multi", ONCE, FIRST_IS_M)],
     "SMK_HALS_SPIN": [("hals_spin", ONCE, NUM(0))],                  # honoured when atoi > 0
     "SMK_HALS_NT": [("hals_nt", ONCE, NUM(256))],
-    "SMK_HALS_EXCHANGE": [("hals_exchange", ONCE, NUM(1))],
     "SMK_SYNC_PROGRESS": [("sync_progress", ONCE, ON_IF_NONZERO)],
     "SMK_PROGRESS_FUSED": [("progress_fused", ONCE, ON_UNLESS_0)],
     "SMK_PROGRESS_DEFER": [("progress_defer", ONCE, ON_UNLESS_0)],

@@ -1,7 +1,8 @@
 """NnlsBlockpivot through the C ABI on a fixed family of problems (k = 17 .. 64, solution densities 0 .. 1, warm starts of every
 density, 1 .. 4099 columns), results saved to <out.npz>: tests/test_gpu_nnls.py runs it once with SMK_NNLS_G16=0 (a wave per
-column, nnls.hip) and once with the default (four columns per wave, nnls_g16.hip) and demands IDENTICAL bits -- the two kernels
-perform the same operations in the same order.   python tools/nnls_g16_check.py out.npz"""
+column, nnls.hip) and once with the default (four columns per wave at k <= 32, nnls_g16.hip) and demands IDENTICAL bits -- the
+two kernels perform the same operations in the same order.  The cases with k in (32, 64] take the wave-per-column kernel in both
+runs and stay in the family: the switch must not reach them.   python tools/nnls_g16_check.py out.npz"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
