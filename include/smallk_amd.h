@@ -307,6 +307,38 @@ int smk_cd_last_profile(int* products, int* sweeps);
  * 3 the reduction of the partial products alone.  *checksum: the violation of the last launch (which 0 / 1), else 0. */
 int smk_cd_sweep_time(int which, int k, int64_t ncols, int slabs, int reps, double* ms, double* checksum);
 
+/* ---- NMF of a sparse matrix under the generalised Kullback-Leibler divergence, by multiplicative updates ---------
+ * scikit-learn's solver="mu" with beta_loss="kullback-leibler" on X = A': W_sklearn = H', components_ = W', sklearn's alpha_W is
+ * alpha_h here and its alpha_H is alpha_w; l1 / l2 of H = m alpha_h l1_ratio / m alpha_h (1 - l1_ratio), of W = n alpha_w l1_ratio /
+ * n alpha_w (1 - l1_ratio).  With EPS = 2^-23, over the stored entries (i, j, a) of A, one iteration is
+ *   H[t, j] *= (sum over column j of a / max(w_i . h_j, EPS) W[i, t]) / (sum_i W[i, t] + l1 + l2 H[t, j])
+ *   W[i, t] *= (sum over row i of a / max(w_i . h_j, EPS) H[t, j]) / (s_t + l1 + l2 W[i, t]),  s_t = sum_j H[t, j], 0 -> 1.0
+ * each penalty added only if > 0, a zero denominator replaced by EPS, W below 2^-52 set to 0.  error = sqrt(2 max(D, 0)),
+ * D = sum a log(a / max(w_i . h_j, EPS)) - sum a + (sum_i w_i) . (sum_j h_j); error_init is taken before iteration 1; when tol > 0
+ * the error is taken at iterations 10, 20, ... and the run stops when (previous error - error) / error_init < tol, else after
+ * max_iter iterations.  stats->error is that of the factors returned.  update_w = 0: W stays as given and only the H step repeats
+ * (fold-in of new columns).  fp64, every sum in a fixed order: the same bits on every call.  The host reads the device on check
+ * iterations only.
+ * SMK_BAD_PARAM: a null pointer, k < 1, k > min(m, n), a negative alpha, l1_ratio outside [0, 1], tol < 0, max_iter < 1, a bad view,
+ * a negative stored value.  SMK_UNSUPPORTED: a dense matrix, k > 128, a column shard, a matrix that stores an entry twice (the
+ * divergence is not linear in a).  On an error W and H are untouched. */
+typedef struct smk_kl_options { double alpha_w, alpha_h, l1_ratio, tol; int max_iter; int update_w; } smk_kl_options;
+typedef struct smk_kl_stats   { int iterations; int converged; double error_init, error; } smk_kl_stats;
+/* W (m x k) and H (k x ncols) are in/out views in device memory (SMK_DT_F64 / SMK_DT_F32, strides in elements, the caller's stream) */
+int smk_nmf_kl_device(const smk_matrix* a, int k, const smk_kl_options* o, void* W, int dtW, int64_t rsW, int64_t csW,
+                      void* H, int dtH, int64_t rsH, int64_t csH, void* stream, smk_kl_stats* stats);
+/* out[0] = D (not clamped), out[1] = sum a log(a / max(w_i . h_j, EPS)), out[2] = sum WH of the given factors (views as above, only
+ * read); the error returns of smk_nmf_kl_device that apply */
+int smk_matrix_kl_divergence_device(const smk_matrix* a, int k, const void* W, int dtW, int64_t rsW, int64_t csW,
+                                    const void* H, int dtH, int64_t rsH, int64_t csH, void* stream, double* out);
+/* diagnostics of the calling thread's last smk_nmf_kl_device call: sweeps over the stored entries that updated a factor, and
+ * sweeps that formed the divergence */
+int smk_kl_last_profile(int* entry_passes, int* divergence_passes);
+/* measurement (tools/kl_rate.py): the average time in ms of `reps` launches on synthetic factors of rank k.  which: 0 the H step
+ * (the quotient gather over CSC(A) with its update), 1 the W step (over CSC(A')), 2 / 3 the plain gather product launch_spmm_seg on
+ * the same plan, rank and gathered factor as 0 / 1: one gather of the same rows without the dot product and the quotient */
+int smk_kl_step_time(const smk_matrix* a, int which, int k, int reps, double* ms);
+
 /* ---- labels, memberships, top terms and fold-in, on the device (the device twins of smk_compute_assignments,
  * smk_compute_fuzzy_assignments and smk_top_terms below: the same comparisons in the same order, so the same integers and the
  * same membership bits; no k <= n and no height >= width requirement) -----------------------------------------------------

@@ -79,6 +79,17 @@ class CdStats(C.Structure):
     _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("violation_init", C.c_double), ("violation", C.c_double)]
 
 
+class KlOptions(C.Structure):
+    """struct smk_kl_options: the penalties, the stopping rule and whether W is updated (0: fold-in, only H moves)."""
+    _fields_ = [("alpha_w", C.c_double), ("alpha_h", C.c_double), ("l1_ratio", C.c_double), ("tol", C.c_double),
+                ("max_iter", C.c_int), ("update_w", C.c_int)]
+
+
+class KlStats(C.Structure):
+    """struct smk_kl_stats: iterations run, whether the rule stopped them, sqrt(2 D) of the start and of the result."""
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("error_init", C.c_double), ("error", C.c_double)]
+
+
 class TreeNodeInfo(C.Structure):
     """struct smk_tree_node: the scalar fields of TreeNode<T> (hierclust/include/tree.hpp:31-50)."""
     _fields_ = [("priority", C.c_double), ("parent", C.c_uint), ("left_child", C.c_uint), ("right_child", C.c_uint),
@@ -161,6 +172,10 @@ SYMBOLS = {
     "smk_cd_sweep": (C.c_int, [C.c_int, _i64, _dp, _i64, _dp, _i64, _dp, _i64, C.c_double, C.c_double, _dp]),
     "smk_cd_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "smk_cd_sweep_time": (C.c_int, [C.c_int, C.c_int, _i64, C.c_int, C.c_int, _dp, _dp]),
+    "smk_nmf_kl_device": (C.c_int, [_vp, C.c_int, C.POINTER(KlOptions), _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, C.POINTER(KlStats)]),
+    "smk_matrix_kl_divergence_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _dp]),
+    "smk_kl_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "smk_kl_step_time": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp]),
     "smk_labels_device": (C.c_int, [_vp, C.c_int, _i64, _i64, C.c_int, _i64, _vp, _vp, _vp]),
     "smk_top_terms_device": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, _vp, _vp]),
     "smk_solver_labels": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),

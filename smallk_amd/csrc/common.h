@@ -499,6 +499,23 @@ int launch_cd_sweep(double* X, int k, i64 N, PartialView R, const double* G, dou
                     int maintained = 0);
 int launch_cd_violation(const double* partials, int n, double* out, double* host_out, hipStream_t st);
 
+// kl.hip: KL-divergence NMF on a sparse matrix by multiplicative updates, k <= 128, factors KP x N with pitch KP =
+// kp_of(k).  launch_kl_step: one half-iteration over the plan `sp` of one CSC (colptr / val the arrays the plan was built on): per
+// stored entry (i, j, a) q = a / max(g_i . x_j, 2^-23) and num_j += q g_i with ONE gather of g_i (G: the factor whose rows the entries
+// name, only read), then x_j[t] *= num_j[t] / (base[t] + l1 + l2 x_j[t]) in place (each penalty only if > 0, a zero denominator
+// becomes 2^-23; unit: a zero base[t] counts as 1.0; flush: results below 2^-52 become 0).  pieces: sp.npieces * KP doubles (null
+// if the plan has none).  Rows >= k of G and X are not relied on; X's are written as zeros.
+// launch_kl_divergence: out4 (and host_out when not null, pinned host memory) = D, sum a log(a / max(d, 2^-23)), sum WH, sum a over
+// the entries with a > 2^-23; sums_g / sums_x: the row sums of the two factors; divpart: 2 * sp.nseg doubles.
+// launch_kl_factor_sums: out[t] = sum_j X[t, j] (zero for t >= k); part: kl_sums_blocks(N) * KP doubles.
+// Fixed summation orders throughout: the same bits on every run.
+int launch_kl_step(const SegPlan& sp, const i64* colptr, const double* val, const double* G, double* X, int k, const double* base, int unit,
+                   double l1, double l2, int flush, double* pieces, hipStream_t st);
+int launch_kl_divergence(const SegPlan& sp, const i64* colptr, const double* val, const double* G, const double* X, int k, const double* sums_g,
+                         const double* sums_x, double* divpart, double* out4, double* host_out, hipStream_t st);
+int kl_sums_blocks(i64 N);
+int launch_kl_factor_sums(const double* X, int k, i64 N, double* part, double* out, hipStream_t st);
+
 // assign.hip: labels / memberships of the columns of H and the top terms of the columns of W, the factors fp64 or fp32 (DT_*) in
 // their k-contiguous layout: column c of H at H + c * ldc, row i of W at W + i * ld (elements).  The host functions' comparisons in
 // the host functions' order: the same integers, the same membership bits.  memb: k * n floats (document c at c * k) or null.

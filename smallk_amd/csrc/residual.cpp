@@ -16,7 +16,7 @@ namespace smk {
 // Does the CSC store an entry twice?  Then sum a_e^2 over the stored entries is not ||A||^2 (the other two terms of the sparse
 // formula are linear in the stored values and right as they are), and the sum of squares per column is taken from the merged
 // entries, once, on the host copy of the CSC (off the hot path), and kept on the device.
-static int ensure_dup_record(const smk_matrix* a)
+int ensure_dup_record(const smk_matrix* a)
 {
     static std::mutex mu;             // lazily built part of a shared, nominally const matrix (as ensure_seg_plans)
     std::lock_guard<std::mutex> lk(mu);

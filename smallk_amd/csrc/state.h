@@ -76,6 +76,8 @@ struct smk_matrix {
     // merged entries.  Looked up once: a sparse matrix does not change after creation.
     mutable int dup_state = -1;
     mutable double* dup_colsq = nullptr;
+    // sparse A, kl.cpp: whether a stored value is negative (the KL divergence refuses such a matrix): -1 = not yet looked, 0 = no, 1 = yes
+    mutable int kl_negative = -1;
     mutable smk::Owned own;                          // every device block above (the lazily built stored transpose included); the blocked CSC and the segment plans free themselves
 };
 
@@ -231,6 +233,9 @@ int ensure_seg_plans(const smk_matrix* a);
 int matrix_measure_scale(const smk_matrix* a, hipStream_t st);
 int matrix_measure_norms(const smk_matrix* a, hipStream_t st);
 int matrix_host_csc(const smk_matrix* a);         // the host copy of a resident CSC (h_colptr / h_rowidx / h_val), fetched on first use
+
+// residual.cpp: the once-per-matrix duplicate record of a sparse matrix (dup_state, dup_colsq; fetches the host copy of the CSC)
+int ensure_dup_record(const smk_matrix* a);
 
 // matrix.cpp: a strided view in device memory handed in by a caller (the *_device entries).  check_device_view: SMK_OK, or
 // SMK_BAD_PARAM with the error text set -- null pointer, unknown element type, negative stride (or a zero stride of an output),

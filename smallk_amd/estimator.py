@@ -1,4 +1,6 @@
-"""``smallk_amd.NMF``: the scikit-learn-style estimator over ``nmf_cd`` (coordinate descent with L1 / L2 penalties, on the GPU).
+"""``smallk_amd.NMF``: the scikit-learn-style estimator over ``nmf_cd`` (coordinate descent with L1 / L2 penalties, on the GPU)
+and, for ``solver="mu"`` with ``beta_loss="kullback-leibler"``, over ``nmf_kl`` (multiplicative updates of the generalised
+Kullback-Leibler divergence on a sparse X).
 
 X is in scikit-learn's orientation, samples x features; the library factors A = X' (features x samples), which costs nothing:
 a scipy CSR X hands its three arrays over as the CSC of A, a C-contiguous dense X is the column-major A, a torch tensor is
@@ -13,6 +15,7 @@ import numpy as np
 from . import solver as S
 
 INITS = (None, "nndsvd", "nndsvda", "random", "custom")
+KL_LOSSES = ("kullback-leibler", 1, 1.0)
 
 
 def _is_sparse(X) -> bool:
@@ -29,14 +32,20 @@ class NMF:
     n_components + 8 <= 128 and "random" above that.  "random" is sqrt(mean(X) / k) |N(0, 1)| drawn from
     ``numpy.random.default_rng(random_state)``, H first, then W: not sklearn's random stream.  ``n_components=None`` is the
     number of features.  X: a numpy array, a scipy sparse matrix, or a torch tensor in GPU memory (results then stay tensors).
-    The library's rules apply: n_components <= min(samples, features) and <= 128, also for the samples given to ``transform``."""
+    The library's rules apply: n_components <= min(samples, features) and <= 128, also for the samples given to ``transform``.
+
+    ``solver="mu"`` together with ``beta_loss="kullback-leibler"`` (or 1) is sklearn's multiplicative-update iteration for the
+    generalised Kullback-Leibler divergence (``nmf_kl``): X is a scipy sparse matrix, ``reconstruction_err_`` is
+    sqrt(2 D(X || W H)) as sklearn's, the stopping rule is sklearn's (every tenth iteration).  Either half alone is refused:
+    ``solver="mu"`` with the Frobenius loss is not sklearn's iteration here, and ``solver="cd"`` has no KL form."""
 
     def __init__(self, n_components=None, *, init=None, solver="cd", beta_loss="frobenius", tol=1e-4, max_iter=200,
                  random_state=None, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, shuffle=False):
-        if solver != "cd":
-            raise ValueError(f"NMF: solver must be 'cd', got {solver!r}")
-        if beta_loss not in ("frobenius", 2, 2.0):
-            raise ValueError(f"NMF: beta_loss must be 'frobenius', got {beta_loss!r}")
+        kl = solver == "mu" and not isinstance(beta_loss, bool) and beta_loss in KL_LOSSES
+        if solver != "cd" and not kl:
+            raise ValueError(f"NMF: solver must be 'cd', or 'mu' together with beta_loss='kullback-leibler'; got {solver!r} with {beta_loss!r}")
+        if not kl and beta_loss not in ("frobenius", 2, 2.0):
+            raise ValueError(f"NMF: beta_loss must be 'frobenius', or 'kullback-leibler' together with solver='mu'; got {beta_loss!r}")
         if shuffle:
             raise ValueError("NMF: shuffle=True is not available; the coordinates are swept in order")
         if init not in INITS:
@@ -57,9 +66,17 @@ class NMF:
         self.tol, self.max_iter, self.random_state = tol, max_iter, random_state
         self.alpha_W, self.alpha_H, self.l1_ratio, self.shuffle = alpha_W, alpha_H, l1_ratio, shuffle
 
+    @property
+    def _kl(self):
+        return self.solver == "mu"
+
+    def _fit_factors(self, A, W0, H0, **kw):
+        return (S.nmf_kl if self._kl else S.nmf_cd)(A, W0, H0, **kw, **self._penalties())
+
     # ---- X -> the resident A = X', the mean of X, whether results go back as tensors
-    @staticmethod
-    def _resident(X):
+    def _resident(self, X):
+        if self._kl and not _is_sparse(X):
+            raise ValueError("NMF: the Kullback-Leibler path takes sparse input (a scipy sparse matrix); a dense X is not supported with this loss")
         if _is_sparse(X):
             X = X.tocsr()
             ns, nf = X.shape
@@ -113,12 +130,12 @@ class NMF:
         try:
             k = int(self.n_components) if self.n_components is not None else A.height
             W0, H0 = self._start(A, k, mean, W, H)
-            r = S.nmf_cd(A, W0, H0, **self._penalties())
+            r = self._fit_factors(A, W0, H0)
             self._W, self._H = r.W, r.H             # (features, k) and (k, samples), float64 tensors on the GPU
             self.n_iter_ = r.n_iter
             self.n_components_ = k
             self.n_features_in_ = A.height
-            self.reconstruction_err_ = math.sqrt(A.residual(r.W, r.H).resid_sq)
+            self.reconstruction_err_ = r.error if self._kl else math.sqrt(A.residual(r.W, r.H).resid_sq)
             self._as_tensor = as_tensor
         finally:
             A.close()
@@ -150,7 +167,7 @@ class NMF:
                 raise ValueError(f"NMF.transform: X has {A.height} features, the model {self.n_features_in_}")
             k = self.n_components_
             H0 = torch.full((k, A.ncols), math.sqrt(mean / k), dtype=torch.float64, device=self._W.device)
-            r = S.nmf_cd(A, self._W, H0, update_W=False, **self._penalties())
+            r = self._fit_factors(A, self._W, H0, update_W=False)
         finally:
             A.close()
         return self._out(r.H.t(), as_tensor)

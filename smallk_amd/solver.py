@@ -82,6 +82,20 @@ class Residual:
         return math.sqrt(self.resid_sq / self.a_sq) if self.a_sq > 0 else math.nan
 
 
+@dataclass
+class KlDivergence:
+    """D(A || W H) of ``SparseMatrix.kl_divergence`` and its two large terms: sum a log(a / w_i . h_j) over the stored entries
+    and sum WH (D = a_log_ratio - sum a + sum_wh)."""
+    divergence: float
+    a_log_ratio: float
+    sum_wh: float
+
+    @property
+    def error(self) -> float:
+        """sqrt(2 max(D, 0)): scikit-learn's ``reconstruction_err_`` for this loss"""
+        return math.sqrt(2.0 * max(self.divergence, 0.0))
+
+
 def _residual_factors(W, H, height, ncols, what):
     """The checks of ``DenseMatrix.residual`` made before the library is called: both factors on the host (array-likes of
     numbers) or both torch tensors, 2-D, W (height, k) and H (k, ncols) with k >= 1.  Returns (on_device, k)."""
@@ -444,6 +458,23 @@ class SparseMatrix(DenseMatrix):
         L.check(L.lib().smk_matrix_sparse_product(self._h, int(transposed), k, _p(X), k, _p(out), k, int(reps),
                                                   C.byref(ms) if reps > 0 else None), "smk_matrix_sparse_product")
         return (out, ms.value) if reps > 0 else out
+
+    def kl_divergence(self, W, H) -> KlDivergence:
+        """The generalised Kullback-Leibler divergence D(A || W H) = sum a log(a / w_i . h_j) - sum a + sum WH over the stored
+        entries of A, computed on the device in fp64 (dot products below 2^-23 count as 2^-23, as in scikit-learn).  W (height, k)
+        and H (k, ncols): both numpy arrays, or both float64 / float32 torch tensors in GPU memory (any strides)."""
+        on_device, k = _residual_factors(W, H, self.height, self.ncols, "kl_divergence")
+        if not on_device:
+            import torch
+            dev = torch.device("cuda", L.lib().smk_current_device())
+            W = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64)).to(dev)
+            H = torch.from_numpy(np.ascontiguousarray(H, dtype=np.float64)).to(dev)
+        wp, wt, (wrs, wcs) = _tensor_view(W, "kl_divergence(W)", kinds="factor")
+        hp, ht, (hrs, hcs) = _tensor_view(H, "kl_divergence(H)", kinds="factor")
+        out = (C.c_double * 3)()
+        L.check(L.lib().smk_matrix_kl_divergence_device(self._h, k, wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), out),
+                "smk_matrix_kl_divergence_device")
+        return KlDivergence(out[0], out[1], out[2])
 
 
 def load_matrix_market(path):
@@ -812,6 +843,63 @@ def cd_last_profile():
     """(passes over A, sweeps launched) of this thread's last ``nmf_cd``"""
     p, s = C.c_int(0), C.c_int(0)
     L.check(L.lib().smk_cd_last_profile(C.byref(p), C.byref(s)), "smk_cd_last_profile")
+    return p.value, s.value
+
+
+@dataclass
+class KlResult:
+    """What ``nmf_kl`` returns: the factors (numpy arrays, or torch tensors on the GPU when the start was tensors), the iterations
+    run (sklearn's ``n_iter_``), whether the stopping rule ended them, and sqrt(2 D(A || W H)) of the start and of the result
+    (the latter is sklearn's ``reconstruction_err_``)."""
+    W: object
+    H: object
+    n_iter: int
+    converged: bool
+    error_init: float
+    error: float
+
+
+def nmf_kl(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True, inplace=False) -> KlResult:
+    """NMF under the generalised Kullback-Leibler divergence by multiplicative updates -- scikit-learn's ``solver="mu"`` with
+    ``beta_loss="kullback-leibler"`` -- on a resident ``SparseMatrix`` A (m, n), from the start W0 (m, k), H0 (k, n): both numpy
+    arrays, or both float64 / float32 torch tensors in GPU memory (any strides).  Minimises
+
+        D(A || W H) + n alpha_W l1_ratio ||W||_1 + m alpha_H l1_ratio ||H||_1
+                    + 1/2 n alpha_W (1 - l1_ratio) ||W||_F^2 + 1/2 m alpha_H (1 - l1_ratio) ||H||_F^2
+
+    which is ``sklearn.decomposition.NMF`` on X = A' with sklearn's ``alpha_W`` = this ``alpha_H`` and its ``alpha_H`` = this
+    ``alpha_W``, W_sklearn = H' and ``components_`` = W'; the stopping rule is sklearn's, looked at every tenth iteration.
+    ``alpha_H="same"`` takes ``alpha_W``.  ``update_W=False``: W stays, only H is fitted (fold-in).  The start is not modified unless
+    ``inplace`` (tensors only): then W0 / H0 receive the result.  A must store no entry twice and no negative value."""
+    if not isinstance(A, DenseMatrix):
+        raise ValueError(f"nmf_kl: A must be a resident SparseMatrix, got {type(A).__name__}")
+    on_device, k = _residual_factors(W0, H0, A.height, A.ncols, "nmf_kl")
+    if inplace and not on_device:
+        raise ValueError("nmf_kl: inplace needs torch tensors")
+    import torch
+    if alpha_H == "same":
+        alpha_H = alpha_W
+    o = L.KlOptions(float(alpha_W), float(alpha_H), float(l1_ratio), float(tol), int(max_iter), int(bool(update_W)))
+    if on_device:
+        W, H = (W0, H0) if inplace else (W0.clone(), H0.clone())
+    else:
+        dev = torch.device("cuda", L.lib().smk_current_device())
+        W = torch.from_numpy(np.ascontiguousarray(W0, dtype=np.float64)).to(dev)
+        H = torch.from_numpy(np.ascontiguousarray(H0, dtype=np.float64)).to(dev)
+    wp, wt, (wrs, wcs) = _tensor_view(W, "nmf_kl(W0)", kinds="factor")
+    hp, ht, (hrs, hcs) = _tensor_view(H, "nmf_kl(H0)", kinds="factor")
+    st = L.KlStats()
+    L.check(L.lib().smk_nmf_kl_device(A._h, k, C.byref(o), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), C.byref(st)),
+            "smk_nmf_kl_device")
+    if not on_device:
+        W, H = W.cpu().numpy(), H.cpu().numpy()
+    return KlResult(W, H, st.iterations, bool(st.converged), st.error_init, st.error)
+
+
+def kl_last_profile():
+    """(sweeps over the stored entries that updated a factor, sweeps that formed the divergence) of this thread's last ``nmf_kl``"""
+    p, s = C.c_int(0), C.c_int(0)
+    L.check(L.lib().smk_kl_last_profile(C.byref(p), C.byref(s)), "smk_kl_last_profile")
     return p.value, s.value
 
 
