@@ -220,6 +220,10 @@ int smk_solver_iterate_checked(smk_solver* s, int iters, double* last_metric);
 int smk_solver_sync(smk_solver* s); /* wait + report solver failures (Result code) */
 /* progress metric of the last iteration that computed one (PG ratio or delta-Fnorm) */
 int smk_solver_progress(smk_solver* s, double* metric);
+/* the four scalars of the check evaluated last, and pg0: the projected-gradient sums of W and of H (PG_RATIO), ||W - Wprev||^2 and
+ * ||W||^2 (DELTA_FNORM; the pair the rule does not use reads 0), PG_RATIO's first norm.  Host state only: nothing is launched or
+ * read.  SMK_BAD_PARAM before any check has been evaluated; SMK_UNSUPPORTED after a run the resident RANK2 kernel finished. */
+int smk_solver_progress_sums(const smk_solver* s, double out5[5]);
 /* optional final NormalizeAndScale (normalize.hpp:118-140), then copy factors to the host */
 int smk_solver_get_factors(smk_solver* s, int normalize, double* W, int64_t ldW, double* H, int64_t ldH);
 /* the same two with the factors in device memory (views as above; SMK_DT_F64 or SMK_DT_F32, fp32 output is the fp64 factor

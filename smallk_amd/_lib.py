@@ -156,6 +156,7 @@ SYMBOLS = {
     "smk_solver_iterate_checked": (C.c_int, [_vp, C.c_int, _dp]),
     "smk_solver_sync": (C.c_int, [_vp]),
     "smk_solver_progress": (C.c_int, [_vp, _dp]),
+    "smk_solver_progress_sums": (C.c_int, [_vp, _dp]),
     "smk_solver_get_factors": (C.c_int, [_vp, C.c_int, _dp, _i64, _dp, _i64]),
     "smk_solver_set_factors_device": (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp]),
     "smk_solver_get_factors_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp]),

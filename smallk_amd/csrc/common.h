@@ -290,7 +290,7 @@ int launch_sum_partials(const double* partials, int n, double* out, hipStream_t 
 // both factors in two launches; also mirrors *flag into pg_accum[flag_slot] (as a double)
 int launch_grad_pg2(const double* X1, i64 N1, PartialView R1, const double* G1, double* part1, const double* X2, i64 N2,
                     PartialView R2, const double* G2, double* part2, int k, double* pg_accum, const int* flag,
-                    int flag_slot, hipStream_t st);
+                    int flag_slot, hipStream_t st, int skip1 = 0);
 // the same + the snapshot of (W', H, W'W) in the gradient launch, and the totals written to `host_out` (pinned host memory, 8
 // doubles) by the summing launch as well: two launches, no copy packet, per checked iteration.  snap may be NULL.  skip1: the
 // projected-gradient sum of side 1 is known to be zero (BPP: the gradient is the NNLS's own dual), only its snapshot is taken.

@@ -1242,11 +1242,13 @@ template <int KP>
 __global__ __launch_bounds__(256) void grad_pg2_kernel(const double* __restrict__ X1, i64 N1, PartialView R1,
                                                        const double* __restrict__ G1, double* __restrict__ part1,
                                                        int grid1, const double* __restrict__ X2, i64 N2, PartialView R2,
-                                                       const double* __restrict__ G2, double* __restrict__ part2, int k)
+                                                       const double* __restrict__ G2, double* __restrict__ part2, int k, int skip1)
 {
     __shared__ double sh[16];
     extern __shared__ __attribute__((aligned(16))) double gs[];      // KP * KP doubles
-    if ((int)blockIdx.x < grid1) grad_pg_body<KP>(X1, k, N1, R1, G1, nullptr, part1, blockIdx.x, gs, sh);
+    // skip1 (BPP): side 1's sum is exactly 0, as in grad_pg2_snap_kernel
+    if ((int)blockIdx.x < grid1 && skip1) { if (threadIdx.x == 0) part1[blockIdx.x] = 0.0; }
+    else if ((int)blockIdx.x < grid1) grad_pg_body<KP>(X1, k, N1, R1, G1, nullptr, part1, blockIdx.x, gs, sh);
     else grad_pg_body<KP>(X2, k, N2, R2, G2, nullptr, part2, blockIdx.x - grid1, gs, sh);
 }
 
@@ -1415,10 +1417,10 @@ int launch_grad_pg(const double* X, int k, i64 N, PartialView R, const double* G
 // as a double in pg_accum[flag_slot]; two launches instead of four
 int launch_grad_pg2(const double* X1, i64 N1, PartialView R1, const double* G1, double* part1, const double* X2, i64 N2,
                     PartialView R2, const double* G2, double* part2, int k, double* pg_accum, const int* flag,
-                    int flag_slot, hipStream_t st)
+                    int flag_slot, hipStream_t st, int skip1)
 {
     const int KPv = kp_of(k), g1 = coltile_grid(KPv, N1), g2 = coltile_grid(KPv, N2);
-    COLTILE_LAUNCH(grad_pg2_kernel, g1 + g2, X1, N1, R1, G1, part1, g1, X2, N2, R2, G2, part2, k);
+    COLTILE_LAUNCH(grad_pg2_kernel, g1 + g2, X1, N1, R1, G1, part1, g1, X2, N2, R2, G2, part2, k, skip1);
     SMK_HIP(hipGetLastError());
     sum_partials2_kernel<<<2, 256, 0, st>>>(part1, g1, part2, g2, pg_accum, flag, flag_slot);
     SMK_HIP(hipGetLastError());

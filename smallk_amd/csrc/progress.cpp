@@ -116,14 +116,18 @@ static int enqueue_progress_kernels(smk_solver* s)
 // metric from the four scalars (PG sums for W and H, delta-Fnorm numerator / denominator)
 static int evaluate_progress(smk_solver* s, const double* h, int iter_index, double* metric)
 {
+    ProgressCheck& pc = s->pc;
     if (s->o.prog_est_algorithm == SMK_PROG_DELTA_FNORM) {
         *metric = std::sqrt(h[2]) / std::sqrt(h[3]);
+        pc.sums[0] = pc.sums[1] = 0.0;  pc.sums[2] = h[2];  pc.sums[3] = h[3];
     } else {
         const double pg = std::sqrt(h[0] + h[1]);
         if (std::isnan(pg)) { set_error("ProjectedGradientNorm: NaN"); return SMK_FAILURE; }   // reference throws
         if (iter_index == 0) { s->pc.pg0 = pg; *metric = 1.0; }
         else *metric = pg / s->pc.pg0;
+        pc.sums[0] = h[0];  pc.sums[1] = h[1];  pc.sums[2] = pc.sums[3] = 0.0;
     }
+    pc.sums_state = 1;
     s->pc.last_metric = *metric;
     return SMK_OK;
 }
@@ -222,7 +226,8 @@ int progress_begin(smk_solver* s, int b, bool snapshot, bool allow_defer)
     if (s->o.prog_est_algorithm == SMK_PROG_PG_RATIO && !is_dist(s) && !is_wide(s->k)) {
         // both gradients in one launch, both sums + the failure flag in a second, one 64-byte read-back
         rc = launch_grad_pg2(s->Wt, s->m, view2(s), s->Gh, s->pg_partials, s->H, s->n, view1(s), s->Gw,
-                             s->pg_partials + s->pg_half, s->k, s->scal, s->fail_flag, 5, s->st);
+                             s->pg_partials + s->pg_half, s->k, s->scal, s->fail_flag, 5, s->st,
+                             (s->o.algorithm == SMK_ALG_BPP && bpp_dual_is_gradient) ? 1 : 0);      // as the fused route: W's sum is exactly 0
         if (rc) return rc;
         pc.pin[b].fused = 1;
         SMK_HIP(hipMemcpyAsync(pc.pin[b].h, s->scal, 8 * sizeof(double), hipMemcpyDeviceToHost, s->st));

@@ -1611,6 +1611,17 @@ int smk_solver_progress(smk_solver* s, double* metric)
     return update_progress(s, s->iter > 0 ? s->iter - 1 : 0, metric);
 }
 
+// the four scalars evaluate_progress saw last and pg0: host state only, nothing is launched or read
+int smk_solver_progress_sums(const smk_solver* s, double out5[5])
+{
+    if (!s || !out5) return SMK_BAD_PARAM;
+    if (s->pc.sums_state == 0) { set_error("progress_sums: no check has been evaluated since set_factors()"); return SMK_BAD_PARAM; }
+    if (s->pc.sums_state == 2) { set_error("progress_sums: the resident RANK2 kernel returns the metric only"); return SMK_UNSUPPORTED; }
+    for (int i = 0; i < 4; ++i) out5[i] = s->pc.sums[i];
+    out5[4] = s->pc.pg0;
+    return SMK_OK;
+}
+
 int smk_solver_iteration_count(const smk_solver* s) { return s ? s->iter : 0; }
 
 static int solver_run_once(smk_solver* s, smk_stats* stats);
@@ -1699,6 +1710,7 @@ static int rank2_persist_run(smk_solver* s, int* status, int* count)
         s->iter += (int)s->r2p_pin[2];
         s->pc.pg0 = s->r2p_pin[3];
         s->pc.last_metric = s->r2p_pin[4];
+        s->pc.sums_state = 2;          // the launch returns no sums (smk_solver_progress_sums: SMK_UNSUPPORTED)
         s->normalized = false;
         s->inited = false;             // HH' and the stored products were never materialised: a later run starts from solver.Init
         s->wc_valid = false;

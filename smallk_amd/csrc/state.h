@@ -99,8 +99,13 @@ struct ProgressCheck {
     int pg_totals_slot = -1;                 // >= 0: the H-side launch has left the partial sums of this slot's check; its totals are due
     unsigned check_routes[4] = {0, 0, 0, 0}; // checks formed so far by route (smk_solver_kernel_name(2)): 1 own launches, 2 NNLS riders + totals launch, 3 riders + pass tail
     double pg0 = 1.0, last_metric = 1.0;     // the estimator: PG_RATIO's first norm, the metric last read
+    // the scalars of the check evaluated last (smk_solver_progress_sums): projected sums of W and H (PG_RATIO), ||W - Wprev||^2 and
+    // ||W||^2 (DELTA_FNORM), the pair the rule does not use reads 0; sums_state: 0 no check yet, 1 valid, 2 the resident RANK2
+    // kernel finished the run (it returns pg0 and the metric only)
+    double sums[4] = {0, 0, 0, 0};
+    int sums_state = 0;
     void reset() { pg_defer_slot = iter_snap_slot = pg_totals_slot = -1; }      // nothing deferred, nothing promised, no totals due
-    void reset_estimator() { pg0 = last_metric = 1.0; }                         // a run from the start
+    void reset_estimator() { pg0 = last_metric = 1.0; sums_state = 0; }         // a run from the start
 };
 
 struct smk_solver {

@@ -593,6 +593,14 @@ class NmfSolver:
         L.check(L.lib().smk_solver_progress(self._h, C.byref(v)), "smk_solver_progress")
         return v.value
 
+    def progress_sums(self):
+        """The scalars of the stopping-rule check evaluated last and the estimator's first norm: (projected-gradient sum of W,
+        of H, ||W - Wprev||^2, ||W||^2, pg0); the pair the rule does not use reads 0.  Host state only.  Raises
+        SmallkError(BAD_PARAM) before any check, SmallkError(UNSUPPORTED) after a run the resident RANK2 kernel finished."""
+        out = (C.c_double * 5)()
+        L.check(L.lib().smk_solver_progress_sums(self._h, out), "smk_solver_progress_sums")
+        return tuple(out)
+
     def factors(self, normalize=False):
         W = np.empty((self.A.height, self.k), order="F")
         H = np.empty((self.k, self.A.ncols), order="F")

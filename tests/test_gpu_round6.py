@@ -105,7 +105,12 @@ def test_check_totals_ride_in_the_pass_tail():
     behind it (bigprod.hip: check_totals_tail), and the host polls the pinned slot for the tag stored behind the result instead of
     waiting for an event.  SMK_PROGRESS_TAIL=0 (totals as a launch of their own), SMK_PROGRESS_POLL=0 (an event again),
     SMK_PROGRESS_DEFER=0 (the whole check as launches behind the iteration) and SMK_SYNC_PROGRESS=1 (no speculation at all) must
-    stop at the same iteration with bit-identical factors (nmf_solve_generic.hpp:98-121)."""
+    stop at the same iteration with bit-identical factors (nmf_solve_generic.hpp:98-121).
+    The tail workgroup and the totals launch add up the SAME per-workgroup sums of the H-side NNLS launch (progress.cpp: check_totals
+    hands `part` and `pg_defer_nblk` to either; 256 partials here, one per thread, the waves' sums added in index order in both), so
+    the four legs that take the riders must also report the same bits from smk_solver_progress_sums -- the projected sums of the
+    check that fired and pg0: block pivoting's W side exactly 0, the H side and pg0 positive.  tests/test_gpu_progress_sums.py holds
+    the totals launch to the host's sums of the device's factors, which anchors the tail's n-partial sum to them as well."""
     code = r"""
 import sys, os, hashlib; sys.path.insert(0, %r)
 import numpy as np, smallk_amd as g
@@ -116,25 +121,32 @@ s = g.NmfSolver(D, g.make_options(m, n, k, "BPP", min_iter=3, max_iter=200, tol=
 s.set_factors_uniform(6, 7)
 rc, iters, _ = s.run()
 W, H = s.factors(normalize=False)
-print("RESULT", rc, iters, hashlib.sha1(W.tobytes()).hexdigest(), hashlib.sha1(H.tobytes()).hexdigest(), "|", s.kernel_name(2))
+print("RESULT", rc, iters, hashlib.sha1(W.tobytes()).hexdigest(), hashlib.sha1(H.tobytes()).hexdigest(), "|", s.kernel_name(2),
+      "|", " ".join(x.hex() for x in s.progress_sums()))
 """ % ROOT
     legs = [({}, "tail of the pass"), ({"SMK_PROGRESS_TAIL": "0"}, "totals as one launch"),
             ({"SMK_PROGRESS_POLL": "0"}, "tail of the pass"), ({"SMK_PROGRESS_TAIL": "0", "SMK_PROGRESS_POLL": "0"}, "totals as one launch"),
             ({"SMK_PROGRESS_DEFER": "0"}, "launches of its own"), ({"SMK_PROGRESS_DEFER": "0", "SMK_PROGRESS_POLL": "0"}, "launches of its own"),
             ({"SMK_SYNC_PROGRESS": "1"}, "launches of its own")]
-    seen = []
+    seen, rider_sums = [], []
     for env, route in legs:
         r = subprocess.run([sys.executable, "-c", code, "0.005"], capture_output=True, text=True, cwd=ROOT, timeout=600,
                            env=dict(os.environ, **env))
         line = [l for l in r.stdout.splitlines() if l.startswith("RESULT")]
         assert r.returncode == 0 and line, r.stdout[-1500:] + r.stderr[-1500:]
-        head, how = line[0].split("|")
+        head, how, sums = line[0].split("|")
         assert route in how, (env, how)
         for other in ("tail of the pass", "totals as one launch"):
             assert other == route or other not in how, (env, how)
         seen.append(head.split()[1:])
+        if route != "launches of its own":
+            rider_sums.append((env, [float.fromhex(x) for x in sums.split()]))
     assert int(seen[0][0]) == 0 and 3 < int(seen[0][1]) < 200, seen[0]          # the rule fired, not the iteration limit
     assert all(x == seen[0] for x in seen), seen
+    print(rider_sums)
+    assert len(rider_sums) == 4 and all(x[1] == rider_sums[0][1] for x in rider_sums), rider_sums
+    sw, sh, _, _, pg0 = rider_sums[0][1]
+    assert sw == 0.0 and sh > 0.0 and pg0 > 0.0 and np.sqrt(sh) / pg0 <= 0.005, rider_sums[0]
 
 
 @pytest.mark.parametrize("shape", ["ragged", "fixed_degree", "dense", "dense_bf16"])
