@@ -68,21 +68,18 @@ class SvdOptions(C.Structure):
 NNDSVD, NNDSVDA = 0, 1
 
 
-class CdOptions(C.Structure):
-    """struct smk_cd_options: the penalties, the stopping rule and whether W is updated (0: fold-in, only H moves)."""
+class PenaltyOptions(C.Structure):
+    """struct smk_cd_options == struct smk_kl_options: the penalties, the stopping rule, whether W is updated (0: only H moves)."""
     _fields_ = [("alpha_w", C.c_double), ("alpha_h", C.c_double), ("l1_ratio", C.c_double), ("tol", C.c_double),
                 ("max_iter", C.c_int), ("update_w", C.c_int)]
+
+
+CdOptions = KlOptions = PenaltyOptions
 
 
 class CdStats(C.Structure):
     """struct smk_cd_stats: iterations run, whether the rule stopped them, the violation of iteration 1 and of the last one."""
     _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("violation_init", C.c_double), ("violation", C.c_double)]
-
-
-class KlOptions(C.Structure):
-    """struct smk_kl_options: the penalties, the stopping rule and whether W is updated (0: fold-in, only H moves)."""
-    _fields_ = [("alpha_w", C.c_double), ("alpha_h", C.c_double), ("l1_ratio", C.c_double), ("tol", C.c_double),
-                ("max_iter", C.c_int), ("update_w", C.c_int)]
 
 
 class KlStats(C.Structure):

@@ -1,9 +1,9 @@
 // smallk_amd/csrc/assign.cpp -- labels, memberships and top terms of factors that are in device memory (include/smallk_amd.h:
 // smk_labels_device, smk_top_terms_device).  The kernels (assign.hip) read a factor in its k-contiguous layout; a
-// view in any other layout is converted into a workspace first.  Every workspace belongs to an smk::Owned local of the entry and
-// is released on every path.  The solver's entries (solver.cpp: smk_solver_labels, smk_solver_top_terms) come through the same
-// two functions with the resident H and Wt, which are k-contiguous as they stand: no copy.
-#include "state.h"
+// view in any other layout is converted into a workspace first.  Every workspace belongs to the smk::Entry local of the entry
+// (entry.h: synchronised before it releases them).  The solver's entries (solver.cpp: smk_solver_labels, smk_solver_top_terms)
+// come through the same two functions with the resident H and Wt, which are k-contiguous as they stand: no copy.
+#include "entry.h"
 
 #include <string>
 
@@ -17,7 +17,7 @@ int labels_from_view(const void* H, int dtype, i64 rs, i64 cs, int k, i64 n, hip
     if (rs != 1 && k > 1) {                  // rows of H are not consecutive in memory: a compact fp64 copy, column c at c * k
         double* ws = nullptr;
         if (own.dev(&ws, (size_t)k * (size_t)n)) { set_error("labels: no memory for the workspace copy of H"); return SMK_DEVICE_ERROR; }
-        const int rc = launch_strided_convert(H, dtype, rs, cs, ws, DT_F64, 1, k, k, n, st);
+        const int rc = convert_view(DeviceView::in(H, dtype, rs, cs), DeviceView::cols(ws, k), k, n, st);
         if (rc) return rc;
         src = ws; ldc = k; dt = DT_F64;
     }
@@ -35,7 +35,7 @@ int top_terms_from_view(const void* W, int dtype, i64 rs, i64 cs, i64 m, int k, 
     if (cs != 1 && k > 1) {                  // columns of W are not consecutive in memory: a compact fp64 copy, row i at i * k
         double* ws = nullptr;
         if (own.dev(&ws, (size_t)m * (size_t)k)) { set_error("top terms: no memory for the workspace copy of W"); return SMK_DEVICE_ERROR; }
-        const int rc = launch_strided_convert(W, dtype, rs, cs, ws, DT_F64, k, 1, m, k, st);
+        const int rc = convert_view(DeviceView::in(W, dtype, rs, cs), DeviceView::rows(ws, k), m, k, st);
         if (rc) return rc;
         src = ws; ld = k; dt = DT_F64;
     }
@@ -57,11 +57,11 @@ int top_terms_from_view(const void* W, int dtype, i64 rs, i64 cs, i64 m, int k, 
 static int assign_args(const char* who, const void* factor, int dtype, int k, i64 extent, const char* extent_name)
 {
     const std::string w(who);
-    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = require_init()) return rc;
     if (!factor) { set_error(w + ": null factor"); return SMK_BAD_PARAM; }
     if (k < 1) { set_error(w + ": k < 1"); return SMK_BAD_PARAM; }
     if (extent < 1) { set_error(w + ": " + extent_name + " < 1"); return SMK_BAD_PARAM; }
-    if (dtype != SMK_DT_F64 && dtype != SMK_DT_F32) { set_error(w + ": factors are fp64 or fp32"); return SMK_BAD_PARAM; }
+    if (!is_factor_dtype(dtype)) { set_error(w + ": factors are fp64 or fp32"); return SMK_BAD_PARAM; }
     if (k > MAX_K) { set_error(w + ": device path supports k <= 2048"); return SMK_UNSUPPORTED; }
     return SMK_OK;
 }
@@ -80,11 +80,10 @@ int smk_labels_device(const void* H, int dtype, int64_t rsH, int64_t csH, int k,
     if (!rc) rc = check_device_view(labels, DT_F32, n, 1, 1, n, true, "smk_labels_device(labels)");
     if (!rc && memberships) rc = check_device_view(memberships, DT_F32, k, n, 1, k, true, "smk_labels_device(memberships)");
     if (rc) return rc;
-    Owned own;
-    hipStream_t st = ctx().stream;
-    rc = join_caller_stream(own, st, stream);
+    Entry e(ctx().stream);
+    rc = e.join(stream);
     if (rc) return rc;
-    return labels_from_view(H, dtype, rsH, csH, k, n, st, own, labels, memberships);
+    return e.synced(labels_from_view(H, dtype, rsH, csH, k, n, e.st, e.own, labels, memberships));
 }
 
 int smk_top_terms_device(const void* W, int dtype, int64_t rsW, int64_t csW, int64_t m, int k, int maxterms, void* stream, void* term_indices)
@@ -97,11 +96,10 @@ int smk_top_terms_device(const void* W, int dtype, int64_t rsW, int64_t csW, int
     rc = check_device_view(W, dtype, m, k, rsW, csW, false, "smk_top_terms_device(W)");
     if (!rc) rc = check_device_view(term_indices, DT_F32, maxterms, k, 1, maxterms, true, "smk_top_terms_device(term_indices)");
     if (rc) return rc;
-    Owned own;
-    hipStream_t st = ctx().stream;
-    rc = join_caller_stream(own, st, stream);
+    Entry e(ctx().stream);
+    rc = e.join(stream);
     if (rc) return rc;
-    return top_terms_from_view(W, dtype, rsW, csW, m, k, maxterms, st, own, term_indices);
+    return e.synced(top_terms_from_view(W, dtype, rsW, csW, m, k, maxterms, e.st, e.own, term_indices));
 }
 
 }  // extern "C"

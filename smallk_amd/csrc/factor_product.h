@@ -18,10 +18,10 @@ struct FactorProduct {
     int ng = 0;
 };
 
-// plans and workspaces (blocks of `own`); a, l, KP and st are set by the caller.  who: the prefix of the error texts.
-static inline int factor_product_alloc(FactorProduct& f, Owned& own, const char* who)
+// the product's matrix, rank, pitch and stream, its plans and workspaces (blocks of `own`).  who: the prefix of the error texts.
+static inline int factor_product_alloc(FactorProduct& f, const smk_matrix* a, int l, int KP, hipStream_t st, Owned& own, const char* who)
 {
-    const smk_matrix* a = f.a;
+    f.a = a; f.l = l; f.KP = KP; f.st = st;
     const std::string w(who);
     if (!a->sparse) {
         // one P layout for both directions and all groups: KP doubles per column, so the summed product IS a factor

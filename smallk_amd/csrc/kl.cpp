@@ -2,10 +2,10 @@
 // updates (include/smallk_amd.h: smk_nmf_kl_device, smk_matrix_kl_divergence_device): scikit-learn's solver="mu",
 // beta_loss="kullback-leibler".  A driver by itself, beside the solver's schedules and beside cd.cpp: each half-iteration is one
 // sweep of kl.hip over the stored entries (CSC(A) for H, CSC(A') for W), the denominators are the row sums of the other factor.
-// The entries are synchronous; every workspace belongs to an smk::Owned local of the entry and is released on every path; of the
-// matrix handle only the once-per-matrix records are written (segment plans, duplicate record, sign record).  W and H are written
-// once, at the end: on any error they are untouched.
-#include "state.h"
+// The entries are synchronous; every workspace and local segment plan belongs to the smk::Entry local of the entry (entry.h:
+// synchronised before it releases them, on every path); of the matrix handle only the once-per-matrix records are written
+// (segment plans, duplicate record, sign record).  W and H are written once, at the end: on any error they are untouched.
+#include "entry.h"
 
 #include <cmath>
 #include <mutex>
@@ -15,15 +15,12 @@ namespace smk {
 
 struct KlRun {
     const smk_matrix* a = nullptr;
-    int k = 0, KP = 0;
-    hipStream_t st = nullptr;
+    FactorPair f;                                 // the factors: Wt KP x m and H KP x n, k, KP, the stream
     const SegPlan *spA = nullptr, *spAt = nullptr;
-    SegPlan localA, localAt;                      // a matrix without plans (SMK_SPMM_SEG=0) gets them for this call
-    double *Wt = nullptr, *H = nullptr;           // the factors: KP x m and KP x n
     double *sumsW = nullptr, *sumsH = nullptr, *part = nullptr, *piecesA = nullptr, *piecesAt = nullptr, *divpart = nullptr, *out4 = nullptr;
     double* pin = nullptr;                        // the pinned slot the host reads the divergence from (4 doubles)
     int entry_passes = 0, divergence_passes = 0;
-    ~KlRun() { free_seg_plan(&localA); free_seg_plan(&localAt); }
+    KlRun(const smk_matrix* a_, int k) : a(a_), f{a_->m, a_->n, k, kp_of(k), matrix_stream(a_)} {}
 };
 
 // the last run of the calling thread (smk_kl_last_profile)
@@ -49,62 +46,44 @@ static int kl_matrix_checks(const smk_matrix* a, const std::string& w)
     return 0;
 }
 
-static int kl_plans(KlRun& r)
+static int kl_plans(KlRun& r, Entry& e)
 {
-    const smk_matrix* a = r.a;
-    ensure_seg_plans(a);
-    r.spA = &a->segA;
-    r.spAt = &a->segAt;
-    if (!r.spA->rowflag || r.spA->ncols != a->n) {
-        const int rc = build_seg_plan(a->n, a->nnz, a->colptr, a->rowidx, &r.localA, r.st);
-        if (rc) return rc;
-        r.spA = &r.localA;
-    }
-    if (!r.spAt->rowflag || r.spAt->ncols != a->m) {
-        const int rc = build_seg_plan(a->m, a->nnz, a->colptr_t, a->rowidx_t, &r.localAt, r.st);
-        if (rc) return rc;
-        r.spAt = &r.localAt;
-    }
-    return 0;
+    const int rc = seg_plan_or_local(r.a, false, e.st, &e.planA, &r.spA);
+    return rc ? rc : seg_plan_or_local(r.a, true, e.st, &e.planAt, &r.spAt);
 }
 
-// the zeroed factor workspaces (pad rows of the resident layout are zeros), the views converted in, the sums' and the sweeps' scratch
-static int kl_setup(KlRun& r, Owned& own, bool sweeps, const void* W, int dtW, i64 rsW, i64 csW, const void* H, int dtH, i64 rsH, i64 csH,
-                    const char* who)
+// the plans, the sums' and the sweeps' scratch, the zeroed factor workspaces and the views converted in
+static int kl_setup(KlRun& r, Entry& e, bool sweeps, const DeviceView& W, const DeviceView& H, const std::string& who)
 {
-    const smk_matrix* a = r.a;
-    const i64 nmax = a->m > a->n ? a->m : a->n;
-    int rc = kl_plans(r);
+    Owned& own = e.own;
+    const int KP = r.f.KP;
+    const i64 nmax = r.a->m > r.a->n ? r.a->m : r.a->n;
+    int rc = kl_plans(r, e);
     if (rc) return rc;
-    rc = own.dev(&r.Wt, (size_t)r.KP * a->m);
-    if (!rc) rc = own.dev(&r.H, (size_t)r.KP * a->n);
-    if (!rc) rc = own.dev(&r.sumsW, (size_t)r.KP);
-    if (!rc) rc = own.dev(&r.sumsH, (size_t)r.KP);
-    if (!rc) rc = own.dev(&r.part, (size_t)kl_sums_blocks(nmax) * r.KP);
+    rc = own.dev(&r.sumsW, (size_t)KP);
+    if (!rc) rc = own.dev(&r.sumsH, (size_t)KP);
+    if (!rc) rc = own.dev(&r.part, (size_t)kl_sums_blocks(nmax) * KP);
     if (!rc) rc = own.dev(&r.divpart, (size_t)2 * (r.spA->nseg > 0 ? r.spA->nseg : 1));
     if (!rc) rc = own.dev(&r.out4, 4);
     if (!rc) rc = own.pinned((void**)&r.pin, 4 * sizeof(double));
-    if (!rc && sweeps && r.spA->npieces > 0) rc = own.dev(&r.piecesA, (size_t)r.spA->npieces * r.KP);
-    if (!rc && sweeps && r.spAt->npieces > 0) rc = own.dev(&r.piecesAt, (size_t)r.spAt->npieces * r.KP);
-    if (rc) { set_error(std::string(who) + ": no memory for the factor workspace"); return SMK_DEVICE_ERROR; }
-    SMK_HIP(hipMemsetAsync(r.Wt, 0, (size_t)r.KP * a->m * sizeof(double), r.st));
-    SMK_HIP(hipMemsetAsync(r.H, 0, (size_t)r.KP * a->n * sizeof(double), r.st));
-    rc = launch_strided_convert(W, dtW, rsW, csW, r.Wt, DT_F64, r.KP, 1, a->m, r.k, r.st);
-    if (!rc) rc = launch_strided_convert(H, dtH, rsH, csH, r.H, DT_F64, 1, r.KP, r.k, a->n, r.st);
-    return rc;
+    if (!rc && sweeps && r.spA->npieces > 0) rc = own.dev(&r.piecesA, (size_t)r.spA->npieces * KP);
+    if (!rc && sweeps && r.spAt->npieces > 0) rc = own.dev(&r.piecesAt, (size_t)r.spAt->npieces * KP);
+    if (rc) { set_error(who + ": no memory for the factor workspace"); return SMK_DEVICE_ERROR; }
+    rc = r.f.alloc_zeroed(own, who);
+    return rc ? rc : r.f.load(W, H);
 }
 
-static int kl_sums_w(KlRun& r) { return launch_kl_factor_sums(r.Wt, r.k, r.a->m, r.part, r.sumsW, r.st); }
-static int kl_sums_h(KlRun& r) { return launch_kl_factor_sums(r.H, r.k, r.a->n, r.part, r.sumsH, r.st); }
+static int kl_sums_w(KlRun& r) { return launch_kl_factor_sums(r.f.Wt, r.f.k, r.a->m, r.part, r.sumsW, r.f.st); }
+static int kl_sums_h(KlRun& r) { return launch_kl_factor_sums(r.f.H, r.f.k, r.a->n, r.part, r.sumsH, r.f.st); }
 
 // out[0 .. 3] = D, sum a log(a / d), sum WH, sum a of the current factors (their row sums in place), through the pinned slot: one
 // synchronisation
 static int kl_divergence(KlRun& r, double* out)
 {
     ++r.divergence_passes;
-    const int rc = launch_kl_divergence(*r.spA, r.a->colptr, r.a->val, r.Wt, r.H, r.k, r.sumsW, r.sumsH, r.divpart, r.out4, r.pin, r.st);
+    const int rc = launch_kl_divergence(*r.spA, r.a->colptr, r.a->val, r.f.Wt, r.f.H, r.f.k, r.sumsW, r.sumsH, r.divpart, r.out4, r.pin, r.f.st);
     if (rc) return rc;
-    SMK_HIP(hipStreamSynchronize(r.st));
+    SMK_HIP(hipStreamSynchronize(r.f.st));
     for (int i = 0; i < 4; ++i) out[i] = r.pin[i];
     return 0;
 }
@@ -121,9 +100,8 @@ static int kl_error(KlRun& r, double* err)
 static int kl_loop(KlRun& r, const smk_kl_options& o, smk_kl_stats* stats)
 {
     const smk_matrix* a = r.a;
-    const double m = (double)a->m, n = (double)a->n;
-    const double l1h = m * o.alpha_h * o.l1_ratio, l2h = m * o.alpha_h * (1.0 - o.l1_ratio);
-    const double l1w = n * o.alpha_w * o.l1_ratio, l2w = n * o.alpha_w * (1.0 - o.l1_ratio);
+    const FactorPair& f = r.f;
+    const Penalties p(a->m, a->n, o.alpha_w, o.alpha_h, o.l1_ratio);
     int rc = kl_sums_w(r);                      // update_w = 0: formed once
     if (!rc) rc = kl_sums_h(r);
     double error_init = 0.0;
@@ -133,11 +111,11 @@ static int kl_loop(KlRun& r, const smk_kl_options& o, smk_kl_stats* stats)
     int checked = 0, it = 0, converged = 0;
     for (it = 1; it <= o.max_iter; ++it) {
         ++r.entry_passes;
-        rc = launch_kl_step(*r.spA, a->colptr, a->val, r.Wt, r.H, r.k, r.sumsW, 0, l1h, l2h, 0, r.piecesA, r.st);
+        rc = launch_kl_step(*r.spA, a->colptr, a->val, f.Wt, f.H, f.k, r.sumsW, 0, p.l1h, p.l2h, 0, r.piecesA, f.st);
         if (!rc && o.update_w) {
             rc = kl_sums_h(r);
             ++r.entry_passes;
-            if (!rc) rc = launch_kl_step(*r.spAt, a->colptr_t, a->val_t, r.H, r.Wt, r.k, r.sumsH, 1, l1w, l2w, 1, r.piecesAt, r.st);
+            if (!rc) rc = launch_kl_step(*r.spAt, a->colptr_t, a->val_t, f.H, f.Wt, f.k, r.sumsH, 1, p.l1w, p.l2w, 1, r.piecesAt, f.st);
             if (!rc) rc = kl_sums_w(r);
         }
         if (rc) return rc;
@@ -163,17 +141,14 @@ static int kl_loop(KlRun& r, const smk_kl_options& o, smk_kl_stats* stats)
     return 0;
 }
 
-static bool kl_dtype(int dt) { return dt == SMK_DT_F64 || dt == SMK_DT_F32; }
-
 // what both entries check first
 static int kl_args(const std::string& w, const smk_matrix* a, int k, const void* W, int dtW, const void* H, int dtH)
 {
-    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = require_init()) return rc;
     if (!a || !W || !H) { set_error(w + ": null argument"); return SMK_BAD_PARAM; }
     if (k < 1) { set_error(w + ": k < 1"); return SMK_BAD_PARAM; }
     if (k > a->m || k > a->n_global) { set_error(w + ": k exceeds min(m, n)"); return SMK_BAD_PARAM; }
-    if (!kl_dtype(dtW) || !kl_dtype(dtH)) { set_error(w + ": W and H are fp64 or fp32"); return SMK_BAD_PARAM; }
-    return 0;
+    return check_factor_dtypes(w, "W and H", dtW, dtH);
 }
 
 static int kl_supported(const std::string& w, const smk_matrix* a, int k)
@@ -195,31 +170,23 @@ int smk_nmf_kl_device(const smk_matrix* a, int k, const smk_kl_options* o, void*
     int rc = kl_args(w, a, k, W, dtW, H, dtH);
     if (rc) return rc;
     if (!o || !stats) { set_error(w + ": null argument"); return SMK_BAD_PARAM; }
-    if (!(o->alpha_w >= 0.0) || !(o->alpha_h >= 0.0)) { set_error(w + ": alpha_w and alpha_h must be >= 0"); return SMK_BAD_PARAM; }
-    if (!(o->l1_ratio >= 0.0 && o->l1_ratio <= 1.0)) { set_error(w + ": l1_ratio must lie in [0, 1]"); return SMK_BAD_PARAM; }
-    if (!(o->tol >= 0.0)) { set_error(w + ": tol must be >= 0"); return SMK_BAD_PARAM; }
-    if (o->max_iter < 1) { set_error(w + ": max_iter < 1"); return SMK_BAD_PARAM; }
-    rc = kl_supported(w, a, k);
+    rc = check_penalties(w, o->alpha_w, o->alpha_h, o->l1_ratio, o->tol, o->max_iter);
+    if (!rc) rc = kl_supported(w, a, k);
     if (rc) return rc;
-    rc = check_device_view(W, dtW, a->m, k, rsW, csW, o->update_w != 0, "smk_nmf_kl_device(W)");
-    if (!rc) rc = check_device_view(H, dtH, k, a->n, rsH, csH, true, "smk_nmf_kl_device(H)");
+    KlRun r(a, k);
+    const DeviceView vW{W, dtW, rsW, csW}, vH{H, dtH, rsH, csH};
+    rc = r.f.check(w, vW, vH, o->update_w != 0, true);
     if (rc) return rc;
-    Owned own;
-    KlRun r;
-    r.a = a;
-    r.k = k;
-    r.KP = kp_of(k);
-    r.st = a->st ? a->st : ctx().stream;
-    rc = join_caller_stream(own, r.st, stream);
-    if (!rc) rc = kl_setup(r, own, true, W, dtW, rsW, csW, H, dtH, rsH, csH, "smk_nmf_kl_device");
+    Entry e(r.f.st);
+    rc = e.join(stream);
+    if (!rc) rc = kl_setup(r, e, true, vW, vH, w);
     smk_kl_stats st{};
     if (!rc) rc = kl_loop(r, *o, &st);
     g_kl_entry_passes = r.entry_passes;
     g_kl_divergence_passes = r.divergence_passes;
-    if (!rc && o->update_w) rc = launch_strided_convert(r.Wt, DT_F64, r.KP, 1, W, dtW, rsW, csW, a->m, k, r.st);
-    if (!rc) rc = launch_strided_convert(r.H, DT_F64, 1, r.KP, H, dtH, rsH, csH, k, a->n, r.st);
-    if (rc) { (void)hipStreamSynchronize(r.st); return rc; }        // the local plans are freed on return
-    SMK_HIP(hipStreamSynchronize(r.st));
+    if (!rc) rc = r.f.store(o->update_w ? &vW : nullptr, &vH);
+    if (!rc) rc = e.sync();
+    if (rc) return rc;
     *stats = st;
     return SMK_OK;
 }
@@ -233,22 +200,18 @@ int smk_matrix_kl_divergence_device(const smk_matrix* a, int k, const void* W, i
     if (!out) { set_error(w + ": null output"); return SMK_BAD_PARAM; }
     rc = kl_supported(w, a, k);
     if (rc) return rc;
-    rc = check_device_view(W, dtW, a->m, k, rsW, csW, false, "smk_matrix_kl_divergence_device(W)");
-    if (!rc) rc = check_device_view(H, dtH, k, a->n, rsH, csH, false, "smk_matrix_kl_divergence_device(H)");
+    KlRun r(a, k);
+    const DeviceView vW = DeviceView::in(W, dtW, rsW, csW), vH = DeviceView::in(H, dtH, rsH, csH);
+    rc = r.f.check(w, vW, vH, false, false);
     if (rc) return rc;
-    Owned own;
-    KlRun r;
-    r.a = a;
-    r.k = k;
-    r.KP = kp_of(k);
-    r.st = a->st ? a->st : ctx().stream;
-    rc = join_caller_stream(own, r.st, stream);
-    if (!rc) rc = kl_setup(r, own, false, W, dtW, rsW, csW, H, dtH, rsH, csH, "smk_matrix_kl_divergence_device");
+    Entry e(r.f.st);
+    rc = e.join(stream);
+    if (!rc) rc = kl_setup(r, e, false, vW, vH, w);
     if (!rc) rc = kl_sums_w(r);
     if (!rc) rc = kl_sums_h(r);
     double d[4] = {0.0, 0.0, 0.0, 0.0};
-    if (!rc) rc = kl_divergence(r, d);
-    if (rc) { (void)hipStreamSynchronize(r.st); return rc; }
+    if (!rc) rc = e.synced(kl_divergence(r, d));
+    if (rc) return rc;
     out[0] = d[0];
     out[1] = d[1];
     out[2] = d[2];
@@ -258,17 +221,16 @@ int smk_matrix_kl_divergence_device(const smk_matrix* a, int k, const void* W, i
 int smk_kl_step_time(const smk_matrix* a, int which, int k, int reps, double* ms)
 {
     const std::string w("smk_kl_step_time");
-    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = require_init()) return rc;
     if (!a || !ms || which < 0 || which > 3 || k < 1 || reps < 1) { set_error(w + ": bad argument"); return SMK_BAD_PARAM; }
     int rc = kl_supported(w, a, k);
     if (rc) return rc;
-    Owned own;
-    KlRun r;
-    r.a = a;
-    r.k = k;
-    r.KP = kp_of(k);
-    r.st = a->st ? a->st : ctx().stream;
-    rc = kl_plans(r);
+    KlRun r(a, k);
+    Entry e(r.f.st);
+    Owned& own = e.own;
+    const hipStream_t st = e.st;
+    const int KP = r.f.KP;
+    rc = kl_plans(r, e);
     if (rc) return rc;
     const bool over_rows = which == 1 || which == 3;          // the W side: CSC(A'), H gathered
     const SegPlan& sp = over_rows ? *r.spAt : *r.spA;
@@ -276,33 +238,21 @@ int smk_kl_step_time(const smk_matrix* a, int which, int k, int reps, double* ms
     const i64* colptr = over_rows ? a->colptr_t : a->colptr;
     const double* val = over_rows ? a->val_t : a->val;
     double *G = nullptr, *X = nullptr, *sums = nullptr, *part = nullptr, *pieces = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    rc = own.dev(&G, (size_t)r.KP * ng);
-    if (!rc) rc = own.dev(&X, (size_t)r.KP * nx);
-    if (!rc) rc = own.dev(&sums, (size_t)r.KP);
-    if (!rc) rc = own.dev(&part, (size_t)kl_sums_blocks(ng) * r.KP);
+    rc = own.dev(&G, (size_t)KP * ng);
+    if (!rc) rc = own.dev(&X, (size_t)KP * nx);
+    if (!rc) rc = own.dev(&sums, (size_t)KP);
+    if (!rc) rc = own.dev(&part, (size_t)kl_sums_blocks(ng) * KP);
     if (!rc) rc = own.dev(&pieces, (size_t)(sp.npieces > 0 ? sp.npieces : 1) * 128);
-    if (!rc) rc = own.event(&e0, hipEventDefault);
-    if (!rc) rc = own.event(&e1, hipEventDefault);
     if (rc) { set_error(w + ": no device memory"); return SMK_DEVICE_ERROR; }
-    rc = launch_fill_factor_uniform(G, k, ng, 11, 0, r.st);
-    if (!rc) rc = launch_fill_factor_uniform(X, k, nx, 12, 0, r.st);
-    if (!rc) rc = launch_kl_factor_sums(G, k, ng, part, sums, r.st);
-    auto once = [&]() -> int {
-        if (which <= 1) return launch_kl_step(sp, colptr, val, G, X, k, sums, which, 0.0, 0.0, which, pieces, r.st);
-        const int prc = launch_spmm_seg(sp, colptr, val, G, k, X, r.KP, r.st, pieces);
-        return prc < 0 ? prc : 0;
-    };
-    for (int i = 0; i < 3 && !rc; ++i) rc = once();         // warm-up: the code object
-    if (!rc && hipEventRecord(e0, r.st) != hipSuccess) rc = SMK_DEVICE_ERROR;
-    for (int i = 0; i < reps && !rc; ++i) rc = once();
-    if (!rc && hipEventRecord(e1, r.st) != hipSuccess) rc = SMK_DEVICE_ERROR;
-    (void)hipStreamSynchronize(r.st);                       // the local plans are freed on return
+    rc = launch_fill_factor_uniform(G, k, ng, 11, 0, st);
+    if (!rc) rc = launch_fill_factor_uniform(X, k, nx, 12, 0, st);
+    if (!rc) rc = launch_kl_factor_sums(G, k, ng, part, sums, st);
     if (rc) return rc;
-    float t = 0.f;
-    SMK_HIP(hipEventElapsedTime(&t, e0, e1));
-    *ms = (double)t / reps;
-    return SMK_OK;
+    return e.synced(time_launches(w, own, st, reps, [&]() -> int {
+        if (which <= 1) return launch_kl_step(sp, colptr, val, G, X, k, sums, which, 0.0, 0.0, which, pieces, st);
+        const int prc = launch_spmm_seg(sp, colptr, val, G, k, X, KP, st, pieces);
+        return prc < 0 ? prc : 0;
+    }, ms));
 }
 
 int smk_kl_last_profile(int* entry_passes, int* divergence_passes)

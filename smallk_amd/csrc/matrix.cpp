@@ -1,7 +1,7 @@
 // smallk_amd/csrc/matrix.cpp -- the resident matrix of the C ABI (include/smallk_amd.h): dense A with or without its
 // stored transpose, sparse A as CSC(A) + CSC(A'), uploads, fills, column subsets, and the parts built on first use
 // (stored transpose of a single copy, segment plans, scale and norms, host copy of the CSC).
-#include "state.h"
+#include "entry.h"
 
 #include <cmath>
 #include <cstdio>
@@ -31,7 +31,7 @@ int matrix_materialize_transpose(const smk_matrix* ca)
     std::lock_guard<std::mutex> lk(mu);
     if (!a->single || a->At) return 0;
     const size_t es = (size_t)elem_size(a->storage);
-    hipStream_t st = a->st ? a->st : ctx().stream;
+    hipStream_t st = matrix_stream(a);
     if (a->own.dev((unsigned char**)&a->At, (size_t)a->ldAt * a->colsAt * es)) { set_error("no memory for the stored transpose of a single-copy matrix"); return SMK_DEVICE_ERROR; }
     SMK_HIP(hipMemsetAsync(a->At, 0, (size_t)a->ldAt * a->colsAt * es, st));
     const int rc = launch_transpose_store(a->A, a->ldA, a->At, a->ldAt, a->storage, a->m, a->n, st);
@@ -49,7 +49,7 @@ int ensure_seg_plans(const smk_matrix* a)
     if (a->seg_tried) return 0;
     a->seg_tried = true;
     const bool seg_on = sw::spmm_seg();
-    hipStream_t bst = a->st ? a->st : ctx().stream;
+    hipStream_t bst = matrix_stream(a);
     if (seg_on && (build_seg_plan(a->n, a->nnz, a->colptr, a->rowidx, &a->segA, bst) ||
                    build_seg_plan(a->m, a->nnz, a->colptr_t, a->rowidx_t, &a->segAt, bst))) {
         free_seg_plan(&a->segA);
@@ -175,7 +175,7 @@ int smk_matrix_create(smk_matrix** out, int64_t height, int64_t width_global, in
 {
     if (!out) return SMK_BAD_PARAM;
     *out = nullptr;
-    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = require_init()) return rc;
     if (height <= 0 || width_global <= 0 || ncols_local <= 0 || col0 < 0 || col0 + ncols_local > width_global ||
         (storage != SMK_STORE_F32 && storage != SMK_STORE_BF16))
         return SMK_BAD_PARAM;
@@ -370,7 +370,7 @@ int smk_matrix_create_sparse_device(smk_matrix** out, int64_t height, int64_t wi
 {
     if (!out) return SMK_BAD_PARAM;
     *out = nullptr;
-    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = require_init()) return rc;
     if (height <= 0 || width <= 0 || nnz <= 0 || height > 0xFFFFFFFFll) { set_error("smk_matrix_create_sparse_device: empty or oversized matrix"); return SMK_BAD_PARAM; }
     if ((idx_type != SMK_IDX_I32 && idx_type != SMK_IDX_I64) || (row_idx_type != SMK_IDX_I32 && row_idx_type != SMK_IDX_I64)) {
         set_error("smk_matrix_create_sparse_device: unknown index type");
@@ -426,7 +426,7 @@ int smk_matrix_clone(const smk_matrix* src, smk_matrix** out)
 {
     if (!src || !out) return SMK_BAD_PARAM;
     *out = nullptr;
-    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = require_init()) return rc;
     smk_matrix* a = new_matrix(src->m, src->n_global, src->c0, src->n, src->storage, src->sparse, src->nnz);
     a->ascale = src->ascale; a->col_spread_log2 = src->col_spread_log2;
     a->colnorm_max = src->colnorm_max; a->rownorm_max = src->rownorm_max;
@@ -481,7 +481,7 @@ int smk_matrix_sparse_product(const smk_matrix* a, int transposed, int k, const 
     const int KP = kp_of(k);
     const int kpp = (k <= 2) ? 2 : KP;
     const int ldx_dev = (k <= 2) ? 2 : KP;
-    hipStream_t st = a->st ? a->st : ctx().stream;
+    hipStream_t st = matrix_stream(a);
     if (k > 2 && !is_wide(k)) ensure_seg_plans(a);
     std::vector<double> xp((size_t)rows * ldx_dev, 0.0), pp((size_t)ncols * kpp);
     for (i64 r = 0; r < rows; ++r)
@@ -540,7 +540,7 @@ int smk_matrix_create_sparse(smk_matrix** out, int64_t height, int64_t width_glo
 {
     if (!out) return SMK_BAD_PARAM;
     *out = nullptr;
-    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = require_init()) return rc;
     if (height <= 0 || width_global <= 0 || ncols_local <= 0 || col0 < 0 || col0 + ncols_local > width_global ||
         nnz < 0 || !col_offsets || (nnz > 0 && (!row_indices || !data)))
         return SMK_BAD_PARAM;
@@ -594,7 +594,7 @@ int matrix_create_sparse_device(smk_matrix** out, i64 height, i64 width, i64 nnz
 {
     if (!out) return SMK_BAD_PARAM;
     *out = nullptr;
-    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = require_init()) return rc;
     if (height <= 0 || width <= 0 || nnz < 0) { set_error("empty matrix"); return SMK_BAD_PARAM; }
     smk_matrix* a = new_matrix(height, width, 0, width, SMK_STORE_F32, true, nnz);
     if (alloc_csc(a)) { smk_matrix_destroy(a); return SMK_DEVICE_ERROR; }

@@ -16,6 +16,7 @@
 
 #include "../../include/smallk_amd.h"
 #include "common.h"
+#include "entry.h"
 #include "owned.h"
 #include "preprocess.h"
 #include "preprocess_result.h"
@@ -266,9 +267,8 @@ int smk_preprocess(const smk_preprocess_options* opts, unsigned height, unsigned
 {
     if (!out) return SMK_BAD_PARAM;
     *out = nullptr;
-    bool init = false;
-    hipStream_t st = smk::context_stream(&init);
-    if (!init) { smk::set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = smk::require_init()) return rc;
+    hipStream_t st = smk::context_stream(nullptr);
     if (!opts || height == 0 || width == 0 || !col_offsets || (nnz > 0 && (!row_indices || !data))) return SMK_BAD_PARAM;
     if ((int64_t)col_offsets[width] - (int64_t)col_offsets[0] != (int64_t)nnz) { smk::set_error("col_offsets do not span nnz"); return SMK_BAD_PARAM; }
     if (nnz > 0x7FFFFFFFu) { smk::set_error("preprocess: more than 2^31 - 1 entries"); return SMK_SIZE_TOO_LARGE; }

@@ -13,6 +13,7 @@
 //   P1 : S1 slabs of n_pad x kpp fp64 = W'A partials,   P2 : S2 slabs of m_pad x kpp = (AH')' partials
 //   packW / packH : MFMA operand fragments of W' / H
 #include "solver_internal.h"
+#include "entry.h"
 #include "check_ring.h"
 #include "comm.h"
 #include "switches.h"
@@ -148,7 +149,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
 {
     if (!out) return SMK_BAD_PARAM;
     *out = nullptr;
-    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = require_init()) return rc;
     if (!opts || !a) return SMK_BAD_PARAM;
     if (!smk_is_valid(opts, 1)) return SMK_BAD_PARAM;
     if (opts->height != a->m || opts->width != a->n_global) { set_error("options/matrix dimension mismatch"); return SMK_BAD_PARAM; }
@@ -166,13 +167,13 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
     s->kpp = kpp_of(s->k);
     s->m = a->m;
     s->n = a->n;
-    s->st = a->st ? a->st : ctx().stream;
+    s->st = matrix_stream(a);
     const sw::Maybe<int> env = sw::nsplit();
     static_assert(ALG_MU == SMK_ALG_MU && ALG_HALS == SMK_ALG_HALS && ALG_RANK2 == SMK_ALG_RANK2 && ALG_BPP == SMK_ALG_BPP, "bigprod_plan.h");
     // the product form (bigprod_plan.h: default_product_form).  Its last rule needs the spread of A's column scales, measured once
     // per matrix where the rule can apply
     if (!env.set && !a->sparse && opts->algorithm != SMK_ALG_RANK2 && a->col_spread_log2 < 0) {
-        const int rc0 = matrix_measure_scale(a, a->st ? a->st : ctx().stream);
+        const int rc0 = matrix_measure_scale(a, matrix_stream(a));
         if (rc0) { --ctx().live_solvers; delete s; return rc0; }
     }
     s->nsplit = resolve_product_form(opts->algorithm, opts->k, a->storage, a->sparse, a->m * a->n_global, a->col_spread_log2,
@@ -188,7 +189,7 @@ int smk_solver_create(smk_solver** out, const smk_options* opts, const smk_matri
             if (!a->blocked_tried) {
                 a->blocked_tried = true;
                 const int b1 = blocked_csc_blocks(a->m), b2 = blocked_csc_blocks(a->n);
-                hipStream_t bst = a->st ? a->st : ctx().stream;
+                hipStream_t bst = matrix_stream(a);
                 if (b1 > 1) (void)build_blocked_csc(a->m, a->n, a->nnz, a->colptr, a->rowidx, a->val, b1, &a->bA, bst);
                 if (b2 > 1) (void)build_blocked_csc(a->n, a->m, a->nnz, a->colptr_t, a->rowidx_t, a->val_t, b2, &a->bAt, bst);
             }
@@ -474,20 +475,15 @@ static int factors_end(smk_solver* s)
     return SMK_OK;
 }
 
-// pad rows of the KP x N device layout must be (and stay) zero
-static int factors_clear(smk_solver* s)
-{
-    SMK_HIP(hipMemsetAsync(s->Wt, 0, (size_t)s->KP * s->m * sizeof(double), s->st));
-    SMK_HIP(hipMemsetAsync(s->H, 0, (size_t)s->KP * s->n * sizeof(double), s->st));
-    return 0;
-}
+// the solver's resident factors as the pair the view entries convert into and out of (entry.h): buffers the pair does not own
+static FactorPair resident_pair(const smk_solver* s) { return {s->m, s->n, s->k, s->KP, s->st, s->Wt, s->H}; }
 
 int smk_solver_set_factors(smk_solver* s, const double* W0, int64_t ldW, const double* H0, int64_t ldH)
 {
     if (!s || !W0 || !H0) return SMK_BAD_PARAM;
     if (ldW < s->m || ldH < s->k) { set_error("leading dimension too small"); return SMK_BAD_PARAM; }
     int rc = factors_begin(s);
-    if (!rc) rc = factors_clear(s);
+    if (!rc) rc = resident_pair(s).zero();
     if (rc) return rc;
     // W0 (m x k, host) -> tmpW (m x k, ld m) -> Wt (KP x m)
     SMK_HIP(hipMemcpy2DAsync(s->tmpW, (size_t)s->m * sizeof(double), W0, (size_t)ldW * sizeof(double),
@@ -499,27 +495,26 @@ int smk_solver_set_factors(smk_solver* s, const double* W0, int64_t ldW, const d
     return factors_end(s);
 }
 
-static bool factor_dtype(int dt) { return dt == SMK_DT_F64 || dt == SMK_DT_F32; }
-
 // The same start from views in device memory (a torch tensor's data_ptr and strides): W0 is m x k, H0 is k x n.  The strided
 // convert kernel writes Wt (KP x m) and H (KP x n) directly -- a row-major W0 already has the layout of Wt with pitch k instead
 // of KP, so it is a straight copy, with no pass through tmpW.
 int smk_solver_set_factors_device(smk_solver* s, const void* W0, int dtypeW, int64_t rsW, int64_t csW, const void* H0, int dtypeH,
                                   int64_t rsH, int64_t csH, void* stream)
 {
+    const char* who = "smk_solver_set_factors_device";
     if (!s) return SMK_BAD_PARAM;
-    if (!factor_dtype(dtypeW) || !factor_dtype(dtypeH)) { set_error("smk_solver_set_factors_device: factors are fp64 or fp32"); return SMK_BAD_PARAM; }
-    int rc = check_device_view(W0, dtypeW, s->m, s->k, rsW, csW, false, "smk_solver_set_factors_device(W0)");
-    if (!rc) rc = check_device_view(H0, dtypeH, s->k, s->n, rsH, csH, false, "smk_solver_set_factors_device(H0)");
+    const FactorPair f = resident_pair(s);
+    const DeviceView vW = DeviceView::in(W0, dtypeW, rsW, csW), vH = DeviceView::in(H0, dtypeH, rsH, csH);
+    int rc = check_factor_dtypes(who, "factors", dtypeW, dtypeH);
+    if (!rc) rc = f.check(who, vW, vH, false, false, "W0", "H0");
     if (rc) return rc;
-    Owned own;
-    rc = join_caller_stream(own, s->st, stream);
+    Entry e(s->st);
+    rc = e.join(stream);
     if (!rc) rc = factors_begin(s);
-    if (!rc) rc = factors_clear(s);
-    if (!rc) rc = launch_strided_convert(W0, dtypeW, rsW, csW, s->Wt, DT_F64, s->KP, 1, s->m, s->k, s->st);
-    if (!rc) rc = launch_strided_convert(H0, dtypeH, rsH, csH, s->H, DT_F64, 1, s->KP, s->k, s->n, s->st);
+    if (!rc) rc = f.zero();
+    if (!rc) rc = f.load(vW, vH);
     if (rc) return rc;
-    return factors_end(s);
+    return e.synced(factors_end(s));
 }
 
 // The same start as smk_solver_set_factors(W0, H0) with W0 = smk_uniform_fill_host(m x k, seed_w), H0 = smk_uniform_fill_host
@@ -828,7 +823,7 @@ static int timed_spmm(smk_solver* s, int which, const i64* colptr, const unsigne
         if (span_open(s, &sp)) return SMK_DEVICE_ERROR;
         (void)hipEventRecord(sp.e0, s->st);
     }
-    int rc;
+    int rc = 0;
     const BlockedCsc& blk = (which == 0) ? s->a->bA : s->a->bAt;
     const SegPlan& seg = (which == 0) ? s->a->segA : s->a->segAt;
     InvRide ride;                                                   // start_inverse: this side's Gram inverse rides in the launch
@@ -842,23 +837,25 @@ static int timed_spmm(smk_solver* s, int which, const i64* colptr, const unsigne
         const i64 FN = which == 0 ? s->m : s->n;
         double* G = which == 0 ? s->Gw : s->Gh;
         if (by_seg) { gram.X = F; gram.N = FN; gram.max_blocks = GRAM_BLOCKS; gram.Gp = s->gram_scratch; gram.G = G; }
-        else { const int grc = launch_gram(F, s->k, FN, G, s->gram_scratch, GRAM_BLOCKS, s->st); if (grc) return grc; }
+        else rc = launch_gram(F, s->k, FN, G, s->gram_scratch, GRAM_BLOCKS, s->st);
     }
-    if (blocked2_route(s, which, ldx)) rc = launch_spmm_blocked2(blk, X, P, which == 0 ? s->pl1.ncols_pad : s->pl2.ncols_pad, s->st);
-    else if (by_seg) {
-        // the partial sums of long columns live in the SOLVER (two solvers on one sparse matrix run on their own streams)
-        if (seg.npieces > 0 && !s->seg_pieces[which] && s->own.dev(&s->seg_pieces[which], (size_t)seg.npieces * 128)) {
-            set_error("no memory for the long-column partial sums");
-            return SMK_DEVICE_ERROR;
+    if (!rc) {        // a failure, the Gram launch's or one below, launches nothing more and reaches the span's clean-up, not a return
+        if (blocked2_route(s, which, ldx)) rc = launch_spmm_blocked2(blk, X, P, which == 0 ? s->pl1.ncols_pad : s->pl2.ncols_pad, s->st);
+        else if (by_seg) {
+            // the partial sums of long columns live in the SOLVER (two solvers on one sparse matrix run on their own streams)
+            if (seg.npieces > 0 && !s->seg_pieces[which] && s->own.dev(&s->seg_pieces[which], (size_t)seg.npieces * 128)) {
+                set_error("no memory for the long-column partial sums");
+                rc = SMK_DEVICE_ERROR;
+            }
+            if (!rc) rc = launch_spmm_seg(seg, colptr, val, X, s->k, P, s->kpp, s->st, s->seg_pieces[which], &ride, &gram);
+            if (rc > 0 && (rc & 2)) rc &= ~2;                           // ... and the Gram matrix
+            else if (rc >= 0 && gram.X) {                               // nothing was launched (a matrix without stored entries): the matrix by itself
+                const int grc = launch_gram(gram.X, s->k, gram.N, gram.G, s->gram_scratch, GRAM_BLOCKS, s->st);
+                if (grc) rc = grc;
+            }
         }
-        rc = launch_spmm_seg(seg, colptr, val, X, s->k, P, s->kpp, s->st, s->seg_pieces[which], &ride, &gram);
-        if (rc > 0 && (rc & 2)) rc &= ~2;                           // ... and the Gram matrix
-        else if (rc >= 0 && gram.X) {                               // nothing was launched (a matrix without stored entries): the matrix by itself
-            const int grc = launch_gram(gram.X, s->k, gram.N, gram.G, s->gram_scratch, GRAM_BLOCKS, s->st);
-            if (grc) return grc;
-        }
+        else rc = launch_spmm_gather(colptr, rowidx, val, ncols, s->a->nnz, X, ldx, s->k, P, s->kpp, s->st, &ride);
     }
-    else rc = launch_spmm_gather(colptr, rowidx, val, ncols, s->a->nnz, X, ldx, s->k, P, s->kpp, s->st, &ride);
     if (rc == 1) { s->inv_done[which] = true; rc = 0; }             // the launch carried the inverse
     if (timed) {
         if (rc) { s->span_pool.push_back(sp); return rc; }
@@ -1908,7 +1905,7 @@ int smk_solver_project_h(smk_solver* s)
 int smk_nnls_blockpivot(int k, int64_t ncols, const double* LHS, int64_t ldL, const double* RHS, int64_t ldR, double* X,
                         int64_t ldX, double* Y, int64_t ldY)
 {
-    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = require_init()) return rc;
     if (k <= 0 || ncols <= 0 || !LHS || !RHS || !X || ldL < k || ldR < k || ldX < k || (Y && ldY < k)) return SMK_BAD_PARAM;
     if (k > MAX_K_BPP) { set_error("device path supports k <= 2048"); return SMK_UNSUPPORTED; }
     const int KP = kp_of(k);
@@ -1964,18 +1961,18 @@ static int factors_ready(smk_solver* s, int normalize)
 int smk_solver_get_factors_device(smk_solver* s, int normalize, void* W, int dtypeW, int64_t rsW, int64_t csW, void* H, int dtypeH,
                                   int64_t rsH, int64_t csH, void* stream)
 {
+    const char* who = "smk_solver_get_factors_device";
     if (!s) return SMK_BAD_PARAM;
-    if (!factor_dtype(dtypeW) || !factor_dtype(dtypeH)) { set_error("smk_solver_get_factors_device: factors are fp64 or fp32"); return SMK_BAD_PARAM; }
-    int rc = check_device_view(W, dtypeW, s->m, s->k, rsW, csW, true, "smk_solver_get_factors_device(W)");
-    if (!rc) rc = check_device_view(H, dtypeH, s->k, s->n, rsH, csH, true, "smk_solver_get_factors_device(H)");
+    const DeviceView vW{W, dtypeW, rsW, csW}, vH{H, dtypeH, rsH, csH};
+    int rc = check_factor_dtypes(who, "factors", dtypeW, dtypeH);
+    if (!rc) rc = resident_pair(s).check(who, vW, vH, true, true);
     if (rc) return rc;
-    Owned own;
-    rc = join_caller_stream(own, s->st, stream);
+    Entry e(s->st);
+    rc = e.join(stream);
     if (!rc) rc = factors_ready(s, normalize);
-    if (!rc) rc = launch_strided_convert(s->Wt, DT_F64, s->KP, 1, W, dtypeW, rsW, csW, s->m, s->k, s->st);
-    if (!rc) rc = launch_strided_convert(s->H, DT_F64, 1, s->KP, H, dtypeH, rsH, csH, s->k, s->n, s->st);
+    if (!rc) rc = resident_pair(s).store(&vW, &vH);
     if (rc) return rc;
-    return sync_and_check(s, nullptr);
+    return e.synced(sync_and_check(s, nullptr));
 }
 
 // Labels / memberships of the local columns and the top terms of the topics, straight from the resident factors (H at H + c KP,

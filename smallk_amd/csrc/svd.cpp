@@ -2,10 +2,10 @@
 // smk_matrix_svd_device, smk_matrix_nndsvd_device, smk_solver_set_factors_nndsvd).  A randomised range finder with
 // power iterations: every pass over A is the accurate-form streaming product (dense) or the fp64 gather product (sparse) the
 // solver already has, every orthonormalisation is launch_gram + a host eigendecomposition of the l x l Gram matrix (svd_host.h)
-// + the tall-skinny apply of svd.hip.  The entries are synchronous; every workspace belongs to an smk::Owned local of the entry
-// and is released on every path; no field of the matrix handle and no buffer of a solver is written here (the solver entry
-// hands its finished start to smk_solver_set_factors_device).
-#include "state.h"
+// + the tall-skinny apply of svd.hip.  The entries are synchronous; every workspace belongs to the smk::Entry local of the entry
+// (entry.h: synchronised before it releases them, on every path); no field of the matrix handle and no buffer of a solver is
+// written here (the solver entry hands its finished start to smk_solver_set_factors_device).
+#include "entry.h"
 #include "factor_product.h"
 #include "svd_host.h"
 
@@ -30,6 +30,7 @@ struct SvdRun {
     std::vector<double> hG, lambda, E, M;
     int host_trips = 0;
     double host_us = 0.0;                         // the host's own work in those trips (eigendecomposition + M), without the copies
+    FactorPair pair(bool v_rows) const { return {a->m, a->n, k, KP, st, Fm, Fn, v_rows}; }
 };
 
 // the last run of the calling thread, for tools/svd_rate.py (smk_svd_last_profile)
@@ -49,11 +50,7 @@ static int svd_alloc(SvdRun& r)
     const int fused = svd_apply_gram_blocks(r.KP, a->m > a->n ? a->m : a->n, ctx().cus);
     if (!rc && fused > 0) rc = own.dev(&r.Gp, (size_t)fused * kk);
     if (rc) { set_error("svd: no memory for the factor workspace"); return SMK_DEVICE_ERROR; }
-    r.fp.a = a;
-    r.fp.l = r.l;
-    r.fp.KP = r.KP;
-    r.fp.st = r.st;
-    return factor_product_alloc(r.fp, own, "svd");
+    return factor_product_alloc(r.fp, a, r.l, r.KP, r.st, own, "svd");
 }
 
 // over_rows: out (KP x n) = (A' X')' for X = KP x m, the contraction over the rows of A; else out (KP x m) = (A X')' for X = KP x n
@@ -114,7 +111,7 @@ static int svd_orth(SvdRun& r, double* F, i64 N)
 static int svd_args(const char* who, const smk_matrix* a, const smk_svd_options* o, int k, SvdRun& r)
 {
     const std::string w(who);
-    if (!ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = require_init()) return rc;
     if (!a) { set_error(w + ": null matrix"); return SMK_BAD_PARAM; }
     if (k < 1) { set_error(w + ": k < 1"); return SMK_BAD_PARAM; }
     if (k > a->m || k > a->n_global) { set_error(w + ": k exceeds min(m, n)"); return SMK_BAD_PARAM; }
@@ -126,7 +123,7 @@ static int svd_args(const char* who, const smk_matrix* a, const smk_svd_options*
         set_error(w + ": a single-copy dense matrix has no stored transpose, and the accurate-form product has no transposed-source kernel");
         return SMK_UNSUPPORTED;
     }
-    if (o && o->omega && o->omega_dtype != SMK_DT_F64 && o->omega_dtype != SMK_DT_F32) { set_error(w + ": omega is fp64 or fp32"); return SMK_BAD_PARAM; }
+    if (o && o->omega && !is_factor_dtype(o->omega_dtype)) { set_error(w + ": omega is fp64 or fp32"); return SMK_BAD_PARAM; }
     r.a = a;
     r.k = k;
     i64 l = (i64)k + p;
@@ -152,7 +149,7 @@ static int svd_core(SvdRun& r, const smk_svd_options* o, double* S)
     // 1. the test matrix, as the factor Omega' (KP x n), and Y = A Omega
     if (o && o->omega) {
         SMK_HIP(hipMemsetAsync(r.Fn, 0, (size_t)r.KP * a->n * sizeof(double), r.st));
-        rc = launch_strided_convert(o->omega, o->omega_dtype, o->omega_rs, o->omega_cs, r.Fn, DT_F64, r.KP, 1, a->n, r.l, r.st);
+        rc = convert_view(DeviceView::in(o->omega, o->omega_dtype, o->omega_rs, o->omega_cs), DeviceView::rows(r.Fn, r.KP), a->n, r.l, r.st);
     } else {
         rc = launch_svd_fill_centred(r.Fn, r.KP, r.l, a->n, o ? o->seed : 0, r.st);
     }
@@ -251,8 +248,6 @@ static int nndsvd_from_svd(SvdRun& r, const double* S, int variant)
     return 0;
 }
 
-static bool out_dtype(int dt) { return dt == SMK_DT_F64 || dt == SMK_DT_F32; }
-
 }  // namespace smk
 
 extern "C" {
@@ -260,51 +255,47 @@ extern "C" {
 int smk_matrix_svd_device(const smk_matrix* a, const smk_svd_options* opts, void* U, int dtypeU, int64_t rsU, int64_t csU, double* S_host,
                           void* V, int dtypeV, int64_t rsV, int64_t csV, void* stream)
 {
+    const char* who = "smk_matrix_svd_device";
     SvdRun r;
     if (!opts) { set_error("smk_matrix_svd_device: null options"); return SMK_BAD_PARAM; }
-    int rc = svd_args("smk_matrix_svd_device", a, opts, opts->k, r);
+    int rc = svd_args(who, a, opts, opts->k, r);
     if (rc) return rc;
     if (!S_host) { set_error("smk_matrix_svd_device: null output"); return SMK_BAD_PARAM; }
-    if (!out_dtype(dtypeU) || !out_dtype(dtypeV)) { set_error("smk_matrix_svd_device: U and V are fp64 or fp32"); return SMK_BAD_PARAM; }
-    rc = check_device_view(U, dtypeU, a->m, r.k, rsU, csU, true, "smk_matrix_svd_device(U)");
-    if (!rc) rc = check_device_view(V, dtypeV, a->n, r.k, rsV, csV, true, "smk_matrix_svd_device(V)");
+    const DeviceView vU{U, dtypeU, rsU, csU}, vV{V, dtypeV, rsV, csV};
+    rc = check_factor_dtypes(who, "U and V", dtypeU, dtypeV);
+    if (!rc) rc = r.pair(true).check(who, vU, vV, true, true, "U", "V");
     if (rc) return rc;
-    Owned own;
-    r.own = &own;
-    r.st = a->st ? a->st : ctx().stream;
-    rc = join_caller_stream(own, r.st, stream);
+    Entry e(matrix_stream(a));
+    r.own = &e.own;
+    r.st = e.st;
+    rc = e.join(stream);
     if (!rc) rc = svd_core(r, opts, S_host);
-    if (!rc) rc = launch_strided_convert(r.Fm, DT_F64, r.KP, 1, U, dtypeU, rsU, csU, a->m, r.k, r.st);
-    if (!rc) rc = launch_strided_convert(r.Fn, DT_F64, r.KP, 1, V, dtypeV, rsV, csV, a->n, r.k, r.st);
-    if (rc) return rc;
-    SMK_HIP(hipStreamSynchronize(r.st));
-    return SMK_OK;
+    if (!rc) rc = r.pair(true).store(&vU, &vV);
+    return rc ? rc : e.sync();
 }
 
 int smk_matrix_nndsvd_device(const smk_matrix* a, const smk_svd_options* opts, int variant, void* W, int dtypeW, int64_t rsW, int64_t csW,
                              void* H, int dtypeH, int64_t rsH, int64_t csH, void* stream)
 {
+    const char* who = "smk_matrix_nndsvd_device";
     SvdRun r;
     if (!opts) { set_error("smk_matrix_nndsvd_device: null options"); return SMK_BAD_PARAM; }
-    int rc = svd_args("smk_matrix_nndsvd_device", a, opts, opts->k, r);
+    int rc = svd_args(who, a, opts, opts->k, r);
     if (rc) return rc;
     if (variant != SMK_NNDSVD && variant != SMK_NNDSVDA) { set_error("smk_matrix_nndsvd_device: unknown variant"); return SMK_BAD_PARAM; }
-    if (!out_dtype(dtypeW) || !out_dtype(dtypeH)) { set_error("smk_matrix_nndsvd_device: W and H are fp64 or fp32"); return SMK_BAD_PARAM; }
-    rc = check_device_view(W, dtypeW, a->m, r.k, rsW, csW, true, "smk_matrix_nndsvd_device(W)");
-    if (!rc) rc = check_device_view(H, dtypeH, r.k, a->n, rsH, csH, true, "smk_matrix_nndsvd_device(H)");
+    const DeviceView vW{W, dtypeW, rsW, csW}, vH{H, dtypeH, rsH, csH};
+    rc = check_factor_dtypes(who, "W and H", dtypeW, dtypeH);
+    if (!rc) rc = r.pair(false).check(who, vW, vH, true, true);
     if (rc) return rc;
-    Owned own;
-    r.own = &own;
-    r.st = a->st ? a->st : ctx().stream;
+    Entry e(matrix_stream(a));
+    r.own = &e.own;
+    r.st = e.st;
     std::vector<double> S((size_t)r.k, 0.0);
-    rc = join_caller_stream(own, r.st, stream);
+    rc = e.join(stream);
     if (!rc) rc = svd_core(r, opts, S.data());
     if (!rc) rc = nndsvd_from_svd(r, S.data(), variant);
-    if (!rc) rc = launch_strided_convert(r.Fm, DT_F64, r.KP, 1, W, dtypeW, rsW, csW, a->m, r.k, r.st);
-    if (!rc) rc = launch_strided_convert(r.Fn, DT_F64, 1, r.KP, H, dtypeH, rsH, csH, r.k, a->n, r.st);
-    if (rc) return rc;
-    SMK_HIP(hipStreamSynchronize(r.st));
-    return SMK_OK;
+    if (!rc) rc = r.pair(false).store(&vW, &vH);
+    return rc ? rc : e.sync();
 }
 
 int smk_svd_last_profile(int* host_trips, double* host_ms)
@@ -322,15 +313,17 @@ int smk_solver_set_factors_nndsvd(smk_solver* s, const smk_svd_options* opts, in
     SvdRun r;
     int rc = svd_args("smk_solver_set_factors_nndsvd", s->a, opts, s->k, r);
     if (rc) return rc;
-    Owned own;
-    r.own = &own;
-    r.st = s->st;
+    Entry e(s->st);
+    r.own = &e.own;
+    r.st = e.st;
     std::vector<double> S((size_t)r.k, 0.0);
     rc = svd_core(r, opts, S.data());
     if (!rc) rc = nndsvd_from_svd(r, S.data(), variant);
     if (rc) return rc;
     // the finished start lies in this call's workspace as W' (KP x m) and H (KP x n): hand it over as any caller would
-    return smk_solver_set_factors_device(s, r.Fm, SMK_DT_F64, r.KP, 1, r.Fn, SMK_DT_F64, 1, r.KP, (void*)s->st);
+    const FactorPair f = r.pair(false);
+    const DeviceView vW = f.first(), vH = f.second();
+    return e.synced(smk_solver_set_factors_device(s, vW.p, vW.dtype, vW.rs, vW.cs, vH.p, vH.dtype, vH.rs, vH.cs, (void*)s->st));
 }
 
 }  // extern "C"

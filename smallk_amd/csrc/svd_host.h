@@ -16,9 +16,17 @@ namespace svdh {
 constexpr double RANK_TOL = 0x1.0p-40;
 constexpr int JACOBI_MAX_SWEEPS = 60;
 
+// jacobi_eigh's time follows where the linker happens to start it within a 64-byte line of code (12 decompositions at l = 24: 0.70 ms
+// from 32 or 48 bytes into a line, 0.79 ms from its start; profiles/view_entries_ab.txt): pinned at 32, by 32 bytes of no-ops.
+#if defined(__clang__) && defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+#define SVDH_PLACED __attribute__((aligned(64), patchable_function_entry(32)))
+#else
+#define SVDH_PLACED
+#endif
+
 // G: l x l symmetric with leading dimension ldg (only read).  lambda: l eigenvalues, largest first (equal ones by the
 // order Jacobi left them in); E: l x l row-major, column j the unit eigenvector of lambda[j].  Returns the sweeps taken.
-inline int jacobi_eigh(const double* G, int ldg, int l, std::vector<double>& lambda, std::vector<double>& E)
+SVDH_PLACED inline int jacobi_eigh(const double* G, int ldg, int l, std::vector<double>& lambda, std::vector<double>& E)
 {
     std::vector<double> a((size_t)l * l), v((size_t)l * l, 0.0);
     double gmax = 0.0;

@@ -11,7 +11,7 @@
 
 #include "preprocess.h"
 #include "preprocess_result.h"
-#include "state.h"
+#include "entry.h"
 #include "vocabulary.h"
 
 struct smk_vocabulary {
@@ -151,7 +151,7 @@ int apply_args(const char* who, const smk_vocabulary* v, const smk_apply_options
     const std::string w(who);
     if (!out) { set_error(w + ": null output"); return SMK_BAD_PARAM; }
     *out = nullptr;
-    if (!smk::ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = smk::require_init()) return rc;
     if (!v) { set_error(w + ": null vocabulary"); return SMK_BAD_PARAM; }
     if (!opts) { set_error(w + ": null options"); return SMK_BAD_PARAM; }
     if (width == 0) { set_error(w + ": width 0"); return SMK_BAD_PARAM; }
@@ -197,7 +197,7 @@ int smk_vocabulary_create(unsigned height_in, unsigned height, const unsigned* t
 {
     if (!out) { set_error("smk_vocabulary_create: null output"); return SMK_BAD_PARAM; }
     *out = nullptr;
-    if (!smk::ctx().init) { set_error("smk_initialize() has not been called"); return SMK_NOTINITIALIZED; }
+    if (int rc = smk::require_init()) return rc;
     if (!term_indices || !idf) { set_error("smk_vocabulary_create: null array"); return SMK_BAD_PARAM; }
     if (height < 1) { set_error("smk_vocabulary_create: height < 1"); return SMK_BAD_PARAM; }
     for (unsigned i = 0; i < height; ++i) {
@@ -289,7 +289,7 @@ int smk_vocabulary_apply_device(const smk_vocabulary* v, const smk_apply_options
         set_error("smk_vocabulary_apply_device: unknown index type");
         return SMK_BAD_PARAM;
     }
-    if (dtype != SMK_DT_F64 && dtype != SMK_DT_F32) { set_error("smk_vocabulary_apply_device: values are fp64 or fp32"); return SMK_BAD_PARAM; }
+    if (!smk::is_factor_dtype(dtype)) { set_error("smk_vocabulary_apply_device: values are fp64 or fp32"); return SMK_BAD_PARAM; }
     if (nnz > 0x7FFFFFFFu) { set_error("smk_vocabulary_apply_device: more than 2^31 - 1 entries"); return SMK_SIZE_TOO_LARGE; }
     // the three arrays as views of 8- / 4-byte elements: same pointer and extent checks as a dense view
     const auto idx_dt = [](int t) { return t == SMK_IDX_I64 ? (int)smk::DT_F64 : (int)smk::DT_F32; };

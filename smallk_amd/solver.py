@@ -799,6 +799,40 @@ def transform(A, W, *, H0=None):
         solver.close()
 
 
+def _penalised_fit(what, kind, entry, stats_type, last_two, result_type, A, W0, H0, *, alpha_W, alpha_H, l1_ratio, tol, max_iter, update_W, inplace):
+    """What ``nmf_cd`` and ``nmf_kl`` share: the checks made before the library is called, the start as tensors on the GPU, the options,
+    the C entry ``entry`` with its statistics struct and the result as ``result_type(W, H, n_iter, converged, *last_two(stats))``."""
+    if not isinstance(A, DenseMatrix):
+        raise ValueError(f"{what}: A must be a resident {kind}, got {type(A).__name__}")
+    on_device, k = _residual_factors(W0, H0, A.height, A.ncols, what)
+    if inplace and not on_device:
+        raise ValueError(f"{what}: inplace needs torch tensors")
+    import torch
+    if alpha_H == "same":
+        alpha_H = alpha_W
+    o = L.PenaltyOptions(float(alpha_W), float(alpha_H), float(l1_ratio), float(tol), int(max_iter), int(bool(update_W)))
+    if on_device:
+        W, H = (W0, H0) if inplace else (W0.clone(), H0.clone())
+    else:
+        dev = torch.device("cuda", L.lib().smk_current_device())
+        W = torch.from_numpy(np.ascontiguousarray(W0, dtype=np.float64)).to(dev)
+        H = torch.from_numpy(np.ascontiguousarray(H0, dtype=np.float64)).to(dev)
+    wp, wt, (wrs, wcs) = _tensor_view(W, f"{what}(W0)", kinds="factor")
+    hp, ht, (hrs, hcs) = _tensor_view(H, f"{what}(H0)", kinds="factor")
+    st = stats_type()
+    L.check(getattr(L.lib(), entry)(A._h, k, C.byref(o), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), C.byref(st)), entry)
+    if not on_device:
+        W, H = W.cpu().numpy(), H.cpu().numpy()
+    return result_type(W, H, st.iterations, bool(st.converged), *last_two(st))
+
+
+def _last_profile(entry):
+    """the two counters ``entry`` (smk_cd_last_profile / smk_kl_last_profile) reports for this thread's last run"""
+    p, s = C.c_int(0), C.c_int(0)
+    L.check(getattr(L.lib(), entry)(C.byref(p), C.byref(s)), entry)
+    return p.value, s.value
+
+
 @dataclass
 class CdResult:
     """What ``nmf_cd`` returns: the factors (numpy arrays, or torch tensors on the GPU when the start was tensors), the iterations
@@ -822,36 +856,13 @@ def nmf_cd(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, ma
     which is ``sklearn.decomposition.NMF`` on X = A' with sklearn's ``alpha_W`` = this ``alpha_H`` and its ``alpha_H`` = this
     ``alpha_W``, W_sklearn = H' and ``components_`` = W'.  ``alpha_H="same"`` takes ``alpha_W``.  ``update_W=False``: W stays, only H is
     fitted (fold-in).  The start is not modified unless ``inplace`` (tensors only): then W0 / H0 receive the result."""
-    if not isinstance(A, DenseMatrix):
-        raise ValueError(f"nmf_cd: A must be a resident DenseMatrix / SparseMatrix, got {type(A).__name__}")
-    on_device, k = _residual_factors(W0, H0, A.height, A.ncols, "nmf_cd")
-    if inplace and not on_device:
-        raise ValueError("nmf_cd: inplace needs torch tensors")
-    import torch
-    if alpha_H == "same":
-        alpha_H = alpha_W
-    o = L.CdOptions(float(alpha_W), float(alpha_H), float(l1_ratio), float(tol), int(max_iter), int(bool(update_W)))
-    if on_device:
-        W, H = (W0, H0) if inplace else (W0.clone(), H0.clone())
-    else:
-        dev = torch.device("cuda", L.lib().smk_current_device())
-        W = torch.from_numpy(np.ascontiguousarray(W0, dtype=np.float64)).to(dev)
-        H = torch.from_numpy(np.ascontiguousarray(H0, dtype=np.float64)).to(dev)
-    wp, wt, (wrs, wcs) = _tensor_view(W, "nmf_cd(W0)", kinds="factor")
-    hp, ht, (hrs, hcs) = _tensor_view(H, "nmf_cd(H0)", kinds="factor")
-    st = L.CdStats()
-    L.check(L.lib().smk_nmf_cd_device(A._h, k, C.byref(o), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), C.byref(st)),
-            "smk_nmf_cd_device")
-    if not on_device:
-        W, H = W.cpu().numpy(), H.cpu().numpy()
-    return CdResult(W, H, st.iterations, bool(st.converged), st.violation_init, st.violation)
+    return _penalised_fit("nmf_cd", "DenseMatrix / SparseMatrix", "smk_nmf_cd_device", L.CdStats, lambda st: (st.violation_init, st.violation), CdResult,
+                          A, W0, H0, alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio, tol=tol, max_iter=max_iter, update_W=update_W, inplace=inplace)
 
 
 def cd_last_profile():
     """(passes over A, sweeps launched) of this thread's last ``nmf_cd``"""
-    p, s = C.c_int(0), C.c_int(0)
-    L.check(L.lib().smk_cd_last_profile(C.byref(p), C.byref(s)), "smk_cd_last_profile")
-    return p.value, s.value
+    return _last_profile("smk_cd_last_profile")
 
 
 @dataclass
@@ -879,36 +890,13 @@ def nmf_kl(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, ma
     ``alpha_W``, W_sklearn = H' and ``components_`` = W'; the stopping rule is sklearn's, looked at every tenth iteration.
     ``alpha_H="same"`` takes ``alpha_W``.  ``update_W=False``: W stays, only H is fitted (fold-in).  The start is not modified unless
     ``inplace`` (tensors only): then W0 / H0 receive the result.  A must store no entry twice and no negative value."""
-    if not isinstance(A, DenseMatrix):
-        raise ValueError(f"nmf_kl: A must be a resident SparseMatrix, got {type(A).__name__}")
-    on_device, k = _residual_factors(W0, H0, A.height, A.ncols, "nmf_kl")
-    if inplace and not on_device:
-        raise ValueError("nmf_kl: inplace needs torch tensors")
-    import torch
-    if alpha_H == "same":
-        alpha_H = alpha_W
-    o = L.KlOptions(float(alpha_W), float(alpha_H), float(l1_ratio), float(tol), int(max_iter), int(bool(update_W)))
-    if on_device:
-        W, H = (W0, H0) if inplace else (W0.clone(), H0.clone())
-    else:
-        dev = torch.device("cuda", L.lib().smk_current_device())
-        W = torch.from_numpy(np.ascontiguousarray(W0, dtype=np.float64)).to(dev)
-        H = torch.from_numpy(np.ascontiguousarray(H0, dtype=np.float64)).to(dev)
-    wp, wt, (wrs, wcs) = _tensor_view(W, "nmf_kl(W0)", kinds="factor")
-    hp, ht, (hrs, hcs) = _tensor_view(H, "nmf_kl(H0)", kinds="factor")
-    st = L.KlStats()
-    L.check(L.lib().smk_nmf_kl_device(A._h, k, C.byref(o), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), C.byref(st)),
-            "smk_nmf_kl_device")
-    if not on_device:
-        W, H = W.cpu().numpy(), H.cpu().numpy()
-    return KlResult(W, H, st.iterations, bool(st.converged), st.error_init, st.error)
+    return _penalised_fit("nmf_kl", "SparseMatrix", "smk_nmf_kl_device", L.KlStats, lambda st: (st.error_init, st.error), KlResult,
+                          A, W0, H0, alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio, tol=tol, max_iter=max_iter, update_W=update_W, inplace=inplace)
 
 
 def kl_last_profile():
     """(sweeps over the stored entries that updated a factor, sweeps that formed the divergence) of this thread's last ``nmf_kl``"""
-    p, s = C.c_int(0), C.c_int(0)
-    L.check(L.lib().smk_kl_last_profile(C.byref(p), C.byref(s)), "smk_kl_last_profile")
-    return p.value, s.value
+    return _last_profile("smk_kl_last_profile")
 
 
 def cd_sweep(G, R, X, l1=0.0, l2=0.0):
