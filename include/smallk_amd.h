@@ -502,6 +502,42 @@ int smk_tree_flat_factors(const smk_tree* t, double* W, int64_t ldW, double* H, 
 /* the priority score of a split: compute_priority(), clust_hier_util.hpp:105-173 */
 double smk_clust_priority(const double* w_parent, const double* w_child /* n x 2, ld n */, int64_t n);
 
+/* ---- new documents down a fitted tree, on the device (tree_route.cpp) -----------------------------------------
+ * The rule is the training code's (tree_partition): at a split with child topic vectors w_l, w_r document a goes left iff h0 > h1,
+ * (h0, h1) = argmin_{h >= 0} ||a - [w_l w_r] h||, the closed-form rank-2 solve.  A router holds, per pair of siblings, the two
+ * topic vectors interleaved in device memory: pairs * m * 16 bytes (an 8-leaf tree has 7 pairs: 112 MB over 10^6 terms).
+ * A structure is the forest HierNMF2 produces: roots are nodes 0 and 1; a valid node has both children SMK_TREE_NONE (a leaf) or two
+ * valid children below node_count; no node is reached twice from the roots (no second parent, no cycle); invalid or unreachable nodes
+ * are ignored.  valid may be NULL (every node valid).  Anything else: SMK_BAD_PARAM, smk_last_error names the node.
+ * smk_tree_router_check is host code and needs no initialised device: pairs = splits + the root pair, max_depth = decisions on the
+ * longest descent. */
+typedef struct smk_tree_router smk_tree_router;
+int smk_tree_router_check(int node_count, const unsigned* left, const unsigned* right, const int* valid, int* pairs, int* max_depth);
+/* topics_host: m x node_count fp64, column-major with ld doubles per column, on the host (column q = the topic vector of node q).
+ * SMK_BAD_PARAM: a null pointer, m < 1, ld < m, a bad structure.  SMK_FAILURE: the 2 x 2 Gram matrix of a reachable pair is singular
+ * by the rank-2 solve's own test (a zero topic vector, for example); the message names the pair.  SMK_DEVICE_ERROR: no memory. */
+int smk_tree_router_create(int64_t m, int node_count, const unsigned* left, const unsigned* right, const int* valid,
+                           const double* topics_host, int64_t ld, smk_tree_router** router);
+/* the same router from a fitted tree, read through smk_tree_get_node / smk_tree_node_topic */
+int smk_tree_router_from_tree(const smk_tree* t, smk_tree_router** router);
+void smk_tree_router_destroy(smk_tree_router* r);
+/* every output may be NULL; table_bytes = pairs * m * 16 */
+int smk_tree_router_sizes(const smk_tree_router* r, int64_t* m, int* node_count, int* pairs, int* max_depth, int64_t* table_bytes);
+/* the arrays create took, bit for bit (node_count entries each, topics with ld doubles per column): what a saved router keeps */
+int smk_tree_router_download(const smk_tree_router* r, unsigned* left, unsigned* right, int* valid, double* topics_host, int64_t ld);
+/* The columns of A_new (a resident SPARSE matrix with m rows) down the tree, one launch, synchronous.  Outputs in device memory, n =
+ * columns of A_new entries each: leaf (int32: the node the document ends at, in the tree's own numbering -- smk_tree_assignments'
+ * -- and never SMK_TREE_NONE: training outliers are a property of the search, not of this rule), depth (int32, may be NULL:
+ * decisions taken), h (fp64, 2 per document, may be NULL: (h0, h1) of the last decision).  A document without entries goes right at
+ * every level.  The same bits on every run.  stream: the caller's (the library's stream waits for it).  SMK_UNSUPPORTED: a dense
+ * A_new, a column shard.  SMK_BAD_PARAM: a null pointer, A_new's height is not m, an output that is not device memory of n entries.
+ * The outputs are written on success only. */
+int smk_tree_route_device(const smk_tree_router* r, const smk_matrix* A_new, void* stream, void* leaf, void* depth, void* h);
+/* diagnostics of the calling thread's last successful smk_tree_route_device call: kernel launches, stored entries they walked */
+int smk_tree_route_last_profile(int* launches, int64_t* entries);
+/* measurement (tools/route_rate.py): the average time in ms of `reps` routing launches into a workspace */
+int smk_tree_route_time(const smk_tree_router* r, const smk_matrix* A_new, int reps, double* ms);
+
 /* ---- flat clustering ------------------------------------------------------------------
  * FlatClust / FlatClustSparse (flatclust/include/flat_clust.hpp, flatclust/src/flat_clust.cpp:118-264):
  * NmfSolve<> restricted to HALS / RANK2 / BPP; same argument meaning as smk_nmf_dense / smk_nmf_sparse. */

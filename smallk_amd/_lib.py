@@ -269,6 +269,18 @@ SYMBOLS = {
     "smk_tree_write": (C.c_int, [_vp, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), _i64]),
     "smk_clust_priority": (C.c_double, [_dp, _dp, _i64]),
     "smk_tree_flat_factors": (C.c_int, [_vp, _dp, _i64, _dp, _i64]),
+    # new documents down a fitted tree (tree_route.cpp)
+    "smk_tree_router_check": (C.c_int, [C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int)]),
+    "smk_tree_router_create": (C.c_int, [_i64, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int), _dp, _i64,
+                                         C.POINTER(_vp)]),
+    "smk_tree_router_from_tree": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "smk_tree_router_destroy": (None, [_vp]),
+    "smk_tree_router_sizes": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64)]),
+    "smk_tree_router_download": (C.c_int, [_vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int), _dp, _i64]),
+    "smk_tree_route_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "smk_tree_route_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(_i64)]),
+    "smk_tree_route_time": (C.c_int, [_vp, _vp, C.c_int, _dp]),
     # flat clustering (flatclust.cpp; reference flatclust/src/flat_clust.cpp, common/include/assignments.hpp)
     "smk_flatclust_dense": (C.c_int, [C.POINTER(Options), _dp, _i64, _dp, _i64, _dp, _i64, C.POINTER(Stats), C.c_int]),
     "smk_flatclust_sparse": (C.c_int, [C.POINTER(Options), C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint),
