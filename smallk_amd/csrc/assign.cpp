@@ -1,7 +1,7 @@
 // smallk_amd/csrc/assign.cpp -- labels, memberships and top terms of factors that are in device memory (include/smallk_amd.h:
 // smk_labels_device, smk_top_terms_device).  The kernels (assign.hip) read a factor in its k-contiguous layout; a
 // view in any other layout is converted into a workspace first.  Every workspace belongs to the smk::Entry local of the entry
-// (entry.h: synchronised before it releases them).  The solver's entries (solver.cpp: smk_solver_labels, smk_solver_top_terms)
+// (entry.h: synchronised before it releases them).  The solver's entries (factors.cpp: smk_solver_labels, smk_solver_top_terms)
 // come through the same two functions with the resident H and Wt, which are k-contiguous as they stand: no copy.
 #include "entry.h"
 

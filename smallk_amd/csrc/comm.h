@@ -1,4 +1,4 @@
-// smallk_amd/csrc/comm.h -- communicator object shared by comm.cpp and solver.cpp
+// smallk_amd/csrc/comm.h -- communicator object shared by comm.cpp, attach.cpp (which gives a solver one) and solver.cpp (which runs the exchange)
 #pragma once
 #include "common.h"
 

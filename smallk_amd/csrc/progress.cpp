@@ -24,7 +24,7 @@ bool check_rides_in_nnls(const smk_solver* s)
 {
     if (!sw::progress_defer() || !sw::progress_fused() || sw::bpp_gradw() || sw::guard_every() > 0) return false;
     if (s->o.algorithm != SMK_ALG_BPP || s->KP > 16 || s->o.prog_est_algorithm != SMK_PROG_PG_RATIO) return false;
-    if (is_dist(s) || s->comm || s->w_sharded) return false;
+    if (is_dist(s) || s->ex.comm || s->ex.w_sharded) return false;
     const i64 gpb = 256 / s->KP;
     return (s->n + gpb - 1) / gpb <= (i64)s->pg_half;          // one partial per workgroup of the H-side launch
 }
@@ -41,14 +41,14 @@ static int missing_behind_comm(const char* what, int b)
 int ensure_snapshot(smk_solver* s, int b, bool attaching)
 {
     if (s->pc.snap[b]) return 0;
-    if (s->comm && !attaching) return missing_behind_comm("the snapshot", b);
+    if (s->ex.comm && !attaching) return missing_behind_comm("the snapshot", b);
     return s->own.dev(&s->pc.snap[b], snapshot_elems(s->k, s->m, s->n));
 }
 // the pinned result slots and their events
 static int ensure_progress_slots(smk_solver* s, int b, bool attaching = false)
 {
     if (s->pc.pin) return 0;
-    if (s->comm && !attaching) return missing_behind_comm("the pinned result", b);
+    if (s->ex.comm && !attaching) return missing_behind_comm("the pinned result", b);
     int rc = s->own.pinned((void**)&s->pc.pin, ProgressCheck::PROG_SLOTS * sizeof(ProgressCheck::ProgSlot));
     for (int i = 0; i < ProgressCheck::PROG_SLOTS && !rc; ++i) rc = s->own.event(&s->pc.pev[i], hipEventDisableTiming);
     return rc;
@@ -99,8 +99,8 @@ static int enqueue_progress_kernels(smk_solver* s)
         if (rc) return rc;
     } else {
         // gradW = W*HHt - AHt  (slot 0, replicated), gradH = WtW*H - WtA (slot 1, local shard)
-        if (s->w_sharded) {           // only this rank's rows of the summed (AH')' exist here: partial sum, joined in dist_agree
-            rc = s->n_own > 0 ? launch_grad_pg(s->Wown, s->k, s->n_own, view_own(s), s->Gh, nullptr, s->pg_partials, s->scal, 0, s->st, s->wide_tmp)
+        if (s->ex.w_sharded) {           // only this rank's rows of the summed (AH')' exist here: partial sum, joined in dist_agree
+            rc = s->ex.n_own > 0 ? launch_grad_pg(s->ex.Wown, s->k, s->ex.n_own, view_own(s), s->Gh, nullptr, s->pg_partials, s->scal, 0, s->st, s->wide_tmp)
                               : launch_zero_f64(s->scal, 1, s->st);
         } else {
             rc = launch_grad_pg(s->Wt, s->k, s->m, view2(s), s->Gh, nullptr, s->pg_partials, s->scal, 0, s->st, s->wide_tmp);
@@ -153,7 +153,7 @@ int update_progress(smk_solver* s, int iter_index, double* metric)
 int progress_depth(const smk_solver* s)
 {
     const int forced = sw::progress_depth();
-    if (is_dist(s) || s->comm || forced <= 1) return 1;
+    if (is_dist(s) || s->ex.comm || forced <= 1) return 1;
     if (snapshot_elems(s->k, s->m, s->n) * sizeof(double) > ((size_t)1 << 30)) return 1;
     return std::min(forced, check_ring::MAX_DEPTH);
 }
@@ -209,7 +209,7 @@ int progress_begin(smk_solver* s, int b, bool snapshot, bool allow_defer)
     // BPP: gradW is the dual of the W-side NNLS (nmf_solver_bpp.hpp:362-366), whose projected-gradient sum is exactly zero after a
     // solve that reached optimality (a solve that did not has raised the failure flag); SMK_BPP_GRADW=1 forms HH' W' - (AH')' anyway
     const bool bpp_dual_is_gradient = !sw::bpp_gradw();
-    if (fused_check && s->o.prog_est_algorithm == SMK_PROG_PG_RATIO && !is_dist(s) && !is_wide(s->k) && !s->w_sharded) {
+    if (fused_check && s->o.prog_est_algorithm == SMK_PROG_PG_RATIO && !is_dist(s) && !is_wide(s->k) && !s->ex.w_sharded) {
         // round 6: gradients + snapshot in one launch, sums + failure flag written into the pinned slot by a second (kernels.hip:
         // grad_pg2_snap_kernel, sum_partials2_host_kernel); SMK_PROGRESS_FUSED=0: the four stream operations of before
         if (snapshot) { rc = ensure_snapshot(s, b); if (rc) return rc; }
@@ -240,7 +240,7 @@ int progress_begin(smk_solver* s, int b, bool snapshot, bool allow_defer)
     }
     if (snapshot) {
         rc = ensure_snapshot(s, b); if (rc) return rc;
-        rc = s->w_sharded ? launch_snapshot(s->Wown, s->n_own, s->H, s->n, s->Gw, pc.snap[b], s->k, 1, s->st)
+        rc = s->ex.w_sharded ? launch_snapshot(s->ex.Wown, s->ex.n_own, s->H, s->n, s->Gw, pc.snap[b], s->k, 1, s->st)
                           : launch_snapshot(s->Wt, s->m, s->H, s->n, s->Gw, pc.snap[b], s->k, 1, s->st);
         if (rc) return rc;
     }
@@ -293,7 +293,7 @@ int progress_end(smk_solver* s, int b, int iter_index, double* metric)
 
 int progress_restore(smk_solver* s, int b)
 {
-    int rc = s->w_sharded ? launch_snapshot(s->Wown, s->n_own, s->H, s->n, s->Gw, s->pc.snap[b], s->k, 0, s->st)
+    int rc = s->ex.w_sharded ? launch_snapshot(s->ex.Wown, s->ex.n_own, s->H, s->n, s->Gw, s->pc.snap[b], s->k, 0, s->st)
                           : launch_snapshot(s->Wt, s->m, s->H, s->n, s->Gw, s->pc.snap[b], s->k, 0, s->st);
     if (rc) return rc;
     // whatever the undone iteration did to the failure flag is void; products / HH' are stale
@@ -302,7 +302,7 @@ int progress_restore(smk_solver* s, int b)
     SMK_HIP(hipStreamSynchronize(s->st));
     s->inited = false;
     s->wc_valid = false;
-    if (s->w_sharded) s->w_full = false;    // the snapshot holds this rank's own rows; the full copy is stale
+    if (s->ex.w_sharded) s->ex.w_full = false;    // the snapshot holds this rank's own rows; the full copy is stale
     return 0;
 }
 

@@ -161,7 +161,7 @@ int smk_solver_residual(smk_solver* s, double* resid_sq, double* a_sq, double* c
     if (!s) { set_error("smk_solver_residual: null solver"); return SMK_BAD_PARAM; }
     int rc = residual_args("smk_solver_residual", s->a, s->k, s->Wt, s->H, resid_sq, a_sq);
     if (rc) return rc;
-    if (s->ar || s->comm) { set_error("smk_solver_residual: not available on a solver with a communicator"); return SMK_UNSUPPORTED; }
+    if (s->ex.ar || s->ex.comm) { set_error("smk_solver_residual: not available on a solver with a communicator"); return SMK_UNSUPPORTED; }
     if (!s->have_factors) { set_error("smk_solver_residual: the solver has no factors yet"); return SMK_BAD_PARAM; }
     Entry e(s->st);
     return residual_from_views(e, s->a, s->k, DeviceView::rows(s->Wt, s->KP), DeviceView::cols(s->H, s->KP), resid_sq, a_sq, nullptr, col_resid_sq);

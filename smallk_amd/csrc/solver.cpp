@@ -1,6 +1,10 @@
 // smallk_amd/csrc/solver.cpp -- the solver handle of the C ABI (include/smallk_amd.h): planning and
-// allocation, the communicator plumbing, the NmfSolve<> driver loop and the per-iteration schedules
-// (MU / HALS / BPP / RANK2) expressed as launches of the kernels in kernels.hip.
+// allocation, the NmfSolve<> driver loop and the per-iteration schedules (MU / HALS / BPP / RANK2)
+// expressed as launches of the kernels in kernels.hip, with everything an iteration calls -- the
+// exchange with the other ranks included -- in this one translation unit.  Beside it: attach.cpp
+// (giving the handle a communicator), factors.cpp (factors in and out), guard.cpp (the run-time guard
+// of the product form), timing.cpp (what a caller reads about the passes), progress.cpp (the stopping
+// rule's check), standalone.cpp (the entries without a handle).
 //
 // Device data layout (all in HBM, fp64 unless noted):
 //   A   : m_pad x n_pad   bf16|f32, column-major, zero padded (rows to 128, cols to 128)
@@ -31,35 +35,13 @@ extern "C" {
 // BPP with a native communicator: every rank solves only its own blocks of W, so it needs only those rows of the summed
 // (AH')' -- a reduce-scatter instead of an all-reduce (half the bytes on the wire) -- and the other ranks receive the
 // packed streaming operand of those rows (4 B per entry in the fp16 form) instead of the fp64 values
-static inline bool w_rows_sharded(const smk_solver* s) { return s->w_sharded; }
+static inline bool w_rows_sharded(const smk_solver* s) { return s->ex.w_sharded; }
 
-// rows [r0, r1) of chunk j (clipped to the padded row count of the H*At pass) and this rank's block [a, b) of it
-// (valid rows only: b <= m; empty when b <= a)
+// rows [r0, r1) of chunk j (clipped to the padded row count of the H*At pass; this rank's block of it: own_block, solver_internal.h)
 static inline void chunk_rows(const smk_solver* s, int j, i64* r0, i64* r1)
 {
-    *r0 = (i64)j * s->world * s->blk;
-    *r1 = std::min<i64>(*r0 + (i64)s->world * s->blk, s->pl2.ncols_pad);
-}
-static inline void own_block(const smk_solver* s, int j, i64* a, i64* b)
-{
-    *a = ((i64)j * s->world + s->rank) * s->blk;
-    *b = std::min<i64>(*a + s->blk, s->m);
-}
-
-// workspace layout: [R2red: rows x kpp f32|f64][Gh: KP*KP f64][scal: 8 f64][Wt: KP x rows f64].  rows = the padded
-// row count (callback hook: one all-reduce per buffer, any world) or world * nchunk * blk with a native communicator
-// (equal blocks for the reduce-scatter / all-gather)
-static inline i64 comm_rows(const smk_solver* s) { return s->comm ? std::max<i64>(s->rows_cap, s->pl2.ncols_pad) : s->pl2.ncols_pad; }
-static size_t comm_bytes(const smk_solver* s)
-{
-    size_t b = (size_t)comm_rows(s) * s->kpp * (s->red_f64 ? sizeof(double) : sizeof(float));
-    b = (b + 255) / 256 * 256;
-    b += (size_t)s->KP * s->KP * sizeof(double);
-    b = (b + 255) / 256 * 256;
-    b += 8 * sizeof(double);
-    b = (b + 255) / 256 * 256;
-    b += (size_t)s->KP * (size_t)comm_rows(s) * sizeof(double);
-    return b;
+    *r0 = (i64)j * s->ex.world * s->ex.blk;
+    *r1 = std::min<i64>(*r0 + (i64)s->ex.world * s->ex.blk, s->pl2.ncols_pad);
 }
 
 // What the transposed-source kernels cover: MU, HALS and BPP with the 16-bit product forms (the reference's BPP keeps a transpose
@@ -74,7 +56,8 @@ static bool single_copy_serves(const smk_solver* s)
 }
 
 // Everything that depends on the product form (s->nsplit): the launch plans of both passes and the fp16 row scales ...
-static int plan_products(smk_solver* s)
+// (extern "C++": attach.cpp and guard.cpp re-plan through these two, solver_internal.h)
+extern "C++" int smk::plan_products(smk_solver* s)
 {
     const smk_matrix* a = s->a;
     if (s->nsplit == NSPLIT_F16X2 && a->ascale == 0.f) {
@@ -124,7 +107,7 @@ static int plan_products(smk_solver* s)
     }
     const bool pack_env = sw::nnls_pack();                          // read per plan, like SMK_NSPLIT (0 = the separate reduce-and-pack launch)
     s->pack_in_solve = pack_env && !s->pack_in_solve_off && s->o.algorithm == SMK_ALG_BPP && s->KP == 16 && s->nsplit == NSPLIT_F16X2 &&
-                       !a->sparse && !a->single && s->ng == 1 && !is_dist(s) && !s->comm && bigprod_supports_tail(s->pl1) && bigprod_supports_tail(s->pl2);
+                       !a->sparse && !a->single && s->ng == 1 && !is_dist(s) && !s->ex.comm && bigprod_supports_tail(s->pl1) && bigprod_supports_tail(s->pl2);
     if (s->pack_in_solve && (a->colnorm_max < 0.0 || a->rownorm_max < 0.0)) {
         const int rc0 = matrix_measure_norms(a, s->st);
         if (rc0) return rc0;
@@ -132,7 +115,7 @@ static int plan_products(smk_solver* s)
     return 0;
 }
 // ... and the buffers sized by those plans: the packed operands and the partial products (dense A)
-static int alloc_product_buffers(smk_solver* s)
+extern "C++" int smk::alloc_product_buffers(smk_solver* s)
 {
     int rc = 0;
     s->own.drop(&s->packW); s->own.drop(&s->packH); s->own.drop(&s->P1); s->own.drop(&s->P2);      // a re-plan sizes them anew
@@ -281,269 +264,19 @@ void smk_solver_destroy(smk_solver* s)
     delete s;
 }
 
-int smk_solver_comm_workspace_bytes(const smk_solver* s, size_t* bytes)
-{
-    if (!s || !bytes) return SMK_BAD_PARAM;
-    *bytes = comm_bytes(s);
-    return SMK_OK;
-}
-
-static void carve_workspace(smk_solver* s, void* workspace)
-{
-    unsigned char* p = (unsigned char*)workspace;
-    s->R2red = (float*)p;
-    size_t b = (size_t)comm_rows(s) * s->kpp * (s->red_f64 ? sizeof(double) : sizeof(float));      // same layout as comm_bytes()
-    b = (b + 255) / 256 * 256;
-    s->Gh = (double*)(p + b);
-    b += (size_t)s->KP * s->KP * sizeof(double);
-    b = (b + 255) / 256 * 256;
-    s->scal = (double*)(p + b);
-    b += 8 * sizeof(double);
-    b = (b + 255) / 256 * 256;
-    s->Wt = (double*)(p + b);
-}
-
-int smk_solver_set_comm(smk_solver* s, int rank, int world, smk_allreduce_fn fn, void* user, void* workspace,
-                        size_t workspace_bytes)
-{
-    if (!s || world < 1 || rank < 0 || rank >= world) return SMK_BAD_PARAM;
-    if (world > 1 && !fn) return SMK_BAD_PARAM;
-    if (s->comm) { set_error("a native communicator is attached"); return SMK_BAD_PARAM; }
-    s->rank = rank; s->world = world;
-    if (fn && (!workspace || workspace_bytes < comm_bytes(s))) return SMK_BAD_PARAM;
-    if (fn) {
-        if (!s->ar) { s->home[0] = s->Gh; s->home[1] = s->scal; s->home[2] = s->Wt; }      // still in the handle's own blocks: remember the way back
-        carve_workspace(s, workspace);
-    } else if (s->ar) {
-        s->Gh = s->home[0]; s->scal = s->home[1]; s->Wt = s->home[2];
-    }
-    s->ar = fn; s->ar_user = user;
-    return SMK_OK;
-}
-
-// Native path: every collective is issued from C on the solver's second stream (RCCL over xGMI, or the in-process
-// stand-in).  Call before set_factors().  The communicator must outlive the solver.
-int smk_solver_attach_comm(smk_solver* s, smk_comm* comm)
-{
-    if (!s || !comm) return SMK_BAD_PARAM;
-    if (s->ar || s->comm) { set_error("solver already has a communicator"); return SMK_BAD_PARAM; }
-    s->comm = comm;
-    s->rank = comm->rank; s->world = comm->world;
-    // MEASUREMENT HOOK (bench.py --emulate-world N, one GPU): the geometry of rank 0 of N ranks -- row blocks, chunk
-    // sizes, per-rank NNLS / Gram / packing work -- while the collectives run through the real one-rank communicator.
-    // Times a rank's work without the transfers; the blocks of the other ranks never arrive, so the factors mean nothing.
-    if (const int emu = sw::comm_emulate_world(); comm->world == 1 && emu > 1 && emu <= 64) { s->world = emu; s->rank = 0; }
-    // The ranks must run ONE exchange protocol.  The product form is chosen per solver, and one input of that choice -- the
-    // spread of the column scales -- is measured on the rank's LOCAL column shard: a rank whose shard alone spans more than
-    // 2^28 would take the accurate form (and with it other buffers and other collectives) while its peers do not.  So the
-    // form is agreed here, first thing, over the communicator: any rank that wants the accurate form moves all of them.
-    // Every rank of the communicator calls attach, so this is a collective like the ones that follow.
-    if (comm->world > 1) {
-        double want = s->nsplit == NSPLIT_F64 ? 1.0 : 0.0;
-        SMK_HIP(hipMemcpy(s->scal, &want, sizeof(double), hipMemcpyHostToDevice));
-        int arc = comm_allreduce(comm, s->scal, 1, 1, s->st);
-        if (arc) { s->comm = nullptr; return arc; }
-        SMK_HIP(hipStreamSynchronize(s->st));
-        SMK_HIP(hipMemcpy(&want, s->scal, sizeof(double), hipMemcpyDeviceToHost));
-        if (want > 0.0 && s->nsplit != NSPLIT_F64 && !s->a->sparse) {
-            s->nsplit = NSPLIT_F64;
-            arc = plan_products(s);
-            if (!arc && alloc_product_buffers(s)) arc = SMK_DEVICE_ERROR;
-            if (arc) { s->comm = nullptr; return arc; }
-        }
-    }
-    // chunk geometry: blocks of >= 4096 rows, at most 4 chunks (SMK_COMM_CHUNKS overrides: 1 .. 8), block a multiple of
-    // 256 rows (the column tile of the streaming kernels and a whole number of packed chunk pairs)
-    {
-        const i64 mpad = s->pl2.ncols_pad;
-        i64 c = mpad / ((i64)s->world * 4096);
-        c = std::max<i64>(1, std::min<i64>(c, 4));
-        if (const auto ce = sw::comm_chunks(); ce.set) c = std::max(1, std::min(ce.v, MAX_CHUNKS));
-        s->blk = round_up((mpad + (i64)s->world * c - 1) / ((i64)s->world * c), 256);
-        s->nchunk = (int)((mpad + (i64)s->world * s->blk - 1) / ((i64)s->world * s->blk));      // chunks that hold rows
-        s->rows_cap = (i64)s->nchunk * s->world * s->blk;
-    }
-    {
-        // fp64 on the wire unless SMK_COMM_F64=0.  SURVEY 8e suggested fp32 (half the bytes); measured at the full C4 size on
-        // the bench's noise-like data (tools/shard8_fullsize.py: 8 shards against one GPU): fp32 costs 1.1e-4 in W after ONE
-        // iteration -- the sums over 65536 columns are ~500, their fp32 rounding 3e-5, and HH' of such data amplifies it a
-        // thousand times -- against 6e-7 with fp64.  With the exchange pipelined behind the pass the extra bytes are hidden
-        // except in the last chunk.
-        s->red_f64 = sw::comm_f64() != 0;
-    }
-    // BPP and MU update the rows of W independently of each other: every rank takes its own blocks (HALS normalises column by
-    // column over ALL rows inside its sweep and keeps the replicated update)
-    // (also under the accurate product form: its W'A pass reads the fp64 factor itself, so the fp64 own blocks are gathered per
-    // chunk in place of the packed operand -- prod1_sharded)
-    s->w_sharded = (s->o.algorithm == SMK_ALG_BPP || s->o.algorithm == SMK_ALG_MU) && !s->a->sparse && (s->world > 1 || comm_forced());
-    const size_t bytes = comm_bytes(s);
-    if (s->own.dev((unsigned char**)&s->comm_ws, bytes)) { s->comm = nullptr; s->w_sharded = false; set_error("no memory for the communicator workspace"); return SMK_DEVICE_ERROR; }
-    SMK_HIP(hipMemsetAsync(s->comm_ws, 0, bytes, s->st));
-    carve_workspace(s, s->comm_ws);
-    if (!s->a->sparse && s->pl2.S == 1 && s->red_f64) {
-        // one row split and fp64 on the wire: the partial products ARE the send buffer.  They get room for the equal
-        // blocks of the last chunk (rows past the padded row count are never written and stay zero).
-        s->own.drop(&s->P2);
-        const size_t pe = (size_t)comm_rows(s) * s->kpp;
-        if (s->own.dev(&s->P2, pe)) return SMK_DEVICE_ERROR;
-        SMK_HIP(hipMemsetAsync(s->P2, 0, pe * sizeof(double), s->st));
-        s->R2red = (float*)s->P2;
-        s->r2_alias = true;
-    }
-    if (s->w_sharded) {
-        // the packed operand of W is gathered in equal blocks: room for rows_cap rows, groups laid out for that length
-        s->own.drop(&s->packW);
-        const size_t pb = packed_bytes(s->a->storage, s->k, s->rows_cap, s->nsplit);
-        if (s->own.dev((unsigned char**)&s->packW, pb)) return SMK_DEVICE_ERROR;
-        SMK_HIP(hipMemsetAsync(s->packW, 0, pb, s->st));
-        size_t off = 0;
-        for (int g = 0; g < s->ng; ++g) {
-            s->pg1[g].pack_offset = off;
-            off += packed_bytes(s->a->storage, s->pg1[g].kg, s->rows_cap, s->nsplit);
-        }
-        s->pl1.pack_offset = s->pg1[0].pack_offset;
-        const size_t own_rows = (size_t)s->nchunk * s->blk;
-        const size_t rb = s->red_f64 ? sizeof(double) : sizeof(float);
-        if (s->own.dev(&s->Wown, own_rows * s->KP)) return SMK_DEVICE_ERROR;
-        if (s->own.dev((unsigned char**)&s->R2own, own_rows * s->kpp * rb)) return SMK_DEVICE_ERROR;
-        SMK_HIP(hipMemsetAsync(s->Wown, 0, own_rows * s->KP * sizeof(double), s->st));
-        SMK_HIP(hipMemsetAsync(s->R2own, 0, own_rows * s->kpp * rb, s->st));
-        s->n_own = 0;
-        for (int j = 0; j < s->nchunk; ++j) {
-            i64 a, b;
-            own_block(s, j, &a, &b);
-            if (b > a) s->n_own += b - a;
-        }
-    }
-    int erc = s->own.stream(&s->st2, hipStreamNonBlocking);
-    for (hipEvent_t* e : {&s->ev_gram, &s->ev_gh, &s->ev_x, &s->ev_y}) erc |= s->own.event(e, hipEventDisableTiming);
-    for (int j = 0; j < MAX_CHUNKS; ++j)
-        for (hipEvent_t* e : {&s->ev_c[j], &s->ev_r[j], &s->ev_a[j]}) erc |= s->own.event(e, hipEventDisableTiming);
-    if (erc) return SMK_DEVICE_ERROR;
-    // nothing is allocated once the collectives are in flight (several ranks may live in one process)
-    return progress_prealloc(s);
-}
-
-// this rank's blocks of the full W (every rank holds all of it after set_factors / a gather / the final scaling) -> Wown
-static int scatter_own(smk_solver* s)
-{
-    for (int j = 0; j < s->nchunk; ++j) {
-        i64 a, b;
-        own_block(s, j, &a, &b);
-        if (b > a)
-            SMK_HIP(hipMemcpyAsync(s->Wown + (i64)j * s->blk * s->KP, s->Wt + a * s->KP, (size_t)(b - a) * s->KP * sizeof(double),
-                                   hipMemcpyDeviceToDevice, s->st));
-    }
-    return 0;
-}
-
-// What every way of setting the factors shares.  Before the factors are written: a matrix refilled after this solver was created
-// has its fp16 product scale and its norms measured again.  After: the failure flag, the copies of the start, this rank's blocks
-// of a row-sharded W, the state of a fresh run.
-static int factors_begin(smk_solver* s)
-{
-    if (s->nsplit == NSPLIT_F16X2 && (s->a->ascale == 0.f || s->a->ascale != s->pg1[0].ascale)) {
-        // the matrix was refilled after this solver was created: its fp16 product scale follows the new contents
-        if (s->a->ascale == 0.f) { const int rc0 = matrix_measure_scale(s->a, s->st); if (rc0) return rc0; }
-        for (int g = 0; g < s->ng; ++g) s->pg1[g].ascale = s->pg2[g].ascale = s->a->ascale;
-        s->pl1.ascale = s->pl2.ascale = s->a->ascale;
-    }
-    if (s->pack_in_solve && (s->a->colnorm_max < 0.0 || s->a->rownorm_max < 0.0)) {      // ... and so do the norms behind the packing NNLS launch
-        const int rc0 = matrix_measure_norms(s->a, s->st);
-        if (rc0) return rc0;
-    }
-    return 0;
-}
-
-static int factors_end(smk_solver* s)
-{
-    const int big = INT_MAX;
-    SMK_HIP(hipMemcpyAsync(s->fail_flag, &big, sizeof(int), hipMemcpyHostToDevice, s->st));
-    if (s->W0c) {
-        SMK_HIP(hipMemcpyAsync(s->W0c, s->Wt, (size_t)s->KP * s->m * sizeof(double), hipMemcpyDeviceToDevice, s->st));
-        SMK_HIP(hipMemcpyAsync(s->H0c, s->H, (size_t)s->KP * s->n * sizeof(double), hipMemcpyDeviceToDevice, s->st));
-    }
-    if (s->w_sharded) { const int rc = scatter_own(s); if (rc) return rc; }
-    SMK_HIP(hipStreamSynchronize(s->st));
-    s->w_full = true;
-    s->wc_valid = false;
-    s->have_factors = true;
-    s->inited = false;
-    s->normalized = false;
-    s->iter = 0;
-    s->pc.reset_estimator();
-    return SMK_OK;
-}
-
-// the solver's resident factors as the pair the view entries convert into and out of (entry.h): buffers the pair does not own
-static FactorPair resident_pair(const smk_solver* s) { return {s->m, s->n, s->k, s->KP, s->st, s->Wt, s->H}; }
-
-int smk_solver_set_factors(smk_solver* s, const double* W0, int64_t ldW, const double* H0, int64_t ldH)
-{
-    if (!s || !W0 || !H0) return SMK_BAD_PARAM;
-    if (ldW < s->m || ldH < s->k) { set_error("leading dimension too small"); return SMK_BAD_PARAM; }
-    int rc = factors_begin(s);
-    if (!rc) rc = resident_pair(s).zero();
-    if (rc) return rc;
-    // W0 (m x k, host) -> tmpW (m x k, ld m) -> Wt (KP x m)
-    SMK_HIP(hipMemcpy2DAsync(s->tmpW, (size_t)s->m * sizeof(double), W0, (size_t)ldW * sizeof(double),
-                             (size_t)s->m * sizeof(double), (size_t)s->k, hipMemcpyHostToDevice, s->st));
-    rc = launch_transpose_f64(s->tmpW, s->m, s->Wt, s->KP, s->m, s->k, s->st);
-    if (rc) return rc;
-    SMK_HIP(hipMemcpy2DAsync(s->H, (size_t)s->KP * sizeof(double), H0, (size_t)ldH * sizeof(double),
-                             (size_t)s->k * sizeof(double), (size_t)s->n, hipMemcpyHostToDevice, s->st));
-    return factors_end(s);
-}
-
-// The same start from views in device memory (a torch tensor's data_ptr and strides): W0 is m x k, H0 is k x n.  The strided
-// convert kernel writes Wt (KP x m) and H (KP x n) directly -- a row-major W0 already has the layout of Wt with pitch k instead
-// of KP, so it is a straight copy, with no pass through tmpW.
-int smk_solver_set_factors_device(smk_solver* s, const void* W0, int dtypeW, int64_t rsW, int64_t csW, const void* H0, int dtypeH,
-                                  int64_t rsH, int64_t csH, void* stream)
-{
-    const char* who = "smk_solver_set_factors_device";
-    if (!s) return SMK_BAD_PARAM;
-    const FactorPair f = resident_pair(s);
-    const DeviceView vW = DeviceView::in(W0, dtypeW, rsW, csW), vH = DeviceView::in(H0, dtypeH, rsH, csH);
-    int rc = check_factor_dtypes(who, "factors", dtypeW, dtypeH);
-    if (!rc) rc = f.check(who, vW, vH, false, false, "W0", "H0");
-    if (rc) return rc;
-    Entry e(s->st);
-    rc = e.join(stream);
-    if (!rc) rc = factors_begin(s);
-    if (!rc) rc = f.zero();
-    if (!rc) rc = f.load(vW, vH);
-    if (rc) return rc;
-    return e.synced(factors_end(s));
-}
-
-// The same start as smk_solver_set_factors(W0, H0) with W0 = smk_uniform_fill_host(m x k, seed_w), H0 = smk_uniform_fill_host
-// (k x n, seed_h) -- the RandomMatrix stand-in of every caller in this library -- generated on the device: no host fill, no
-// upload.  (HierNMF2 draws two such matrices per node.)  Unsharded solvers only.
-int smk_solver_set_factors_uniform(smk_solver* s, uint64_t seed_w, uint64_t seed_h)
-{
-    if (!s) return SMK_BAD_PARAM;
-    if (is_dist(s) || s->comm) { set_error("set_factors_uniform: not for sharded solvers"); return SMK_UNSUPPORTED; }
-    int rc = factors_begin(s);
-    if (!rc) rc = launch_fill_factor_uniform(s->Wt, s->k, s->m, seed_w, 1, s->st);
-    if (!rc) rc = launch_fill_factor_uniform(s->H, s->k, s->n, seed_h, 0, s->st);
-    if (rc) return rc;
-    return factors_end(s);       // never row-sharded here
-}
-
 // ---- collectives -------------------------------------------------------------------------------
 // callback hook: one host call per buffer, in stream order on the main stream
 static int dist_allreduce_cb(smk_solver* s, void* ptr, i64 count, int f64)
 {
-    if (s->ar && s->ar(s->ar_user, ptr, (int64_t)count, f64)) { set_error("all-reduce callback failed"); return SMK_DEVICE_ERROR; }
+    if (s->ex.ar && s->ex.ar(s->ex.ar_user, ptr, (int64_t)count, f64)) { set_error("all-reduce callback failed"); return SMK_DEVICE_ERROR; }
     return 0;
 }
 
 // A pair of timing events for one span of smk_solver_kernel_time: a pair whose times resolve_events has read, else a new one
-// from the owner.  The caller records both and pushes the span onto s->ev[slot], or hands it back to s->span_pool.
-static int span_open(smk_solver* s, smk_solver::TimedSpan* sp, int counts = 1)
+// from the owner.  The caller records both and pushes the span onto s->timing.ev[slot], or hands it back to s->timing.span_pool.
+static int span_open(smk_solver* s, Timing::TimedSpan* sp, int counts = 1)
 {
-    if (!s->span_pool.empty()) { *sp = s->span_pool.back(); s->span_pool.pop_back(); }
+    if (!s->timing.span_pool.empty()) { *sp = s->timing.span_pool.back(); s->timing.span_pool.pop_back(); }
     else if (s->own.event(&sp->e0, hipEventDefault) || s->own.event(&sp->e1, hipEventDefault)) return SMK_DEVICE_ERROR;
     sp->counts = counts;
     return 0;
@@ -553,7 +286,7 @@ static int span_open(smk_solver* s, smk_solver::TimedSpan* sp, int counts = 1)
 static int comm_fork(smk_solver* s, hipEvent_t ev)
 {
     SMK_HIP(hipEventRecord(ev, s->st));
-    SMK_HIP(hipStreamWaitEvent(s->st2, ev, 0));
+    SMK_HIP(hipStreamWaitEvent(s->ex.st2, ev, 0));
     return 0;
 }
 // The main stream waits for `n` events of the collective stream.  On a timed pass the wait is bracketed by two events on the
@@ -562,19 +295,19 @@ static int comm_fork(smk_solver* s, hipEvent_t ev)
 // time, so an exchange that is hidden completely still reads ~5 us per wait).
 static int main_waits_for_comm(smk_solver* s, const hipEvent_t* evs, int n)
 {
-    const bool timed = s->timing && (s->pass_timed[0] || s->pass_timed[1]);
-    smk_solver::TimedSpan sp{};
-    if (timed && (s->cal_counter++ & 3u) == 0 && s->st2) {        // every fourth bracket is preceded by a calibration bracket
-        if (!s->ev_cal) {
-            if (s->own.event(&s->ev_cal, hipEventDisableTiming)) return SMK_DEVICE_ERROR;
-            SMK_HIP(hipEventRecord(s->ev_cal, s->st2));
+    const bool timed = s->timing.on && (s->timing.pass_timed[0] || s->timing.pass_timed[1]);
+    Timing::TimedSpan sp{};
+    if (timed && (s->timing.cal_counter++ & 3u) == 0 && s->ex.st2) {        // every fourth bracket is preceded by a calibration bracket
+        if (!s->timing.ev_cal) {
+            if (s->own.event(&s->timing.ev_cal, hipEventDisableTiming)) return SMK_DEVICE_ERROR;
+            SMK_HIP(hipEventRecord(s->timing.ev_cal, s->ex.st2));
         } else {
-            smk_solver::TimedSpan cal{};
+            Timing::TimedSpan cal{};
             if (span_open(s, &cal)) return SMK_DEVICE_ERROR;
             (void)hipEventRecord(cal.e0, s->st);
-            (void)hipStreamWaitEvent(s->st, s->ev_cal, 0);
+            (void)hipStreamWaitEvent(s->st, s->timing.ev_cal, 0);
             (void)hipEventRecord(cal.e1, s->st);
-            s->ev[4].push_back(cal);
+            s->timing.ev[4].push_back(cal);
         }
     }
     if (timed) {
@@ -583,46 +316,46 @@ static int main_waits_for_comm(smk_solver* s, const hipEvent_t* evs, int n)
     }
     for (int i = 0; i < n; ++i)
         if (hipStreamWaitEvent(s->st, evs[i], 0) != hipSuccess) {
-            if (timed) s->span_pool.push_back(sp);
+            if (timed) s->timing.span_pool.push_back(sp);
             set_error("hipStreamWaitEvent failed");
             return SMK_DEVICE_ERROR;
         }
     if (timed) {
         (void)hipEventRecord(sp.e1, s->st);
-        s->ev[3].push_back(sp);
+        s->timing.ev[3].push_back(sp);
     }
     return 0;
 }
 // ... and the main stream waits for what st2 has been given so far
 static int comm_join(smk_solver* s, hipEvent_t ev)
 {
-    SMK_HIP(hipEventRecord(ev, s->st2));
+    SMK_HIP(hipEventRecord(ev, s->ex.st2));
     return main_waits_for_comm(s, &ev, 1);
 }
 
 // a collective on st2 bracketed by events when timing is on (slot 2 of smk_solver_kernel_time)
 static int timed_collective(smk_solver* s, int pass, const std::function<int()>& issue)
 {
-    if (!s->timing || !s->pass_timed[pass]) return issue();
-    smk_solver::TimedSpan sp{};
+    if (!s->timing.on || !s->timing.pass_timed[pass]) return issue();
+    Timing::TimedSpan sp{};
     if (span_open(s, &sp)) return SMK_DEVICE_ERROR;
-    (void)hipEventRecord(sp.e0, s->st2);
+    (void)hipEventRecord(sp.e0, s->ex.st2);
     const int rc = issue();
-    if (rc) { s->span_pool.push_back(sp); return rc; }
-    (void)hipEventRecord(sp.e1, s->st2);
-    s->ev[2].push_back(sp);
+    if (rc) { s->timing.span_pool.push_back(sp); return rc; }
+    (void)hipEventRecord(sp.e1, s->ex.st2);
+    s->timing.ev[2].push_back(sp);
     return 0;
 }
 
 // a small in-place sum that the main stream needs right away (scalars of the stopping rule, W'W of a row-sharded W)
 static int dist_allreduce_now(smk_solver* s, void* ptr, i64 count, int f64)
 {
-    if (!s->comm) return dist_allreduce_cb(s, ptr, count, f64);
-    int rc = comm_fork(s, s->ev_x);
+    if (!s->ex.comm) return dist_allreduce_cb(s, ptr, count, f64);
+    int rc = comm_fork(s, s->ex.ev_x);
     if (rc) return rc;
-    rc = comm_allreduce(s->comm, ptr, count, f64, s->st2);
+    rc = comm_allreduce(s->ex.comm, ptr, count, f64, s->ex.st2);
     if (rc) return rc;
-    return comm_join(s, s->ev_y);
+    return comm_join(s, s->ex.ev_y);
 }
 
 // HH' is needed only after the H*At pass: with a native communicator its all-reduce runs on the second stream
@@ -630,33 +363,33 @@ static int dist_allreduce_now(smk_solver* s, void* ptr, i64 count, int f64)
 static int allreduce_gh(smk_solver* s)
 {
     if (!is_dist(s)) return 0;
-    if (!s->comm) return dist_allreduce_cb(s, s->Gh, (i64)s->KP * s->KP, 1);
-    int rc = comm_fork(s, s->ev_gram);
+    if (!s->ex.comm) return dist_allreduce_cb(s, s->Gh, (i64)s->KP * s->KP, 1);
+    int rc = comm_fork(s, s->ex.ev_gram);
     if (rc) return rc;
-    rc = comm_allreduce(s->comm, s->Gh, (i64)s->KP * s->KP, 1, s->st2);
+    rc = comm_allreduce(s->ex.comm, s->Gh, (i64)s->KP * s->KP, 1, s->ex.st2);
     if (rc) return rc;
-    SMK_HIP(hipEventRecord(s->ev_gh, s->st2));
-    s->gh_pending = true;
+    SMK_HIP(hipEventRecord(s->ex.ev_gh, s->ex.st2));
+    s->ex.gh_pending = true;
     return 0;
 }
 static int wait_gh(smk_solver* s)
 {
-    if (!s->gh_pending) return 0;
-    const int rc = main_waits_for_comm(s, &s->ev_gh, 1);
+    if (!s->ex.gh_pending) return 0;
+    const int rc = main_waits_for_comm(s, &s->ex.ev_gh, 1);
     if (rc) return rc;
-    s->gh_pending = false;
+    s->ex.gh_pending = false;
     return 0;
 }
 // the main stream joins the chunk exchanges of the last H*At pass (every consumer of the summed (AH')' calls this)
 // (extern "C++": progress.cpp calls it too, solver_internal.h -- as gather_w, sync_and_check and dist_agree below)
 extern "C++" int smk::wait_r2(smk_solver* s)
 {
-    if (!s->r2_pending) return 0;
+    if (!s->ex.r2_pending) return 0;
     // (the chunk exchanges were recorded on ONE in-order stream: the last event covers the others -- one barrier packet on the
     // main stream instead of nchunk; tools/mb/mb_event_hop.hip prices them)
-    const int rc = main_waits_for_comm(s, &s->ev_r[s->nchunk - 1], 1);
+    const int rc = main_waits_for_comm(s, &s->ex.ev_r[s->ex.nchunk - 1], 1);
     if (rc) return rc;
-    s->r2_pending = false;
+    s->ex.r2_pending = false;
     return 0;
 }
 
@@ -670,8 +403,8 @@ static inline double* inv_scratch(smk_solver* s, int side)
 // sharded run finishes on the second stream)
 static int start_inverse(smk_solver* s, int side, const double* G, hipEvent_t after = nullptr)
 {
-    s->inv_done[side] = false;
-    s->inv_ride[side] = false;
+    Handoff& h = s->hand[side];
+    h.forget_inverse();                 // G is new: whatever rode, ran beside or was done belonged to the matrix before it
     if (s->o.algorithm != SMK_ALG_BPP) return 0;
     {
         // The inverse is formed by one more workgroup of the product launch that follows this Gram matrix in every BPP schedule
@@ -682,7 +415,7 @@ static int start_inverse(smk_solver* s, int side, const double* G, hipEvent_t af
         const bool ride = sw::inv_ride();
         const bool route = s->KP == 64 || (s->KP == 32 && nnls_inverse_at_32());
         const bool carrier = s->a->sparse ? true : (s->ng == 1 && bigprod_supports_ride(side == 0 ? s->pg1[0] : s->pg2[0]));
-        if (ride && route && carrier && !after && !is_dist(s) && !s->comm && !s->w_sharded) { s->inv_ride[side] = true; return 0; }
+        if (ride && route && carrier && !after && !is_dist(s) && !s->ex.comm && !s->ex.w_sharded) { h.inverse_will_ride(); return 0; }
     }
     if (!s->st_inv) return 0;
     if (after) {
@@ -694,28 +427,29 @@ static int start_inverse(smk_solver* s, int side, const double* G, hipEvent_t af
     int rc = launch_gram_inverse(G, s->k, inv_scratch(s, side), s->st_inv);
     if (rc) return rc;
     SMK_HIP(hipEventRecord(s->ev_inv[side], s->st_inv));
-    s->inv_pending[side] = true;
+    h.inverse_sent_to_side_stream();
     return 0;
 }
-static bool guard_applies(const smk_solver* s);
+// `side` names the factor whose Gram matrix G is (0: W'W, the solve writes H; 1: HH', the solve writes W): hs is the hand-off
+// record of that factor, hx the one of the factor being solved
 static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, PartialView R, const double* G)
 {
-    if (s->inv_pending[side]) {
+    const int fx = side == 0 ? 1 : 0;                // the factor being solved (0 = W, 1 = H); the other one is `side`
+    Handoff &hs = s->hand[side], &hx = s->hand[fx];
+    if (hs.inverse_on_side_stream()) {
         SMK_HIP(hipStreamWaitEvent(s->st, s->ev_inv[side], 0));
-        s->inv_pending[side] = false;
-        s->inv_done[side] = true;
+        hs.inverse_joined();
     }
     // k in (8, 16], fp16 form, one GPU: the launch that solves ALL columns of a factor also leaves its Gram partials (the
     // gram_x that follows in every BPP schedule then only reduces them)
     const bool fuse = sw::nnls_gram();
     const i64 N = side == 0 ? s->n : s->m;
     const bool want = fuse && s->KP == 16 && s->nsplit == NSPLIT_F16X2 && !is_dist(s) && c0 == 0 && c1 == N && (X == s->H || X == s->Wt);
-    s->nnls_gram_nblk[side] = 0;
+    hx.gram_partials = 0;
     // ... and packs it, when the system matrix is the Gram matrix of a factor that an NNLS launch of this run produced (>= 0:
     // the bound behind the row scales needs that; the first solve of a run works from the caller's factor and packs the old way)
-    const int fx = side == 0 ? 1 : 0;                // the factor being solved (0 = W, 1 = H); the other one is `side`
     NnlsPack pk;
-    const bool pack = want && s->pack_in_solve && !s->pack_in_solve_off && !s->comm && s->from_nnls[side] && s->a->colnorm_max >= 0.0 && s->a->rownorm_max >= 0.0;
+    const bool pack = want && s->pack_in_solve && !s->pack_in_solve_off && !s->ex.comm && hs.from_nnls && s->a->colnorm_max >= 0.0 && s->a->rownorm_max >= 0.0;
     if (pack) {
         pk.out = (unsigned char*)(fx == 0 ? s->packW : s->packH);
         pk.xscale = s->xscale[fx];
@@ -727,12 +461,12 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
         // repeated without the packing: pack_fail_soft)
         pk.anorm *= sw::nnls_pack_test_anorm();
     }
-    s->nnls_packed[fx] = false;
+    hx.packed_by_solve = false;
     // slot 5 of smk_solver_kernel_time: the block-pivoting launches (both kernels of a k > 16 solve), sampled with the pass that fed them
-    smk_solver::TimedSpan tsp{};
-    if (s->timing && s->pass_timed[side] && c1 > c0 && span_open(s, &tsp) == 0) (void)hipEventRecord(tsp.e0, s->st);
+    Timing::TimedSpan tsp{};
+    if (s->timing.on && s->timing.pass_timed[side] && c1 > c0 && span_open(s, &tsp) == 0) (void)hipEventRecord(tsp.e0, s->st);
     else tsp.e1 = nullptr;                      // (a launch that cannot be timed still runs)
-    struct Stamp { smk_solver* s; smk_solver::TimedSpan sp; ~Stamp() { if (sp.e1) { (void)hipEventRecord(sp.e1, s->st); s->ev[5].push_back(sp); } } } stamp{s, tsp};
+    struct Stamp { smk_solver* s; Timing::TimedSpan sp; ~Stamp() { if (sp.e1) { (void)hipEventRecord(sp.e1, s->st); s->timing.ev[5].push_back(sp); } } } stamp{s, tsp};
     // riders of the checked loop (check_rides_in_nnls): the previous iteration's projected-gradient sum, this iteration's snapshot
     NnlsRiders rd;
     bool riders = false;
@@ -748,8 +482,8 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
             riders = true;
         }
     }
-    const int rc = launch_nnls_bpp(X, nullptr, s->k, c0, c1, R, G, s->fail_flag, s->iter, inv_scratch(s, side), s->inv_done[side] ? 1 : 0, ctx().cus, s->st,
-                                   want ? s->gram_scratch : nullptr, want ? &s->nnls_gram_nblk[side] : nullptr, pack ? &pk : nullptr,
+    const int rc = launch_nnls_bpp(X, nullptr, s->k, c0, c1, R, G, s->fail_flag, s->iter, inv_scratch(s, side), hs.inverse_ready() ? 1 : 0, ctx().cus, s->st,
+                                   want ? s->gram_scratch : nullptr, want ? &hx.gram_partials : nullptr, pack ? &pk : nullptr,
                                    riders ? &rd : nullptr);
     if (!rc && rd.pg_part) {
         // the totals of the deferred check are due: they ride in the tail of the pass that follows (prod2), or go out as a launch
@@ -759,11 +493,11 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
         pc.pg_defer_slot = -1;
     }
     if (!rc && (X == s->H || X == s->Wt)) {
-        s->from_nnls[fx] = c0 == 0 && c1 == N;
-        s->nnls_packed[fx] = pack && s->nnls_gram_nblk[side] > 0;
+        hx.from_nnls = c0 == 0 && c1 == N;
+        hx.packed_by_solve = pack && hx.gram_partials > 0;
     }
     // without the side stream (k <= 32) a first launch at k > 32 computes the inverse itself, in stream order
-    if (!rc && c1 > c0 && (s->KP >= 64 || (s->KP == 32 && nnls_inverse_at_32()))) s->inv_done[side] = true;
+    if (!rc && c1 > c0 && (s->KP >= 64 || (s->KP == 32 && nnls_inverse_at_32()))) hs.inverse_formed_by_solve();
     return rc;
 }
 
@@ -771,10 +505,10 @@ static int nnls_side(smk_solver* s, int side, double* X, i64 c0, i64 c1, Partial
 // every pass starts here: is it one of the timed samples?
 static inline void begin_pass(smk_solver* s, int which)
 {
-    if (!s->timing) { s->pass_timed[which] = false; return; }
-    const unsigned c = s->pass_counter[which]++;
-    s->pass_timed[which] = s->timing_stride <= 1 || (c % (unsigned)s->timing_stride) == 0;
-    if (s->pass_timed[which]) ++s->pass_sampled[which];
+    if (!s->timing.on) { s->timing.pass_timed[which] = false; return; }
+    const unsigned c = s->timing.pass_counter[which]++;
+    s->timing.pass_timed[which] = s->timing.stride <= 1 || (c % (unsigned)s->timing.stride) == 0;
+    if (s->timing.pass_timed[which]) ++s->timing.pass_sampled[which];
 }
 
 // one launch of the streaming product, bracketed by events when timing is on; `counts`: this launch completes a pass
@@ -782,43 +516,34 @@ static int timed_bigprod(smk_solver* s, int which, const BigProdPlan& pl_in, con
                          double* P, int counts = 1)
 {
     BigProdPlan pl = pl_in;
-    if (s->inv_ride[which] && bigprod_supports_ride(pl)) {          // start_inverse: this side's Gram inverse rides in the launch
+    Handoff& h = s->hand[which];
+    if (h.take_inverse_ride() && bigprod_supports_ride(pl)) {       // start_inverse: this factor's Gram inverse rides in the launch
         pl.inv_ride.G = which == 0 ? s->Gw : s->Gh;
         pl.inv_ride.k = s->k;
         pl.inv_ride.Ginv = inv_scratch(s, which);
     }
-    s->inv_ride[which] = false;
-    if (s->timing && s->pass_timed[which]) {
-        smk_solver::TimedSpan sp{};
+    const bool timed = s->timing.on && s->timing.pass_timed[which];
+    Timing::TimedSpan sp{};
+    if (timed) {
         if (span_open(s, &sp, counts)) return SMK_DEVICE_ERROR;
-        s->ev[which].push_back(sp);
+        s->timing.ev[which].push_back(sp);
         SMK_HIP(hipEventRecord(sp.e0, s->st));
-        int rc = launch_bigprod(pl, B, ldb, Xp, P, s->st);
-        if (rc == 1) { s->inv_done[which] = true; rc = 0; }        // the launch carried the inverse
-        if (rc) { s->ev[which].pop_back(); s->span_pool.push_back(sp); return rc; }
-        SMK_HIP(hipEventRecord(sp.e1, s->st));
-        return 0;
     }
     int rc = launch_bigprod(pl, B, ldb, Xp, P, s->st);
-    if (rc == 1) { s->inv_done[which] = true; rc = 0; }
+    if (rc == 1) { h.inverse_carried(); rc = 0; }
+    if (timed) {
+        if (rc) { s->timing.ev[which].pop_back(); s->timing.span_pool.push_back(sp); return rc; }
+        SMK_HIP(hipEventRecord(sp.e1, s->st));
+    }
     return rc;
-}
-
-// the routes of a gather product with a factor of ldx doubles per column (timed_spmm takes them, smk_solver_kernel_name names them):
-// the rank-2 product by row blocks, else the entry-balanced segments, else the column-per-lane-group kernel
-static bool blocked2_route(const smk_solver* s, int which, int ldx) { return ldx == 2 && (which == 0 ? s->a->bA : s->a->bAt).nb > 1; }
-static bool seg_route(const smk_solver* s, int which, int ldx, i64 ncols)
-{
-    const SegPlan& seg = (which == 0) ? s->a->segA : s->a->segAt;
-    return ldx == s->KP && s->k > 2 && !is_wide(s->k) && seg.ncols == ncols && seg.rowflag && !seg.uniform;
 }
 
 // R1 = W'A  (k x n, local columns)
 static int timed_spmm(smk_solver* s, int which, const i64* colptr, const unsigned* rowidx, const double* val, i64 ncols,
                       const double* X, int ldx, double* P)
 {
-    smk_solver::TimedSpan sp{};
-    const bool timed = s->timing && s->pass_timed[which];
+    Timing::TimedSpan sp{};
+    const bool timed = s->timing.on && s->timing.pass_timed[which];
     if (timed) {
         if (span_open(s, &sp)) return SMK_DEVICE_ERROR;
         (void)hipEventRecord(sp.e0, s->st);
@@ -826,13 +551,12 @@ static int timed_spmm(smk_solver* s, int which, const i64* colptr, const unsigne
     int rc = 0;
     const BlockedCsc& blk = (which == 0) ? s->a->bA : s->a->bAt;
     const SegPlan& seg = (which == 0) ? s->a->segA : s->a->segAt;
-    InvRide ride;                                                   // start_inverse: this side's Gram inverse rides in the launch
-    if (s->inv_ride[which]) { ride.G = which == 0 ? s->Gw : s->Gh; ride.k = s->k; ride.Ginv = inv_scratch(s, which); }
-    s->inv_ride[which] = false;
+    Handoff& h = s->hand[which];
+    InvRide ride;                                                   // start_inverse: this factor's Gram inverse rides in the launch
+    if (h.take_inverse_ride()) { ride.G = which == 0 ? s->Gw : s->Gh; ride.k = s->k; ride.Ginv = inv_scratch(s, which); }
     GramRide gram;                                                  // gram_factor: this factor's Gram matrix is due
     const bool by_seg = seg_route(s, which, ldx, ncols);
-    if (s->gram_ride[which]) {
-        s->gram_ride[which] = false;
+    if (h.take_gram_ride()) {
         const double* F = which == 0 ? s->Wt : s->H;
         const i64 FN = which == 0 ? s->m : s->n;
         double* G = which == 0 ? s->Gw : s->Gh;
@@ -856,11 +580,11 @@ static int timed_spmm(smk_solver* s, int which, const i64* colptr, const unsigne
         }
         else rc = launch_spmm_gather(colptr, rowidx, val, ncols, s->a->nnz, X, ldx, s->k, P, s->kpp, s->st, &ride);
     }
-    if (rc == 1) { s->inv_done[which] = true; rc = 0; }             // the launch carried the inverse
+    if (rc == 1) { h.inverse_carried(); rc = 0; }
     if (timed) {
-        if (rc) { s->span_pool.push_back(sp); return rc; }
+        if (rc) { s->timing.span_pool.push_back(sp); return rc; }
         (void)hipEventRecord(sp.e1, s->st);
-        s->ev[which].push_back(sp);
+        s->timing.ev[which].push_back(sp);
     }
     return rc;
 }
@@ -877,36 +601,36 @@ static int prod1_sharded(smk_solver* s)
     int rc = 0;
     // one launch per group of 64 factor rows: this rank's blocks into their places in the operand (padding rows as zeros)
     for (int g = 0; g < s->ng && !rc && !f64; ++g)
-        rc = launch_pack_own_blocks(s->Wown, s->KP, s->pg1[g].k0, s->pg1[g].kg, s->n_own, s->blk, s->nchunk, s->world, s->rank, storage,
+        rc = launch_pack_own_blocks(s->ex.Wown, s->KP, s->pg1[g].k0, s->pg1[g].kg, s->ex.n_own, s->ex.blk, s->ex.nchunk, s->ex.world, s->ex.rank, storage,
                                     s->nsplit, (unsigned char*)s->packW + s->pg1[g].pack_offset, s->st, s->xscale[0]);
     if (rc) return rc;
-    rc = comm_fork(s, s->ev_x);
+    rc = comm_fork(s, s->ex.ev_x);
     if (rc) return rc;
-    for (int j = 0; j < s->nchunk; ++j) {
+    for (int j = 0; j < s->ex.nchunk; ++j) {
         i64 r0, r1;
         chunk_rows(s, j, &r0, &r1);
         rc = timed_collective(s, 0, [&] {
             if (f64)        // block r of chunk j from every rank, straight into its rows of the full fp64 W
-                return comm_allgather_to(s->comm, s->Wown + (i64)j * s->blk * s->KP, s->Wt + r0 * s->KP, s->blk * s->KP, 1, s->st2);
+                return comm_allgather_to(s->ex.comm, s->ex.Wown + (i64)j * s->ex.blk * s->KP, s->Wt + r0 * s->KP, s->ex.blk * s->KP, 1, s->ex.st2);
             for (int g = 0; g < s->ng; ++g) {
-                const size_t per = packed_row_offset(storage, s->pg1[g].kg, s->nsplit, s->blk);          // bytes per block
+                const size_t per = packed_row_offset(storage, s->pg1[g].kg, s->nsplit, s->ex.blk);          // bytes per block
                 unsigned char* base = (unsigned char*)s->packW + s->pg1[g].pack_offset + packed_row_offset(storage, s->pg1[g].kg, s->nsplit, r0);
-                const int grc = comm_allgather(s->comm, base, (i64)(per / 4), 0, s->st2);
+                const int grc = comm_allgather(s->ex.comm, base, (i64)(per / 4), 0, s->ex.st2);
                 if (grc) return grc;
             }
             return 0;
         });
         if (rc) return rc;
-        SMK_HIP(hipEventRecord(s->ev_a[j], s->st2));
+        SMK_HIP(hipEventRecord(s->ex.ev_a[j], s->ex.st2));
     }
     bool first = true;
-    for (int j = 0; j < s->nchunk; ++j) {
+    for (int j = 0; j < s->ex.nchunk; ++j) {
         i64 r0, r1;
         chunk_rows(s, j, &r0, &r1);
-        { const int wrc = main_waits_for_comm(s, &s->ev_a[j], 1); if (wrc) return wrc; }
+        { const int wrc = main_waits_for_comm(s, &s->ex.ev_a[j], 1); if (wrc) return wrc; }
         const i64 rows = std::min<i64>(r1, s->m) - r0;
         if (rows <= 0) continue;
-        const bool last = (j == s->nchunk - 1) || (std::min<i64>(r1, s->m) >= s->m);
+        const bool last = (j == s->ex.nchunk - 1) || (std::min<i64>(r1, s->m) >= s->m);
         for (int g = 0; g < s->ng; ++g) {
             BigProdPlan pl = s->pg1[g];
             pl.stages = (rows + pl.mb - 1) / pl.mb;
@@ -919,23 +643,24 @@ static int prod1_sharded(smk_solver* s)
         }
         first = false;
     }
-    if (f64) s->w_full = true;       // every row of the fp64 W is current again (a by-product of the accurate form's gather)
+    if (f64) s->ex.w_full = true;       // every row of the fp64 W is current again (a by-product of the accurate form's gather)
     return 0;
 }
 
 // the product of factor `side` (0 = W, 1 = H) takes the pending reduction of that factor's Gram partials along (gram_factor)
 static inline void take_tail(smk_solver* s, int side, BigProdPlan* pl)
 {
-    if (s->tail_nblk[side] <= 0) return;
+    Handoff& h = s->hand[side];
+    if (h.tail_nblk <= 0) return;
     pl->tail_gp = s->gram_scratch;
-    pl->tail_nblk = s->tail_nblk[side];
+    pl->tail_nblk = h.tail_nblk;
     pl->tail_g = side == 0 ? s->Gw : s->Gh;
-    s->tail_nblk[side] = 0;
+    h.tail_nblk = 0;
 }
 
 static int prod1(smk_solver* s)
 {
-    if (s->w_sharded) return prod1_sharded(s);
+    if (s->ex.w_sharded) return prod1_sharded(s);
     begin_pass(s, 0);
     if (s->a->sparse) {
         if (s->Wc) {        // RANK2: gather from the compact copy of W (16 B per row)
@@ -946,8 +671,8 @@ static int prod1(smk_solver* s)
     }
     int rc = 0;
     const bool f64 = s->nsplit == NSPLIT_F64;                 // the accurate form reads the fp64 factor itself
-    if (!s->packed_fresh[0] && !f64) rc = launch_pack(s->Wt, s->k, s->m, s->a->storage, s->nsplit, s->packW, s->st, s->xscale[0]);
-    s->packed_fresh[0] = false;
+    if (!s->hand[0].packed_fresh && !f64) rc = launch_pack(s->Wt, s->k, s->m, s->a->storage, s->nsplit, s->packW, s->st, s->xscale[0]);
+    s->hand[0].packed_fresh = false;
     if (rc) return rc;
     for (int g = 0; g < s->ng; ++g) {
         const void* Xp = f64 ? (const void*)(s->Wt + s->pg1[g].k0) : (const void*)((const unsigned char*)s->packW + s->pg1[g].pack_offset);
@@ -967,7 +692,7 @@ static int prod2(smk_solver* s)
     begin_pass(s, 1);
     int rc = 0;
     const PartialView pv{s->P2, s->pl2.S, (i64)s->pl2.ncols_pad * s->kpp, s->kpp, 1};
-    if (s->pc.pg_totals_slot >= 0 && (s->a->sparse || s->comm || s->ng != 1 || s->tail_nblk[1] <= 0)) {
+    if (s->pc.pg_totals_slot >= 0 && (s->a->sparse || s->ex.comm || s->ng != 1 || s->hand[1].tail_nblk <= 0)) {
         rc = check_totals(s, nullptr);                  // no tail to ride in
         if (rc) return rc;
     }
@@ -977,23 +702,23 @@ static int prod2(smk_solver* s)
         if (rc) return rc;
         rc = wait_gh(s);
         if (rc || !is_dist(s)) return rc;
-        rc = launch_reduce_partials(pv, s->k, 0, s->pl2.ncols_pad, s->R2red, s->red_f64 ? 1 : 0, s->st);
+        rc = launch_reduce_partials(pv, s->k, 0, s->pl2.ncols_pad, s->R2red, s->ex.red_f64 ? 1 : 0, s->st);
         if (rc) return rc;
-        if (!s->comm) return dist_allreduce_cb(s, s->R2red, (i64)s->pl2.ncols_pad * s->kpp, 0);
-        rc = comm_fork(s, s->ev_c[0]);
+        if (!s->ex.comm) return dist_allreduce_cb(s, s->R2red, (i64)s->pl2.ncols_pad * s->kpp, 0);
+        rc = comm_fork(s, s->ex.ev_c[0]);
         if (rc) return rc;
-        rc = timed_collective(s, 1, [&] { return comm_allreduce(s->comm, s->R2red, (i64)s->pl2.ncols_pad * s->kpp, s->red_f64 ? 1 : 0, s->st2); });
+        rc = timed_collective(s, 1, [&] { return comm_allreduce(s->ex.comm, s->R2red, (i64)s->pl2.ncols_pad * s->kpp, s->ex.red_f64 ? 1 : 0, s->ex.st2); });
         if (rc) return rc;
-        return comm_join(s, s->ev_r[0]);
+        return comm_join(s, s->ex.ev_r[0]);
     }
     const bool f64 = s->nsplit == NSPLIT_F64;
-    if (!s->packed_fresh[1] && !f64) rc = launch_pack(s->H, s->k, s->n, s->a->storage, s->nsplit, s->packH, s->st, s->xscale[1]);
-    s->packed_fresh[1] = false;
+    if (!s->hand[1].packed_fresh && !f64) rc = launch_pack(s->H, s->k, s->n, s->a->storage, s->nsplit, s->packH, s->st, s->xscale[1]);
+    s->hand[1].packed_fresh = false;
     if (rc) return rc;
     auto xh = [&](const BigProdPlan& pl) -> const void* {
         return f64 ? (const void*)(s->H + pl.k0) : (const void*)((const unsigned char*)s->packH + pl.pack_offset);
     };
-    if (!s->comm) {
+    if (!s->ex.comm) {
         for (int g = 0; g < s->ng && !rc; ++g) {
             BigProdPlan pl = s->pg2[g];
             take_tail(s, 1, &pl);
@@ -1013,8 +738,8 @@ static int prod2(smk_solver* s)
         if (rc) return rc;
         return dist_allreduce_cb(s, s->R2red, (i64)s->pl2.ncols_pad * s->kpp, 0);
     }
-    const size_t es = (size_t)elem_size(s->a->storage), rb = s->red_f64 ? sizeof(double) : sizeof(float);
-    for (int j = 0; j < s->nchunk; ++j) {
+    const size_t es = (size_t)elem_size(s->a->storage), rb = s->ex.red_f64 ? sizeof(double) : sizeof(float);
+    for (int j = 0; j < s->ex.nchunk; ++j) {
         i64 r0, r1;
         chunk_rows(s, j, &r0, &r1);
         for (int g = 0; g < s->ng; ++g) {
@@ -1025,24 +750,24 @@ static int prod2(smk_solver* s)
             const unsigned char* Bsrc = pl.tr ? (const unsigned char*)s->a->A + (size_t)r0 * es
                                               : (const unsigned char*)s->a->At + (size_t)r0 * s->a->ldAt * es;
             rc = timed_bigprod(s, 1, pl, Bsrc, pl.tr ? s->a->ldA : s->a->ldAt,
-                               xh(pl), s->P2 + pl.k0 + r0 * pl.pstride, j == s->nchunk - 1 ? 1 : 0);
+                               xh(pl), s->P2 + pl.k0 + r0 * pl.pstride, j == s->ex.nchunk - 1 ? 1 : 0);
             if (rc) return rc;
         }
-        rc = comm_fork(s, s->ev_c[j]);
+        rc = comm_fork(s, s->ex.ev_c[j]);
         if (rc) return rc;
         // off the main stream: the row splits of the chunk summed (and rounded to the wire type), then its exchange
-        if (!s->r2_alias) { rc = launch_reduce_partials(pv, s->k, r0, r1 - r0, s->R2red, s->red_f64 ? 1 : 0, s->st2); if (rc) return rc; }
+        if (!s->ex.r2_alias) { rc = launch_reduce_partials(pv, s->k, r0, r1 - r0, s->R2red, s->ex.red_f64 ? 1 : 0, s->ex.st2); if (rc) return rc; }
         unsigned char* base = (unsigned char*)s->R2red + (size_t)r0 * s->kpp * rb;
         rc = timed_collective(s, 1, [&] {
-            if (s->w_sharded)       // every rank receives the sum of ITS block, next to its other blocks
-                return comm_reduce_scatter_to(s->comm, base, (unsigned char*)s->R2own + (size_t)j * s->blk * s->kpp * rb, s->blk * s->kpp,
-                                              s->red_f64 ? 1 : 0, s->st2);
-            return comm_allreduce(s->comm, base, (r1 - r0) * s->kpp, s->red_f64 ? 1 : 0, s->st2);
+            if (s->ex.w_sharded)       // every rank receives the sum of ITS block, next to its other blocks
+                return comm_reduce_scatter_to(s->ex.comm, base, (unsigned char*)s->ex.R2own + (size_t)j * s->ex.blk * s->kpp * rb, s->ex.blk * s->kpp,
+                                              s->ex.red_f64 ? 1 : 0, s->ex.st2);
+            return comm_allreduce(s->ex.comm, base, (r1 - r0) * s->kpp, s->ex.red_f64 ? 1 : 0, s->ex.st2);
         });
         if (rc) return rc;
-        SMK_HIP(hipEventRecord(s->ev_r[j], s->st2));
+        SMK_HIP(hipEventRecord(s->ex.ev_r[j], s->ex.st2));
     }
-    s->r2_pending = true;
+    s->ex.r2_pending = true;
     return wait_gh(s);
 }
 
@@ -1053,8 +778,9 @@ static int gram_factor(smk_solver* s, int side)
     const double* X = side == 0 ? s->Wt : s->H;
     const i64 N = side == 0 ? s->m : s->n;
     double* G = side == 0 ? s->Gw : s->Gh;
-    s->packed_fresh[side] = false;
-    s->gram_ride[side] = false;
+    Handoff& h = s->hand[side];
+    h.packed_fresh = false;
+    h.gram_ride = false;
     {
         // Sparse A: the gather product that follows in every schedule reads the same factor, and its two launches (segments, long-column
         // fix-up) carry the Gram matrix along -- partial sums as extra workgroups of the first, their reduction as extra workgroups of
@@ -1063,15 +789,15 @@ static int gram_factor(smk_solver* s, int side)
         // A product that takes another route forms the matrix first, as before (timed_spmm).  SMK_GRAM_RIDE=0: never rides.
         const bool ride = sw::gram_ride();
         const bool inverse_next = s->o.algorithm == SMK_ALG_BPP && (s->KP == 64 || (s->KP == 32 && nnls_inverse_at_32()));
-        if (ride && s->a->sparse && !is_dist(s) && !s->comm && !s->w_sharded && (s->KP == 16 || s->KP == 32) && s->k > 2 && !inverse_next &&
+        if (ride && s->a->sparse && !is_dist(s) && !s->ex.comm && !s->ex.w_sharded && (s->KP == 16 || s->KP == 32) && s->k > 2 && !inverse_next &&
             s->o.algorithm != SMK_ALG_RANK2) {
-            s->gram_ride[side] = true;
+            h.gram_ride = true;
             return 0;
         }
     }
-    if (side == 0 && s->w_sharded) {
+    if (side == 0 && s->ex.w_sharded) {
         // W'W from this rank's own rows, summed over the ranks; the fp16 row scales follow the finished matrix
-        int rc = s->n_own > 0 ? launch_gram(s->Wown, s->k, s->n_own, G, s->gram_scratch, GRAM_BLOCKS, s->st)
+        int rc = s->ex.n_own > 0 ? launch_gram(s->ex.Wown, s->k, s->ex.n_own, G, s->gram_scratch, GRAM_BLOCKS, s->st)
                               : launch_zero_f64(G, (i64)s->KP * s->KP, s->st);
         if (rc) return rc;
         rc = dist_allreduce_now(s, G, (i64)s->KP * s->KP, 1);
@@ -1080,15 +806,14 @@ static int gram_factor(smk_solver* s, int side)
         return 0;
     }
     if (s->nsplit == NSPLIT_F16X2) {     // the reduce launch also derives the row scales of the operand packed next
-        const int ns = side == 0 ? 1 : 0;            // the NNLS launch that solved THIS factor (side 1 solves W, side 0 solves H)
-        if (s->nnls_gram_nblk[ns] > 0) {
-            const int nb = s->nnls_gram_nblk[ns];
-            s->nnls_gram_nblk[ns] = 0;
+        if (h.gram_partials > 0) {                   // the NNLS launch that solved THIS factor left them
+            const int nb = h.gram_partials;
+            h.gram_partials = 0;
             // the solve packed the operand itself: nothing is needed before the product, which takes the reduction along
-            if (s->nnls_packed[side]) {
-                s->nnls_packed[side] = false;
-                s->packed_fresh[side] = true;
-                s->tail_nblk[side] = nb;
+            if (h.packed_by_solve) {
+                h.packed_by_solve = false;
+                h.packed_fresh = true;
+                h.tail_nblk = nb;
                 return 0;
             }
             // ... and packs it in the same launch (the packing workgroups add up the 16 diagonal entries themselves)
@@ -1096,7 +821,7 @@ static int gram_factor(smk_solver* s, int side)
             if (fuse_pack && !s->a->sparse) {
                 const int rc = launch_reduce_pack_f16x2(s->gram_scratch, nb, s->k, G, s->xscale[side], s->oscale[side], (double)s->a->ascale, X, N,
                                                         s->a->storage, side == 0 ? s->packW : s->packH, s->st);
-                if (rc == 0) { s->packed_fresh[side] = true; return 0; }
+                if (rc == 0) { h.packed_fresh = true; return 0; }
                 if (rc != 1) return rc;
             }
             return launch_gram_reduce(s->gram_scratch, nb, s->k, G, s->st, s->xscale[side], s->oscale[side], (double)s->a->ascale);
@@ -1109,7 +834,7 @@ static int gram_factor(smk_solver* s, int side)
     if (!s->a->sparse && s->o.algorithm != SMK_ALG_RANK2 && s->nsplit != NSPLIT_F64) {
         const int rc = launch_gram_pack(X, s->k, N, G, s->gram_scratch, GRAM_BLOCKS, s->a->storage, s->nsplit,
                                         side == 0 ? s->packW : s->packH, s->st);
-        if (rc == 0) { s->packed_fresh[side] = true; return 0; }
+        if (rc == 0) { h.packed_fresh = true; return 0; }
         if (rc != 1) return rc;
     }
     return launch_gram(X, s->k, N, G, s->gram_scratch, GRAM_BLOCKS, s->st);
@@ -1130,30 +855,28 @@ static int gram_h(smk_solver* s)
     if (rc) return rc;
     // sharded: HH' is final only after its all-reduce -- in stream order with the callback hook, on the second stream
     // (event ev_gh) with a native communicator; either way the inversion runs beside the H*At pass
-    return start_inverse(s, 1, s->Gh, (is_dist(s) && s->gh_pending) ? s->ev_gh : nullptr);
+    return start_inverse(s, 1, s->Gh, (is_dist(s) && s->ex.gh_pending) ? s->ex.ev_gh : nullptr);
 }
 
 // row-sharded W: bring every row of the fp64 W to every rank (results, DELTA_FNORM); one in-place all-gather per chunk
 extern "C++" int smk::gather_w(smk_solver* s)
 {
-    if (!s->w_sharded || s->w_full) return 0;
-    int rc = comm_fork(s, s->ev_x);
+    if (!s->ex.w_sharded || s->ex.w_full) return 0;
+    int rc = comm_fork(s, s->ex.ev_x);
     if (rc) return rc;
-    for (int j = 0; j < s->nchunk && !rc; ++j)
-        rc = comm_allgather_to(s->comm, s->Wown + (i64)j * s->blk * s->KP, s->Wt + (i64)j * s->world * s->blk * s->KP, s->blk * s->KP, 1, s->st2);
+    for (int j = 0; j < s->ex.nchunk && !rc; ++j)
+        rc = comm_allgather_to(s->ex.comm, s->ex.Wown + (i64)j * s->ex.blk * s->KP, s->Wt + (i64)j * s->ex.world * s->ex.blk * s->KP, s->ex.blk * s->KP, 1, s->ex.st2);
     if (rc) return rc;
-    s->w_full = true;
-    return comm_join(s, s->ev_y);
+    s->ex.w_full = true;
+    return comm_join(s, s->ex.ev_y);
 }
 
 // solver.Init (mu :98-114, hals :142-159, bpp :310-335) + progress_est->Init
-static int solver_init(smk_solver* s)
+extern "C++" int smk::solver_init(smk_solver* s)
 {
     int rc = 0;
     // the factors are the caller's (or a restored snapshot): nothing is known to come from an NNLS launch, nothing is pending
-    s->from_nnls[0] = s->from_nnls[1] = false;
-    s->nnls_packed[0] = s->nnls_packed[1] = false;
-    s->tail_nblk[0] = s->tail_nblk[1] = 0;
+    s->forget_handoffs();
     s->pc.reset();
     if (s->o.algorithm == SMK_ALG_HALS) {
         rc = gram_h(s);  if (rc) return rc;
@@ -1183,9 +906,9 @@ static int solver_iteration(smk_solver* s)
             rc = gram_h(s);   if (rc) return rc;
             rc = prod2(s);    if (rc) return rc;
             rc = wait_r2(s);  if (rc) return rc;
-            if (s->w_sharded) {       // own blocks only (back to back in Wown, their rows of the summed (AH')' in R2own)
-                if (s->n_own > 0) { rc = launch_mu_update(s->Wown, s->k, s->n_own, view_own(s), s->Gh, s->st, s->wide_tmp); if (rc) return rc; }
-                s->w_full = false;
+            if (s->ex.w_sharded) {       // own blocks only (back to back in Wown, their rows of the summed (AH')' in R2own)
+                if (s->ex.n_own > 0) { rc = launch_mu_update(s->ex.Wown, s->k, s->ex.n_own, view_own(s), s->Gh, s->st, s->wide_tmp); if (rc) return rc; }
+                s->ex.w_full = false;
             } else {
                 rc = launch_mu_update(s->Wt, s->k, s->m, r2, s->Gh, s->st, s->wide_tmp); if (rc) return rc;
             }
@@ -1198,7 +921,7 @@ static int solver_iteration(smk_solver* s)
             // reductions stay.  SMK_HALS_EPILOGUE=0: the launches of before.
             const bool ep_on = sw::hals_epilogue();
             const bool bf16_frag = s->a->storage == SMK_STORE_BF16 || s->nsplit >= 2;
-            const bool ep_ok = ep_on && !s->a->sparse && !is_dist(s) && !s->comm && (s->KP == 16 || s->KP == 32) && bf16_frag && s->nsplit >= 1 && s->nsplit <= 3 &&
+            const bool ep_ok = ep_on && !s->a->sparse && !is_dist(s) && !s->ex.comm && (s->KP == 16 || s->KP == 32) && bf16_frag && s->nsplit >= 1 && s->nsplit <= 3 &&
                                s->ng == 1 && s->hals_ep_blocks > 0;
             HalsEpilogue epw, eph;
             if (ep_ok) {
@@ -1210,12 +933,12 @@ static int solver_iteration(smk_solver* s)
             rc = wait_r2(s);  if (rc) return rc;
             rc = launch_hals_w_update(s->Wt, s->k, s->m, r2, s->Gh, s->hals_scratch, ctx().cus, s->fail_flag, s->hals_calls++, s->hals_multi ? 1 : 0, s->st,
                                       ep_ok ? &epw : nullptr); if (rc) return rc;
-            if (epw.done) { rc = launch_gram_reduce(s->gram_scratch, epw.nblk, s->k, s->Gw, s->st, nullptr, nullptr, 1.0); s->packed_fresh[0] = true; }
+            if (epw.done) { rc = launch_gram_reduce(s->gram_scratch, epw.nblk, s->k, s->Gw, s->st, nullptr, nullptr, 1.0); s->hand[0].packed_fresh = true; }
             else rc = gram_w(s);
             if (rc) return rc;
             rc = prod1(s);    if (rc) return rc;
             rc = launch_hals_sweep(s->H, s->k, s->n, r1, s->Gw, s->st, ep_ok ? &eph : nullptr); if (rc) return rc;
-            if (eph.done) { rc = launch_gram_reduce(s->gram_scratch, eph.nblk, s->k, s->Gh, s->st, nullptr, nullptr, 1.0); s->packed_fresh[1] = true; }
+            if (eph.done) { rc = launch_gram_reduce(s->gram_scratch, eph.nblk, s->k, s->Gh, s->st, nullptr, nullptr, 1.0); s->hand[1].packed_fresh = true; }
             else rc = gram_h(s);
             if (rc) return rc;
             rc = prod2(s);    if (rc) return rc;
@@ -1225,17 +948,17 @@ static int solver_iteration(smk_solver* s)
             rc = nnls_side(s, 0, s->H, 0, s->n, r1, s->Gw); if (rc) return rc;
             rc = gram_h(s);   if (rc) return rc;
             rc = prod2(s);    if (rc) return rc;
-            if (s->w_sharded) {
+            if (s->ex.w_sharded) {
                 // W is replicated in the algorithm but its rows are independent NNLS problems: every rank solves its own
                 // blocks (held back to back, one launch) once the last slice of the reduce-scatter has landed
                 rc = wait_r2(s);  if (rc) return rc;
-                rc = nnls_side(s, 1, s->Wown, 0, s->n_own, view_own(s), s->Gh); if (rc) return rc;
-                s->w_full = false;
-            } else if (s->ar && s->world > 1) {
+                rc = nnls_side(s, 1, s->ex.Wown, 0, s->ex.n_own, view_own(s), s->Gh); if (rc) return rc;
+                s->ex.w_full = false;
+            } else if (s->ex.ar && s->ex.world > 1) {
                 // callback hook (one primitive only): every rank solves a row range, zeroes the rest and sum-all-reduces
-                const i64 base = s->m / s->world, extra = s->m % s->world;
-                const i64 i0 = s->rank * base + (s->rank < extra ? s->rank : extra);
-                const i64 i1 = i0 + base + (s->rank < extra ? 1 : 0);
+                const i64 base = s->m / s->ex.world, extra = s->m % s->ex.world;
+                const i64 i0 = s->ex.rank * base + (s->ex.rank < extra ? s->ex.rank : extra);
+                const i64 i1 = i0 + base + (s->ex.rank < extra ? 1 : 0);
                 rc = nnls_side(s, 1, s->Wt, i0, i1, r2, s->Gh); if (rc) return rc;
                 if (i0 > 0) SMK_HIP(hipMemsetAsync(s->Wt, 0, (size_t)i0 * s->KP * sizeof(double), s->st));
                 if (i1 < s->m) SMK_HIP(hipMemsetAsync(s->Wt + i1 * s->KP, 0, (size_t)(s->m - i1) * s->KP * sizeof(double), s->st));
@@ -1273,21 +996,6 @@ static int solver_iteration(smk_solver* s)
     return 0;
 }
 
-static int resolve_events(smk_solver* s)
-{
-    for (int w = 0; w < 6; ++w) {
-        for (auto& e : s->ev[w]) {
-            float ms = 0.f;
-            SMK_HIP(hipEventElapsedTime(&ms, e.e0, e.e1));
-            s->acc_ms[w] += (double)ms;                                // sampled totals; smk_solver_kernel_time scales them by passes seen / passes sampled
-            s->launches[w] += e.counts;
-        }
-        s->span_pool.insert(s->span_pool.end(), s->ev[w].begin(), s->ev[w].end());      // read: span_open hands them out again
-        s->ev[w].clear();
-    }
-    return 0;
-}
-
 // wait for the stream; translate device-side failure flags into Result codes
 extern "C++" int smk::sync_and_check(smk_solver* s, int* fail_iter)
 {
@@ -1315,7 +1023,7 @@ extern "C++" int smk::dist_agree(smk_solver* s)
     return launch_dist_scalars(s->scal, s->fail_flag, s->iter > 0 ? s->iter - 1 : 0, 1, wpart, s->st);
 }
 
-static int normalize_device(smk_solver* s)
+extern "C++" int smk::normalize_device(smk_solver* s)
 {
     if (s->normalized) return 0;
     { const int grc = gather_w(s); if (grc) return grc; }
@@ -1324,7 +1032,7 @@ static int normalize_device(smk_solver* s)
     if (rc) return rc;
     rc = launch_scale_rows(s->Wt, s->k, s->m, s->Gw, 1, s->fail_flag, s->st);
     if (rc) return rc;
-    if (s->w_sharded) { rc = scatter_own(s); if (rc) return rc; }      // the own rows follow the scaled full copy
+    if (s->ex.w_sharded) { rc = scatter_own(s); if (rc) return rc; }      // the own rows follow the scaled full copy
     s->wc_valid = false;
     s->normalized = true;
     // Gw/Gh and the stored products describe the un-normalised factors: a later iterate()/run() on this
@@ -1373,155 +1081,6 @@ static int pack_fail_soft(smk_solver* s)
     fprintf(stderr, "smallk_amd: an NNLS launch could not pack its result inside fp16's range; repeating the run with the separate pack launch\n");
     s->pack_in_solve_off = true;
     return restart_from_initial_factors(s);
-}
-
-// ---- run-time guard of the product form ------------------------------------------------------------------------------
-// Which product form a run takes is decided when the solver is created (rank, algorithm, the spread of the column scales:
-// thresholds found by sweeps).  A matrix outside the swept families must not leave the 1e-4 bar silently, so the choice is
-// can be re-examined while the run goes on (OPT-IN: SMK_GUARD_EVERY=16; default 0 = off, see the note at the end).  Every
-// SMK_GUARD_EVERY iterations of a BPP run the solver forms W'A for a sample
-// of 64 columns in the ACCURATE form (fp64 factor against the stored data, bigprod_f64_kernel) and compares it with what the
-// fast form has just produced for the same columns: delta = ||P_fast - P_acc||_F / ||P_acc||_F, the product error ON THIS
-// DATA (4e-8 for well-scaled data; much more when small entries sit next to large ones).  To first order an error delta in
-// the right-hand sides moves the solution of the k x k normal equations by at most cond(G) delta, G = W'W or HH', and the
-// condition numbers are cheap: both Gram matrices come back with the two sums (k <= 256: Cholesky + inverse on the host,
-// 1-norm).  When max(cond) * delta exceeds SMK_GUARD_TAU (default 1e-4: ONE iteration could move the factors by the parity
-// bar) the solver changes to the accurate form for the rest of the run: plans and buffers are rebuilt and solver.Init is
-// repeated on the current factors, exactly what a fresh solver given them would do.  The check is asynchronous -- enqueued
-// behind one iteration, read GUARD_EVERY iterations later -- so it never stalls the stream (C4: one 67 MB pass per 16
-// iterations of 137 GB each; measured -1.1 % on C4, -8 % on the 0.09 ms iterations of C2 where the host runs at most 16
-// iterations ahead).  Not for sharded runs (every rank would have to agree; their form is agreed once, at attach).
-// WHY IT IS NOT ON BY DEFAULT (round 4, profiles/r04_guard_cases.txt): cond(G) delta is a worst-case bound, and the
-// non-negativity constraints take the ill-conditioned directions out of the problems that are actually solved.  HALS on
-// uniform noise at k = 8 shows cond(HH') = 2.3e4, delta = 1.2e-8, product 2.6e-4 > tau, while the run ends 1.7e-6 from the
-// oracle after 40 iterations; with the guard on, C3 (HALS, k = 32) changes to the accurate form and runs at 253 instead of
-// 1160 iterations/s.  For block pivoting -- where the bound describes the solves that are really done -- the cases measured
-// separate cleanly (noise: 2e-6 .. 7e-6 over 40 iterations; a planted factor with nearly collinear columns: > 1e-2), so the
-// guard is offered for BPP runs on data outside the swept families, and the static rules of smk_solver_create stay the default.
-static bool guard_applies(const smk_solver* s)
-{
-    const int every = sw::guard_every();
-    if (every <= 0 || s->guard_off || s->a->sparse || s->nsplit == NSPLIT_F64 || is_dist(s) || s->comm) return false;
-    if (s->o.algorithm != SMK_ALG_BPP) return false;
-    return s->k <= 256 && s->n >= 64 && s->iter > 0 && s->iter % every == 0;
-}
-
-// 1-norm condition number of the live k x k block of a KP x KP symmetric matrix (inf when it is not positive definite)
-static double cond1_spd(const double* G, int KP, int k)
-{
-    std::vector<double> L((size_t)k * k, 0.0), X((size_t)k * k, 0.0);
-    double n1 = 0.0;
-    for (int c = 0; c < k; ++c) { double sum = 0.0; for (int r = 0; r < k; ++r) sum += std::fabs(G[(size_t)c * KP + r]); n1 = std::max(n1, sum); }
-    for (int j = 0; j < k; ++j) {                                  // G = L L'
-        double d = G[(size_t)j * KP + j];
-        for (int p = 0; p < j; ++p) d -= L[(size_t)j * k + p] * L[(size_t)j * k + p];
-        if (!(d > 0.0)) return INFINITY;
-        const double ljj = std::sqrt(d);
-        L[(size_t)j * k + j] = ljj;
-        for (int i = j + 1; i < k; ++i) {
-            double v = G[(size_t)j * KP + i];
-            for (int p = 0; p < j; ++p) v -= L[(size_t)i * k + p] * L[(size_t)j * k + p];
-            L[(size_t)i * k + j] = v / ljj;
-        }
-    }
-    double ninv = 0.0;
-    std::vector<double> y((size_t)k);
-    for (int c = 0; c < k; ++c) {                                  // column c of the inverse: L y = e_c, L' x = y
-        for (int i = 0; i < k; ++i) {
-            double v = i == c ? 1.0 : 0.0;
-            for (int p = 0; p < i; ++p) v -= L[(size_t)i * k + p] * y[(size_t)p];
-            y[(size_t)i] = v / L[(size_t)i * k + i];
-        }
-        double sum = 0.0;
-        for (int i = k - 1; i >= 0; --i) {
-            double v = y[(size_t)i];
-            for (int p = i + 1; p < k; ++p) v -= L[(size_t)p * k + i] * X[(size_t)p];
-            X[(size_t)i] = v / L[(size_t)i * k + i];
-            sum += std::fabs(X[(size_t)i]);
-        }
-        ninv = std::max(ninv, sum);
-    }
-    return n1 * ninv;
-}
-
-static int guard_resolve(smk_solver* s)
-{
-    if (!s->guard_pending) return 0;
-    s->guard_pending = false;
-    SMK_HIP(hipEventSynchronize(s->guard_ev));
-    const double tau = sw::guard_tau();
-    const double* p = s->guard_pin;
-    const double delta = p[1] > 0.0 ? std::sqrt(p[0] / p[1]) : 0.0;
-    const size_t kk = (size_t)s->KP * s->KP;
-    const double cond = std::max(cond1_spd(p + 2, s->KP, s->k), cond1_spd(p + 2 + kk, s->KP, s->k));
-    s->guard_checks += 1;
-    s->guard_last = cond * delta;
-    if (sw::guard_verbose()) fprintf(stderr, "[smk guard] iteration %d: delta %.3e, cond %.3e, product %.3e (tau %.1e)\n", s->iter, delta, cond, cond * delta, tau);
-    if (!(cond * delta > tau)) return 0;
-    // change to the accurate form: new plans and buffers, then solver.Init on the current factors
-    s->guard_fired += 1;
-    s->nsplit = NSPLIT_F64;
-    int rc = plan_products(s);
-    if (!rc && alloc_product_buffers(s)) rc = SMK_DEVICE_ERROR;
-    if (rc) return rc;
-    s->packed_fresh[0] = s->packed_fresh[1] = false;
-    s->nnls_gram_nblk[0] = s->nnls_gram_nblk[1] = 0;
-    const int iter_keep = s->iter;
-    rc = solver_init(s);
-    s->iter = iter_keep;
-    return rc;
-}
-
-static int guard_enqueue(smk_solver* s)
-{
-    const size_t kk = (size_t)s->KP * s->KP;
-    if (!s->guard_As) {                    // first use: the sample (64 columns, evenly spaced), plans, buffers
-        const int nc = 64;
-        std::vector<unsigned> cols((size_t)nc);
-        for (int i = 0; i < nc; ++i) cols[(size_t)i] = (unsigned)((i64)i * s->n / nc);
-        const i64 es = elem_size(s->a->storage);
-        int rc = s->own.dev(&s->guard_cols, (size_t)nc);
-        rc |= s->own.dev((unsigned char**)&s->guard_As, (size_t)s->a->ldA * COL_PAD * es);
-        rc |= s->own.dev(&s->guard_dev, 2 + 2 * kk);
-        if (rc) return SMK_DEVICE_ERROR;
-        SMK_HIP(hipMemsetAsync(s->guard_As, 0, (size_t)s->a->ldA * COL_PAD * es, s->st));
-        SMK_HIP(hipMemcpyAsync(s->guard_cols, cols.data(), (size_t)nc * sizeof(unsigned), hipMemcpyHostToDevice, s->st));
-        rc = launch_gather_cols(s->a->A, s->a->ldA * es, s->guard_cols, nc, s->guard_As, s->a->ldA * es, s->a->ldA * es, s->st);
-        if (rc) return rc;
-        SMK_HIP(hipStreamSynchronize(s->st));              // `cols` leaves scope
-        const int ng = plan_bigprod_groups(s->a->storage, s->k, s->m, nc, NSPLIT_F64, ctx().cus, s->guard_pl);
-        for (int g = 0; g < ng; ++g) s->guard_pl[g].ldx = s->KP;
-        if (s->own.dev(&s->guard_P, s->guard_pl[0].p_elems) || s->own.pinned((void**)&s->guard_pin, (2 + 2 * kk) * sizeof(double)) ||
-            s->own.event(&s->guard_ev, hipEventDisableTiming))
-            return SMK_DEVICE_ERROR;
-        s->guard_ncols = nc;
-    }
-    // the full fp64 W (s->Wt) against the sampled columns, one launch per group of 64 factor rows
-    for (int g = 0; g < s->ng; ++g) {
-        const int rc = launch_bigprod(s->guard_pl[g], s->guard_As, s->a->ldA, s->Wt + s->guard_pl[g].k0, s->guard_P + s->guard_pl[g].k0, s->st);
-        if (rc) return rc;
-    }
-    const BigProdPlan& gp = s->guard_pl[0];
-    int rc = launch_guard_compare(view1(s), s->guard_cols, s->guard_ncols, s->guard_P, gp.S, (i64)gp.ncols_pad * gp.pstride, gp.pstride, s->k,
-                                  s->guard_dev, s->st);
-    if (rc) return rc;
-    SMK_HIP(hipMemcpyAsync(s->guard_dev + 2, s->Gw, kk * sizeof(double), hipMemcpyDeviceToDevice, s->st));
-    SMK_HIP(hipMemcpyAsync(s->guard_dev + 2 + kk, s->Gh, kk * sizeof(double), hipMemcpyDeviceToDevice, s->st));
-    SMK_HIP(hipMemcpyAsync(s->guard_pin, s->guard_dev, (2 + 2 * kk) * sizeof(double), hipMemcpyDeviceToHost, s->st));
-    SMK_HIP(hipEventRecord(s->guard_ev, s->st));
-    s->guard_pending = true;
-    return 0;
-}
-
-// after every iteration: read the check enqueued GUARD_EVERY iterations ago, enqueue the next one
-static int guard_step(smk_solver* s)
-{
-    if (!guard_applies(s)) return 0;
-    int rc = guard_resolve(s);
-    if (rc || s->nsplit == NSPLIT_F64) return rc;
-    rc = wait_r2(s);                      // HH' / the stored products are final
-    if (rc) return rc;
-    return guard_enqueue(s);
 }
 
 int smk_solver_iterate(smk_solver* s, int iters)
@@ -1581,9 +1140,9 @@ int smk_solver_iterate_checked(smk_solver* s, int iters, double* last_metric)
 int smk_solver_product_form(const smk_solver* s, int* guard_checks, int* guard_fired, double* guard_last)
 {
     if (!s) return SMK_BAD_PARAM;
-    if (guard_checks) *guard_checks = s->guard_checks;
-    if (guard_fired) *guard_fired = s->guard_fired;
-    if (guard_last) *guard_last = s->guard_last;
+    if (guard_checks) *guard_checks = s->guard.checks;
+    if (guard_fired) *guard_fired = s->guard.fired;
+    if (guard_last) *guard_last = s->guard.last;
     return s->nsplit;
 }
 
@@ -1648,10 +1207,10 @@ static bool rank2_persist_eligible(const smk_solver* s)
 {
     const int mode = sw::r2_persist();
     const i64 max_nnz = sw::r2_persist_nnz();
-    if (!mode || s->r2p_off) return false;
+    if (!mode || s->r2p.off) return false;
     if (g_r2p_off_devices.load(std::memory_order_relaxed) & (1ull << (smk_current_device() & 63))) return false;
     if (s->o.algorithm != SMK_ALG_RANK2 || !s->a->sparse || s->o.prog_est_algorithm != SMK_PROG_PG_RATIO) return false;
-    if (is_dist(s) || s->comm || s->o.verbose || s->timing || !s->Hc || !s->Wc) return false;
+    if (is_dist(s) || s->ex.comm || s->o.verbose || s->timing.on || !s->Hc || !s->Wc) return false;
     if (rank2_persist_workgroups(s->m, s->n, s->a->nnz, ctx().cus) < 1) return false;      // more than 4096 rows per workgroup
     return s->a->nnz <= max_nnz || mode == 2;
 }
@@ -1665,13 +1224,13 @@ static int rank2_persist_run(smk_solver* s, int* status, int* count)
     // TEST HOOK: behave as if the kernel's workgroups had not all become resident (the caller must then finish the run on the
     // launch-per-kernel loop from the state solver.Init left)
     if (sw::r2p_test_abort()) { *status = R2P_ABORTED; return 0; }
-    if (!s->r2p_sync) {
-        int rc = s->own.dev(&s->r2p_hc1, (size_t)2 * s->n);
-        rc |= s->own.dev(&s->r2p_r2c, (size_t)2 * s->m);
-        rc |= s->own.dev(&s->r2p_part, (size_t)3 * 8 * 1024);                  // three arrays of [workgroups <= 1024][8]
-        rc |= s->own.dev(&s->r2p_out, (size_t)16);
-        rc |= s->own.pinned((void**)&s->r2p_pin, 16 * sizeof(double));
-        rc |= s->own.dev((unsigned char**)&s->r2p_sync, rank2_persist_sync_bytes());           // last: its presence says the set is complete
+    if (!s->r2p.sync) {
+        int rc = s->own.dev(&s->r2p.hc1, (size_t)2 * s->n);
+        rc |= s->own.dev(&s->r2p.r2c, (size_t)2 * s->m);
+        rc |= s->own.dev(&s->r2p.part, (size_t)3 * 8 * 1024);                  // three arrays of [workgroups <= 1024][8]
+        rc |= s->own.dev(&s->r2p.out, (size_t)16);
+        rc |= s->own.pinned((void**)&s->r2p.pin, 16 * sizeof(double));
+        rc |= s->own.dev((unsigned char**)&s->r2p.sync, rank2_persist_sync_bytes());           // last: its presence says the set is complete
         if (rc) return SMK_DEVICE_ERROR;
     }
     R2PersistArgs a;
@@ -1679,34 +1238,34 @@ static int rank2_persist_run(smk_solver* s, int* status, int* count)
     a.colptr_t = s->a->colptr_t; a.rowidx_t = s->a->rowidx_t; a.val_t = s->a->val_t;
     a.m = s->m; a.n = s->n;
     a.Gw0 = s->Gw; a.R1 = view1(s);
-    a.Wc = s->Wc; a.Hc0 = s->Hc; a.Hc1 = s->r2p_hc1; a.R2c = s->r2p_r2c;
-    a.gp_h = s->r2p_part; a.gp_w = s->r2p_part + 8 * 1024; a.pgp = s->r2p_part + 2 * 8 * 1024;
-    a.sync = s->r2p_sync;
+    a.Wc = s->Wc; a.Hc0 = s->Hc; a.Hc1 = s->r2p.hc1; a.R2c = s->r2p.r2c;
+    a.gp_h = s->r2p.part; a.gp_w = s->r2p.part + 8 * 1024; a.pgp = s->r2p.part + 2 * 8 * 1024;
+    a.sync = s->r2p.sync;
     a.min_iter = s->o.min_iter; a.max_iter = s->o.max_iter; a.tolcount = s->o.tolcount; a.tol = s->o.tol;
     a.iter_tag0 = s->iter;
     a.Wt = s->Wt; a.H = s->H; a.Gw = s->Gw;
     a.fail_flag = s->fail_flag;
     a.lds_bytes = (unsigned)rank2_persist_lds_bytes();
-    a.out = s->r2p_out;
+    a.out = s->r2p.out;
     int rc = launch_rank2_persist(a, nwg, s->st);
     if (rc == 1) { *status = R2P_ABORTED; return 0; }       // the grid does not fit the device as it is now
     if (rc) return rc;
-    SMK_HIP(hipMemcpyAsync(s->r2p_pin, s->r2p_out, 16 * sizeof(double), hipMemcpyDeviceToHost, s->st));
+    SMK_HIP(hipMemcpyAsync(s->r2p.pin, s->r2p.out, 16 * sizeof(double), hipMemcpyDeviceToHost, s->st));
     SMK_HIP(hipStreamSynchronize(s->st));
-    *status = (int)s->r2p_pin[0];
-    *count = (int)s->r2p_pin[1];
+    *status = (int)s->r2p.pin[0];
+    *count = (int)s->r2p.pin[1];
     {
         if (sw::r2p_profile()) {
-            const double it = std::max(1.0, s->r2p_pin[2]);
+            const double it = std::max(1.0, s->r2p.pin[2]);
             fprintf(stderr, "[r2p] %ld x %ld nnz %ld: %d workgroups, status %d, %.0f iterations; per iteration (workgroup 0): "
                     "B1 %.1f us, phase W %.1f, B2 %.1f, phase G %.1f\n", (long)s->m, (long)s->n, (long)s->a->nnz, nwg, *status, it,
-                    s->r2p_pin[8] / it, s->r2p_pin[9] / it, s->r2p_pin[10] / it, s->r2p_pin[11] / it);
+                    s->r2p.pin[8] / it, s->r2p.pin[9] / it, s->r2p.pin[10] / it, s->r2p.pin[11] / it);
         }
     }
     if (*status == R2P_CONVERGED || *status == R2P_EXHAUSTED) {
-        s->iter += (int)s->r2p_pin[2];
-        s->pc.pg0 = s->r2p_pin[3];
-        s->pc.last_metric = s->r2p_pin[4];
+        s->iter += (int)s->r2p.pin[2];
+        s->pc.pg0 = s->r2p.pin[3];
+        s->pc.last_metric = s->r2p.pin[4];
         s->pc.sums_state = 2;          // the launch returns no sums (smk_solver_progress_sums: SMK_UNSUPPORTED)
         s->normalized = false;
         s->inited = false;             // HH' and the stored products were never materialised: a later run starts from solver.Init
@@ -1752,7 +1311,7 @@ static int solver_run_once(smk_solver* s, smk_stats* stats)
         if (status == R2P_SOLVER_FAILED) { result = SMK_FAILURE; goto failed_check; }
         // ABORTED: some workgroup never became resident (or the deadline passed); the solver state is the one solver.Init
         // left, so the launch-per-kernel loop below takes over, latched for the life of the handle
-        s->r2p_off = true;
+        s->r2p.off = true;
         s->wc_valid = false;           // the compact copy of W served as the kernel's work array
         const unsigned long long bit = 1ull << (smk_current_device() & 63);
         if (!(g_r2p_off_devices.fetch_or(bit, std::memory_order_relaxed) & bit))       // once per device and process
@@ -1873,7 +1432,7 @@ int smk_solver_project_h(smk_solver* s)
     if (!s) { set_error("smk_solver_project_h: null solver"); return SMK_BAD_PARAM; }
     if (!s->have_factors) { set_error("smk_solver_project_h: set_factors() first"); return SMK_BAD_PARAM; }
     if (s->o.algorithm != SMK_ALG_BPP) { set_error("smk_solver_project_h: a BPP solver"); return SMK_BAD_PARAM; }
-    if (is_dist(s) || s->w_sharded) { set_error("smk_solver_project_h: not available on a sharded solver"); return SMK_UNSUPPORTED; }
+    if (is_dist(s) || s->ex.w_sharded) { set_error("smk_solver_project_h: not available on a sharded solver"); return SMK_UNSUPPORTED; }
     int rc = 0;
     // one pass: the accurate product form (the fp64 product of the stored data) costs one slower pass, and H then differs from the
     // reference's by summation order only (as smk_solver_nnls_hals)
@@ -1884,228 +1443,16 @@ int smk_solver_project_h(smk_solver* s)
         if (rc) return rc;
     }
     // as solver.Init: the factors are the caller's, nothing is known to come from an NNLS launch, nothing is pending
-    s->from_nnls[0] = s->from_nnls[1] = false;
-    s->nnls_packed[0] = s->nnls_packed[1] = false;
-    s->tail_nblk[0] = s->tail_nblk[1] = 0;
+    s->forget_handoffs();
     s->pc.reset();
     s->normalized = false;          // H is about to change
     rc = gram_w(s);
     if (!rc) rc = prod1(s);
     if (!rc) rc = nnls_side(s, 0, s->H, 0, s->n, view1(s), s->Gw);
     s->inited = false;              // Gw / R1 no longer describe a solver schedule
-    s->from_nnls[0] = s->from_nnls[1] = false;
-    s->nnls_packed[0] = s->nnls_packed[1] = false;      // (by-products of the solve for a schedule that does not follow)
-    s->nnls_gram_nblk[0] = s->nnls_gram_nblk[1] = 0;
+    s->forget_handoffs();           // (what the solve left is for a schedule that does not follow)
     if (rc) return rc;
     return sync_and_check(s, nullptr);
-}
-
-// NnlsBlockpivot(LHS, RHS, X, Y), common/include/nnls.hpp:144-244, on its own: min ||.|| s.t. X >= 0 for
-// LHS X = RHS with LHS k x k SPD, warm start X (passive set = X > 0), dual Y = LHS X - RHS.
-int smk_nnls_blockpivot(int k, int64_t ncols, const double* LHS, int64_t ldL, const double* RHS, int64_t ldR, double* X,
-                        int64_t ldX, double* Y, int64_t ldY)
-{
-    if (int rc = require_init()) return rc;
-    if (k <= 0 || ncols <= 0 || !LHS || !RHS || !X || ldL < k || ldR < k || ldX < k || (Y && ldY < k)) return SMK_BAD_PARAM;
-    if (k > MAX_K_BPP) { set_error("device path supports k <= 2048"); return SMK_UNSUPPORTED; }
-    const int KP = kp_of(k);
-    std::vector<double> hg((size_t)KP * KP, 0.0), hr((size_t)KP * ncols, 0.0), hx((size_t)KP * ncols, 0.0);
-    for (int c = 0; c < k; ++c)
-        for (int r = 0; r < k; ++r) hg[(size_t)c * KP + r] = LHS[(size_t)c * ldL + r];
-    for (int64_t c = 0; c < ncols; ++c)
-        for (int r = 0; r < k; ++r) {
-            hr[(size_t)c * KP + r] = RHS[(size_t)c * ldR + r];
-            hx[(size_t)c * KP + r] = X[(size_t)c * ldX + r];
-        }
-    Scratch<double> dg, dr, dx, dy, dscratch;
-    Scratch<int> dflag;
-    int rc = dg.alloc(hg.size());
-    rc |= dr.alloc(hr.size());
-    rc |= dx.alloc(hx.size());
-    rc |= dy.alloc(hx.size());
-    rc |= dscratch.alloc(nnls_uses_tiles(k) ? nnls_wide_scratch_elems(k, ctx().cus, ncols) : nnls_scratch_elems(k));
-    rc |= dflag.alloc(1);
-    if (rc) return SMK_DEVICE_ERROR;
-    const int big = INT_MAX;
-    SMK_HIP(hipMemcpyAsync(dg, hg.data(), hg.size() * sizeof(double), hipMemcpyHostToDevice, ctx().stream));
-    SMK_HIP(hipMemcpyAsync(dr, hr.data(), hr.size() * sizeof(double), hipMemcpyHostToDevice, ctx().stream));
-    SMK_HIP(hipMemcpyAsync(dx, hx.data(), hx.size() * sizeof(double), hipMemcpyHostToDevice, ctx().stream));
-    SMK_HIP(hipMemsetAsync(dy, 0, hx.size() * sizeof(double), ctx().stream));
-    SMK_HIP(hipMemcpyAsync(dflag, &big, sizeof(int), hipMemcpyHostToDevice, ctx().stream));
-    const PartialView pv{dr, 1, 0, KP, 1};
-    rc = launch_nnls_bpp(dx, dy, k, 0, ncols, pv, dg, dflag, 0, dscratch, 0, ctx().cus, ctx().stream);
-    if (rc) return rc;
-    int flag = INT_MAX;
-    SMK_HIP(hipMemcpyAsync(hx.data(), dx, hx.size() * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
-    SMK_HIP(hipMemcpyAsync(hr.data(), dy, hx.size() * sizeof(double), hipMemcpyDeviceToHost, ctx().stream));
-    SMK_HIP(hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, ctx().stream));
-    SMK_HIP(hipStreamSynchronize(ctx().stream));
-    for (int64_t c = 0; c < ncols; ++c)
-        for (int r = 0; r < k; ++r) {
-            X[(size_t)c * ldX + r] = hx[(size_t)c * KP + r];
-            if (Y) Y[(size_t)c * ldY + r] = hr[(size_t)c * KP + r];
-        }
-    return flag == INT_MAX ? SMK_OK : SMK_FAILURE;
-}
-
-// what every way of reading the factors does first
-static int factors_ready(smk_solver* s, int normalize)
-{
-    int rc = gather_w(s);                 // a collective when W is row-sharded and stale: every rank must be here
-    if (rc) return rc;
-    if (normalize) { rc = normalize_device(s); if (rc) return rc; }
-    return 0;
-}
-
-// ... into views in device memory: W (m x k) from Wt, H (k x n) from the first k rows of the resident H, converted in flight
-int smk_solver_get_factors_device(smk_solver* s, int normalize, void* W, int dtypeW, int64_t rsW, int64_t csW, void* H, int dtypeH,
-                                  int64_t rsH, int64_t csH, void* stream)
-{
-    const char* who = "smk_solver_get_factors_device";
-    if (!s) return SMK_BAD_PARAM;
-    const DeviceView vW{W, dtypeW, rsW, csW}, vH{H, dtypeH, rsH, csH};
-    int rc = check_factor_dtypes(who, "factors", dtypeW, dtypeH);
-    if (!rc) rc = resident_pair(s).check(who, vW, vH, true, true);
-    if (rc) return rc;
-    Entry e(s->st);
-    rc = e.join(stream);
-    if (!rc) rc = factors_ready(s, normalize);
-    if (!rc) rc = resident_pair(s).store(&vW, &vH);
-    if (rc) return rc;
-    return e.synced(sync_and_check(s, nullptr));
-}
-
-// Labels / memberships of the local columns and the top terms of the topics, straight from the resident factors (H at H + c KP,
-// W as Wt + i KP: the k-contiguous layout the kernels of assign.hip read; the pad rows are never candidates).  normalize as in
-// smk_solver_get_factors; the solver is otherwise left exactly as it was.
-int smk_solver_labels(smk_solver* s, int normalize, void* stream, void* labels, void* memberships)
-{
-    if (!s) { set_error("smk_solver_labels: null solver"); return SMK_BAD_PARAM; }
-    if (!s->have_factors) { set_error("smk_solver_labels: the solver has no factors yet"); return SMK_BAD_PARAM; }
-    if (!labels) { set_error("smk_solver_labels: null output"); return SMK_BAD_PARAM; }
-    int rc = check_device_view(labels, DT_F32, s->n, 1, 1, s->n, true, "smk_solver_labels(labels)");       // 32-bit integers
-    if (!rc && memberships) rc = check_device_view(memberships, DT_F32, s->k, s->n, 1, s->k, true, "smk_solver_labels(memberships)");
-    if (rc) return rc;
-    Owned own;
-    rc = join_caller_stream(own, s->st, stream);
-    if (!rc) rc = factors_ready(s, normalize);
-    if (rc) return rc;
-    return labels_from_view(s->H, DT_F64, 1, s->KP, s->k, s->n, s->st, own, labels, memberships);
-}
-
-int smk_solver_top_terms(smk_solver* s, int normalize, int maxterms, void* stream, void* term_indices)
-{
-    if (!s) { set_error("smk_solver_top_terms: null solver"); return SMK_BAD_PARAM; }
-    if (!s->have_factors) { set_error("smk_solver_top_terms: the solver has no factors yet"); return SMK_BAD_PARAM; }
-    if (maxterms < 1) { set_error("smk_solver_top_terms: maxterms < 1"); return SMK_BAD_PARAM; }
-    if (!term_indices) { set_error("smk_solver_top_terms: null output"); return SMK_BAD_PARAM; }
-    int rc = check_device_view(term_indices, DT_F32, maxterms, s->k, 1, maxterms, true, "smk_solver_top_terms(term_indices)");
-    if (rc) return rc;
-    Owned own;
-    rc = join_caller_stream(own, s->st, stream);
-    if (!rc) rc = factors_ready(s, normalize);       // a row-sharded W is gathered here
-    if (rc) return rc;
-    return top_terms_from_view(s->Wt, DT_F64, s->KP, 1, s->m, s->k, maxterms, s->st, own, term_indices);
-}
-
-int smk_solver_get_factors(smk_solver* s, int normalize, double* W, int64_t ldW, double* H, int64_t ldH)
-{
-    if (!s || !W || !H) return SMK_BAD_PARAM;
-    if (ldW < s->m || ldH < s->k) { set_error("leading dimension too small"); return SMK_BAD_PARAM; }
-    int rc = factors_ready(s, normalize);
-    if (rc) return rc;
-    rc = launch_transpose_f64(s->Wt, s->KP, s->tmpW, s->m, s->k, s->m, s->st);
-    if (rc) return rc;
-    // Device-to-host copies are kept contiguous: a strided hipMemcpy2DAsync into pageable memory leaves
-    // ~190 KiB of runtime staging behind per call on this ROCm (1200 one-shot sparse runs: 230 MiB).
-    if (ldW == s->m) {
-        SMK_HIP(hipMemcpyAsync(W, s->tmpW, (size_t)s->m * s->k * sizeof(double), hipMemcpyDeviceToHost, s->st));
-    } else {
-        for (int c = 0; c < s->k; ++c)
-            SMK_HIP(hipMemcpyAsync(W + (size_t)c * ldW, s->tmpW + (size_t)c * s->m, (size_t)s->m * sizeof(double),
-                                   hipMemcpyDeviceToHost, s->st));
-    }
-    if (s->k == s->KP && ldH == s->k) {
-        SMK_HIP(hipMemcpyAsync(H, s->H, (size_t)s->k * s->n * sizeof(double), hipMemcpyDeviceToHost, s->st));
-    } else {
-        if (!s->tmpH) { rc = s->own.dev(&s->tmpH, (size_t)s->k * s->n); if (rc) return rc; }
-        rc = launch_compact_rows(s->H, s->KP, s->tmpH, s->k, s->n, s->st);
-        if (rc) return rc;
-        if (ldH == s->k) {
-            SMK_HIP(hipMemcpyAsync(H, s->tmpH, (size_t)s->k * s->n * sizeof(double), hipMemcpyDeviceToHost, s->st));
-        } else {      // caller's leading dimension exceeds k: compact on the device, scatter on the host
-            std::vector<double> tmp((size_t)s->k * s->n);
-            SMK_HIP(hipMemcpyAsync(tmp.data(), s->tmpH, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, s->st));
-            SMK_HIP(hipStreamSynchronize(s->st));
-            for (i64 c = 0; c < s->n; ++c)
-                std::copy(tmp.begin() + c * s->k, tmp.begin() + (c + 1) * s->k, H + c * ldH);
-        }
-    }
-    return sync_and_check(s, nullptr);
-}
-
-int smk_solver_enable_timing(smk_solver* s, int on)
-{
-    if (!s) return SMK_BAD_PARAM;
-    s->timing = on != 0;
-    // one pass in 16 under 1 GB of streamed matrix per pass, one in 8 under 32 GB (a C4 shard in chunks: 8 launches and 8
-    // collectives per iteration would carry ~0.1 ms of event gaps in 3.4 ms), every pass above
-    {
-        const double bytes = (double)s->m * (double)s->n * (s->a->sparse ? 12.0 : (double)elem_size(s->a->storage));
-        s->timing_stride = bytes < (double)((i64)1 << 30) ? 16 : bytes < 32.0 * (double)((i64)1 << 30) ? 8 : 1;
-    }
-    if (const auto ts = sw::timing_stride(); ts.set) s->timing_stride = std::max(1, ts.v);
-    s->pass_counter[0] = s->pass_counter[1] = 0;
-    s->pass_sampled[0] = s->pass_sampled[1] = 0;
-    for (int w = 0; w < 6; ++w) { s->acc_ms[w] = 0.0; s->launches[w] = 0; }
-    return SMK_OK;
-}
-
-int smk_solver_kernel_time(smk_solver* s, int which, double* total_ms, int* launches)
-{
-    if (!s || which < 0 || which > 5) return SMK_BAD_PARAM;      // 2: the (AH')' sum and the W all-gather of a sharded run; 3: main-stream waits for them; 5: block pivoting
-    if (which == 4) {       // calibration brackets: unscaled (their average is what matters)
-        if (total_ms) *total_ms = s->acc_ms[4];
-        if (launches) *launches = s->launches[4];
-        return SMK_OK;
-    }
-    // one pass in `timing_stride` carries events: totals are scaled by the TRUE ratio passes seen / passes sampled (100 passes
-    // at stride 8 are 13 samples standing for 100, not for 104); the collectives (slot 2) are sampled with either pass
-    const unsigned seen = which < 2 ? s->pass_counter[which] : s->pass_counter[0] + s->pass_counter[1];
-    const unsigned sampled = which < 2 ? s->pass_sampled[which] : s->pass_sampled[0] + s->pass_sampled[1];
-    const double f = sampled > 0 ? (double)seen / (double)sampled : 1.0;
-    if (total_ms) *total_ms = s->acc_ms[which] * f;
-    if (launches) *launches = (int)llround((double)s->launches[which] * f);
-    return SMK_OK;
-}
-
-// the kernel pass `which` launches (what the bench lines and profiles attribute their time to); same decision as timed_spmm /
-// launch_bigprod
-int smk_solver_kernel_name(const smk_solver* s, int which, char* out, int cap)
-{
-    if (!s || which < 0 || which > 2 || !out || cap < 8) return SMK_BAD_PARAM;
-    std::string name;
-    if (which == 2) {
-        static const char* const route[4] = {"", "launches of its own behind the iteration",
-                                             "sums in the next H-side NNLS launch, totals as one launch",
-                                             "sums in the next H-side NNLS launch, totals in the tail of the pass behind it"};
-        for (int r = 3; r >= 1; --r)
-            if (s->pc.check_routes[r]) name += (name.empty() ? "" : "; ") + std::to_string(s->pc.check_routes[r]) + " x " + route[r];
-        if (name.empty()) name = "none formed yet";
-    } else if (s->a->sparse) {
-        const int ldx = s->Wc ? 2 : s->KP;
-        if (s->r2p_sync && s->o.algorithm == SMK_ALG_RANK2) name = "smk::rank2_persist_kernel";
-        else if (blocked2_route(s, which, ldx)) name = "smk::spmm_blocked2_kernel";
-        else if (seg_route(s, which, ldx, which == 0 ? s->n : s->m)) name = "smk::spmm_seg_kernel";
-        else name = "smk::spmm_gather_kernel";
-    } else {
-        const BigProdPlan& pl = which == 0 ? s->pl1 : s->pl2;
-        name = s->nsplit == NSPLIT_F64 ? (s->k <= 2 ? "smk::bigprod_f64_k2_kernel" : "smk::bigprod_f64_kernel")
-             : s->a->storage == SMK_STORE_F32 ? "smk::bigprod_f3_kernel" : "smk::bigprod_kernel";
-        name += " variant " + std::to_string(pl.variant) + (pl.tr ? " (transposed source)" : "");
-    }
-    snprintf(out, (size_t)cap, "%s", name.c_str());
-    return SMK_OK;
 }
 
 int smk_debug_nnls_stats(unsigned long long* out256, int reset)
@@ -2113,113 +1460,6 @@ int smk_debug_nnls_stats(unsigned long long* out256, int reset)
     if (!ctx().init) return SMK_NOTINITIALIZED;
     const int rc = nnls_stats_read(out256, reset);
     return rc == 0 ? SMK_OK : rc == -1 ? SMK_UNSUPPORTED : SMK_DEVICE_ERROR;
-}
-
-int smk_solver_kernel_work(const smk_solver* s, int which, double* bytes, double* flops)
-{
-    if (!s || which < 0 || which > 1) return SMK_BAD_PARAM;
-    if (s->a->sparse) {   // per nonzero: 12 bytes of A (value + row index) + one KP-row of X gathered
-        if (bytes) *bytes = (double)s->a->nnz * (12.0 + 8.0 * (s->Wc ? 2 : s->KP));      // RANK2 gathers 16 B rows of the compact copy
-        if (flops) *flops = 2.0 * (double)s->a->nnz * s->k;
-        return SMK_OK;
-    }
-    const double mn = (double)s->m * (double)s->n;
-    if (bytes) *bytes = mn * elem_size(s->a->storage);
-    if (flops) *flops = 2.0 * mn * s->k / s->ng;      // per launch: k > 64 streams the matrix once per group of 64 rows
-    return SMK_OK;
-}
-
-// Result Nmf(...) on `nshards` column shards of A, one host thread + one HIP device per shard: A and H
-// column-sharded, W replicated, RCCL collectives issued from C on each shard's streams.  `devices` NULL: shard r on
-// device r.  local_stub != 0: every shard on the CURRENT device with the in-process stand-in for RCCL (which refuses
-// two ranks on one device) -- for boxes with fewer GPUs than shards, and for the tests.
-int smk_nmf_dense_sharded(const smk_options* opts, const double* A, int64_t ldA, double* W, int64_t ldW, double* H,
-                          int64_t ldH, smk_stats* stats, int storage, int nshards, const int* devices, int local_stub)
-{
-    if (!ctx().init) {
-        fprintf(stderr, "nmflib error: nmf_initialize() must be called prior to any factorization routine\n\n");
-        return SMK_NOTINITIALIZED;
-    }
-    if (!opts || !smk_is_valid(opts, 1)) return SMK_BAD_PARAM;
-    if (!A || !W || !H || nshards < 1 || nshards > 16) return SMK_BAD_PARAM;
-    if (opts->k > MAX_K || (opts->algorithm == SMK_ALG_BPP && opts->k > MAX_K_BPP)) { set_error("device path supports k <= 2048"); return SMK_UNSUPPORTED; }
-    const int64_t m = opts->height, n = opts->width;
-    if (ldA < m || ldW < m || ldH < opts->k) { set_error("leading dimension too small"); return SMK_BAD_PARAM; }
-    if (nshards > n) nshards = (int)n;
-    if (nshards == 1) return smk_nmf_dense(opts, A, ldA, W, ldW, H, ldH, stats, storage);
-    int dev0 = 0;
-    SMK_HIP(hipGetDevice(&dev0));
-    if (!local_stub) {
-        int ndev = 0;
-        SMK_HIP(hipGetDeviceCount(&ndev));
-        for (int r = 0; r < nshards; ++r)
-            if ((devices ? devices[r] : r) >= ndev) { set_error("smk_nmf_dense_sharded: not enough devices for the shards"); return SMK_BAD_PARAM; }
-    }
-    std::vector<smk_comm*> comms((size_t)nshards, nullptr);
-    std::vector<int> devs((size_t)nshards);
-    for (int r = 0; r < nshards; ++r) devs[(size_t)r] = local_stub ? dev0 : (devices ? devices[r] : r);
-    int rc = local_stub ? smk_comm_init_local(comms.data(), nshards) : smk_comm_init_all(comms.data(), nshards, devs.data());
-    if (rc != SMK_OK) return rc;
-
-    std::vector<int> rcs((size_t)nshards, SMK_OK);
-    std::vector<smk_stats> sts((size_t)nshards, smk_stats{0, 0});
-    std::vector<std::string> errs((size_t)nshards);
-    std::vector<double> Wcopy((size_t)m * opts->k);          // every shard starts from the same W0
-    for (int c = 0; c < opts->k; ++c) std::copy(W + (size_t)c * ldW, W + (size_t)c * ldW + m, Wcopy.begin() + (size_t)c * m);
-    auto worker = [&](int r) {
-        DeviceCtx local;
-        t_ctx = &local;
-        int wrc = SMK_OK;
-        smk_matrix* a = nullptr;
-        smk_solver* s = nullptr;
-        const int64_t base = n / nshards, extra = n % nshards;
-        const int64_t c0 = r * base + std::min<int64_t>(r, extra), nc = base + (r < extra ? 1 : 0);
-        wrc = smk_initialize(devs[(size_t)r]);
-        if (wrc == SMK_OK) wrc = smk_matrix_create(&a, m, n, c0, nc, storage);
-        if (wrc == SMK_OK) wrc = smk_matrix_upload_f64(a, A + (size_t)c0 * ldA, ldA);
-        if (wrc == SMK_OK) wrc = smk_solver_create(&s, opts, a);
-        if (wrc == SMK_OK) wrc = smk_solver_attach_comm(s, comms[(size_t)r]);
-        if (wrc == SMK_OK) wrc = smk_solver_set_factors(s, Wcopy.data(), m, H + (size_t)c0 * ldH, ldH);
-        // a shard that failed before the first collective would strand the others: agree on the setup first
-        {
-            double ok = (wrc == SMK_OK) ? 0.0 : 1.0;
-            Scratch<double> dflag;
-            if (smk::dev_malloc(dflag.put(), sizeof(double)) == hipSuccess) {
-                (void)hipMemcpy(dflag, &ok, sizeof(double), hipMemcpyHostToDevice);
-                (void)comm_allreduce(comms[(size_t)r], dflag, 1, 1, ctx().stream);
-                (void)hipStreamSynchronize(ctx().stream);
-                (void)hipMemcpy(&ok, dflag, sizeof(double), hipMemcpyDeviceToHost);
-            }
-            if (ok != 0.0 && wrc == SMK_OK) wrc = SMK_FAILURE;
-        }
-        if (wrc == SMK_OK) {
-            wrc = smk_solver_run(s, &sts[(size_t)r]);
-            // anything but an agreed result (OK / FAILURE are all-reduced) means this rank left the loop alone: release the
-            // peers that wait for it in a collective
-            if (wrc != SMK_OK && wrc != SMK_FAILURE) smk_comm_abort(comms[(size_t)r]);
-            if (wrc == SMK_OK || wrc == SMK_FAILURE) {
-                // W is replicated: rank 0 returns it; every rank returns its own columns of H
-                std::vector<double> Wl(r == 0 ? 0 : (size_t)m * opts->k);
-                (void)smk_solver_get_factors(s, 0, r == 0 ? W : Wl.data(), r == 0 ? ldW : m, H + (size_t)c0 * ldH, ldH);
-            }
-        }
-        errs[(size_t)r] = smk_last_error();
-        smk_solver_destroy(s);
-        smk_matrix_destroy(a);
-        smk_finalize();
-        rcs[(size_t)r] = wrc;
-        t_ctx = nullptr;
-    };
-    std::vector<std::thread> th;
-    for (int r = 0; r < nshards; ++r) th.emplace_back(worker, r);
-    for (auto& t : th) t.join();
-    for (smk_comm* c : comms) smk_comm_destroy(c);
-    (void)hipSetDevice(dev0);
-    int result = SMK_OK;
-    for (int r = 0; r < nshards; ++r)
-        if (rcs[(size_t)r] != SMK_OK && result == SMK_OK) { result = rcs[(size_t)r]; set_error(errs[(size_t)r]); }
-    if (stats) *stats = sts[0];
-    return result;
 }
 
 }  // extern "C"

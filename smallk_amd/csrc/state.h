@@ -1,4 +1,5 @@
-// smallk_amd/csrc/state.h -- host state shared by context.cpp, matrix.cpp, solver.cpp and progress.cpp: the per-thread device
+// smallk_amd/csrc/state.h -- host state shared by context.cpp, matrix.cpp and the files behind the solver handle (solver.cpp, progress.cpp,
+// attach.cpp, factors.cpp, guard.cpp, timing.cpp): the per-thread device
 // context, the resident matrix and the solver handle behind the opaque types of include/smallk_amd.h, and the
 // few functions that cross those files.
 #pragma once
@@ -108,72 +109,92 @@ struct ProgressCheck {
     void reset_estimator() { pg0 = last_metric = 1.0; sums_state = 0; }         // a run from the start
 };
 
-struct smk_solver {
-    smk_options o;
-    const smk_matrix* a = nullptr;
-    int k = 0, KP = 0, kpp = 0, nsplit = 3;
-    i64 m = 0, n = 0;
-    hipStream_t st = nullptr;
-    smk::Owned own;                       // every device block, pinned block, event and stream below was created through it and is released by it alone
-    double *H = nullptr, *Wt = nullptr, *Gw = nullptr, *Gh = nullptr, *gram_scratch = nullptr;
-    double* seg_pieces[2] = {nullptr, nullptr};     // sparse A, spmm_seg.hip: partial sums of the long columns of pass 0 / 1
-    double *Wprev = nullptr, *hals_scratch = nullptr, *pg_partials = nullptr, *scal = nullptr, *tmpW = nullptr;
-    double* wide_tmp = nullptr;           // k > 128: max(m, n) x KP, the product X G of the MU rule and of the gradients
-    double* tmpH = nullptr;               // k x n compact copy of H for the host (get_factors)
-    // RANK2 (rank2.hip): scratch of the fused solve / progress kernels (ticket + partial sums), W'W of the W just solved
-    // (before its normalisation), and -- sparse A -- compact N x 2 copies of the factors for the gather products
-    double *r2_scratch = nullptr, *r2_prog = nullptr, *Graw = nullptr, *Hc = nullptr, *Wc = nullptr;
-    // the whole RANK2 factorisation as one resident launch (rank2_persist.hip): second H buffer, the rows of (AH')', partial
-    // sums, barrier words, result slots (device + pinned); latched off after an aborted launch
-    double *r2p_hc1 = nullptr, *r2p_r2c = nullptr, *r2p_part = nullptr, *r2p_out = nullptr, *r2p_pin = nullptr;
-    unsigned* r2p_sync = nullptr;
-    bool r2p_off = false;
-    // run-time guard of the product form (guard_step): a column sample of A, its accurate-form product, the comparison scalars
-    // + both Gram matrices on their way to the host
-    void* guard_As = nullptr;
-    unsigned* guard_cols = nullptr;
-    double *guard_P = nullptr, *guard_dev = nullptr, *guard_pin = nullptr;
-    hipEvent_t guard_ev = nullptr;
-    BigProdPlan guard_pl[MAX_GROUPS];
-    int guard_ncols = 0, guard_checks = 0, guard_fired = 0;
-    bool guard_pending = false, guard_off = false;
-    double guard_last = 0.0;               // cond * delta of the last check
-    bool wc_valid = false;
-    double* nnls_scratch = nullptr;       // BPP: inverses of W'W and HH' + path selectors (k in (16, 64]), two halves
-    int hals_ep_blocks = 0;               // HALS, k <= 32: Gram partials the sweeps' epilogues may write into gram_scratch (0: epilogues off)
-    hipStream_t st_inv = nullptr;         // the 0.1 ms single-workgroup inversions run here, beside the streaming products
-    hipEvent_t ev_g[2] = {nullptr, nullptr}, ev_inv[2] = {nullptr, nullptr};
-    bool inv_pending[2] = {false, false};
-    bool gram_ride[2] = {false, false};   // sparse, k in (8, 32]: this factor's Gram matrix is due and rides in the two launches of the gather product that follows (gram_factor, timed_spmm)
-    bool inv_ride[2] = {false, false};    // sparse BPP, k in (16, 64]: this side's Gram matrix is new, its inverse is to ride in the product launch that follows (timed_spmm)
-    double *xscale[2] = {nullptr, nullptr}, *oscale[2] = {nullptr, nullptr};   // fp16 two-term products: row scales of W / H (from the Gram diagonal) and their inverses
-    bool packed_fresh[2] = {false, false};   // the fused Gram kernel has already written packW / packH for the next product
-    int nnls_gram_nblk[2] = {0, 0};          // > 0: the NNLS launch of this side left that many Gram partials in gram_scratch (k <= 16)
-    // k in (8, 16], BPP, fp16 form, one GPU (C2): the NNLS launch also PACKS the factor it solves (row scales from an a-priori
-    // bound, NnlsPack) and the reduction of its Gram partials rides in the streaming pass that follows (BigProdPlan::tail_*),
-    // so nothing stands between the solve and the product.  Indexed by factor: 0 = W, 1 = H.
-    bool pack_in_solve = false;              // the shape qualifies (decided with the plans)
-    bool pack_in_solve_off = false;          // latched by pack_fail_soft
-    bool from_nnls[2] = {false, false};      // the factor is the output of an NNLS launch of this run (hence >= 0)
-    bool nnls_packed[2] = {false, false};    // the last NNLS launch packed this factor
-    int tail_nblk[2] = {0, 0};               // > 0: the next product of this factor carries the reduction of that many partials
-    // HALS: the fused W sweep needs every workgroup resident; if its bounded polls ever expire (flag -3) the run is
-    // repeated from the initial factors on the one-launch-per-column path, latched for the life of the handle
-    double *W0c = nullptr, *H0c = nullptr;
-    bool hals_multi = false;
-    int hals_calls = 0;
-    void *packW = nullptr, *packH = nullptr;
-    double *P1 = nullptr, *P2 = nullptr;
-    float* R2red = nullptr;
-    BigProdPlan pl1, pl2;                 // first group of each pass (row splits, P layout)
-    BigProdPlan pg1[MAX_GROUPS], pg2[MAX_GROUPS];   // all groups: k > 64 streams the big matrix once per 64 factor rows
-    int ng = 1;
-    int* fail_flag = nullptr;
-    int iter = 0;
-    bool have_factors = false, inited = false, normalized = false;
-    ProgressCheck pc;                     // the stopping rule's check (progress.cpp)
-    size_t pg_half = 2048;
-    // comm: a native communicator (RCCL or the in-process stand-in, comm.cpp) or -- test hook -- a host callback
+// What one launch tells the next about a factor (solver.cpp).  smk_solver::hand[f] is indexed by the FACTOR, 0 = W and 1 = H, and by
+// nothing else: the NNLS launch of side 0 solves H against W'W, so it reads hand[0] (is W the output of a solve, is the inverse of
+// W'W in place) and writes hand[1] (what it left of H).
+enum class Inverse {
+    none,               // nobody has formed it: launch_nnls_bpp does, in stream order
+    ride_due,           // the product launch that follows this Gram matrix is to carry it (start_inverse)
+    on_side_stream,     // enqueued on st_inv, ev_inv[f] recorded behind it: the solve waits for that event
+    done                // in inv_scratch(f), ordered before the main stream
+};
+struct Handoff {
+    // what the launch that last wrote this factor left
+    bool from_nnls = false;          // the factor is the output of an NNLS launch of this run (hence >= 0)
+    bool packed_by_solve = false;    // that launch also packed it (NnlsPack: k in (8, 16], BPP, fp16 form, one GPU -- C2) ...
+    int gram_partials = 0;           // ... and left that many Gram partials of it in gram_scratch (k <= 16; 0: none)
+    // what this factor's Gram matrix owes the next product of this factor
+    bool packed_fresh = false;       // the Gram launch has already written packW / packH for that product
+    int tail_nblk = 0;               // > 0: the product carries the reduction of that many partials in its tail (BigProdPlan::tail_*)
+    bool gram_ride = false;          // sparse, k in (8, 32]: the Gram matrix is due and rides in the two launches of the gather product (gram_factor, timed_spmm)
+    // the inverse of this factor's Gram matrix (BPP, k in (16, 64]): start_inverse begins every life of it with forget_inverse()
+    Inverse inverse = Inverse::none;
+    void forget_inverse() { inverse = Inverse::none; }                       // the Gram matrix is new
+    void inverse_will_ride() { inverse = Inverse::ride_due; }                // the product launch that follows is to carry it
+    bool take_inverse_ride()                                                 // "this launch will carry it" (asked by every product launch)
+    {
+        if (inverse != Inverse::ride_due) return false;
+        inverse = Inverse::none;                                             // until the launch says it did
+        return true;
+    }
+    void inverse_carried() { inverse = Inverse::done; }                      // the launch returned 1
+    void inverse_sent_to_side_stream() { inverse = Inverse::on_side_stream; }
+    bool inverse_on_side_stream() const { return inverse == Inverse::on_side_stream; }
+    void inverse_joined() { inverse = Inverse::done; }                       // the main stream waits for ev_inv[f]
+    void inverse_formed_by_solve() { inverse = Inverse::done; }              // launch_nnls_bpp found none and formed it itself
+    bool inverse_ready() const { return inverse == Inverse::done; }
+    bool take_gram_ride() { const bool due = gram_ride; gram_ride = false; return due; }
+    // the factor is the caller's (or a restored snapshot, or about to be): nothing is known to come from an NNLS launch, nothing
+    // is owed, nothing is in flight that anybody will wait for
+    void reset() { *this = Handoff(); }
+};
+
+// Run-time guard of the product form (guard.cpp): a column sample of A, its accurate-form product, the comparison scalars + both
+// Gram matrices on their way to the host
+struct ProductGuard {
+    void* As = nullptr;
+    unsigned* cols = nullptr;
+    double *P = nullptr, *dev = nullptr, *pin = nullptr;
+    hipEvent_t ev = nullptr;
+    BigProdPlan pl[MAX_GROUPS];
+    int ncols = 0, checks = 0, fired = 0;
+    bool pending = false, off = false;
+    double last = 0.0;                     // cond * delta of the last check
+};
+
+// The whole RANK2 factorisation as one resident launch (rank2_persist.hip): second H buffer, the rows of (AH')', partial sums,
+// barrier words, result slots (device + pinned); latched off after an aborted launch
+struct ResidentRank2 {
+    double *hc1 = nullptr, *r2c = nullptr, *part = nullptr, *out = nullptr, *pin = nullptr;
+    unsigned* sync = nullptr;
+    bool off = false;
+};
+
+// smk_solver_kernel_time (timing.cpp; the spans are opened on the per-iteration path, solver.cpp)
+struct Timing {
+    bool on = false;
+    // a pair of event records around a launch costs ~11 us of idle time (5.7 us in front of the kernel, 5.8 behind it: measured
+    // on C2, where that was 23 of 119 us per iteration): passes shorter than ~0.2 ms are timed one launch in `stride`
+    // and the totals scaled back up, so that measuring does not change what is measured
+    int stride = 1;
+    unsigned pass_counter[2] = {0, 0}, pass_sampled[2] = {0, 0};     // passes seen / passes that carried events since enable_timing
+    bool pass_timed[2] = {false, false};     // this W'A / H*At pass (all of its launches, and the collectives behind it) is a timed sample
+    struct TimedSpan { hipEvent_t e0, e1; int counts; };     // counts: this span completes one launch (a pass cut into chunks is ONE launch)
+    // 0: W'A passes, 1: H*At passes, 2: the big collectives of a sharded run (on st2), 3: what the MAIN stream spends waiting
+    // for events of the collective stream (the exposed part of the exchange: the bracket holds nothing but the wait)
+    // 4: the same bracket around a wait for an event that completed long ago -- what a bracket costs by itself (three packets
+    // through the command processor, ~15 us): exposure = slot 3 - brackets x the average of slot 4
+    std::vector<TimedSpan> ev[6];       // 0 / 1: the passes, 2 - 4: collectives, waits, calibration, 5: the block-pivoting launches
+    std::vector<TimedSpan> span_pool;   // event pairs whose times have been read (resolve_events): span_open hands them out again
+    double acc_ms[6] = {0, 0, 0, 0, 0, 0};
+    int launches[6] = {0, 0, 0, 0, 0, 0};
+    hipEvent_t ev_cal = nullptr;          // recorded once on the collective stream
+    unsigned cal_counter = 0;
+};
+
+// comm: a native communicator (RCCL or the in-process stand-in, comm.cpp) or -- test hook -- a host callback (attach.cpp; the
+// exchange itself runs on the per-iteration path, solver.cpp)
+struct Exchange {
     int rank = 0, world = 1;
     smk_allreduce_fn ar = nullptr;
     double* home[3] = {nullptr, nullptr, nullptr};   // callback hook: where Gh / scal / Wt pointed before smk_solver_set_comm moved them into the caller's workspace
@@ -201,26 +222,58 @@ struct smk_solver {
     hipEvent_t ev_c[MAX_CHUNKS] = {}, ev_r[MAX_CHUNKS] = {}, ev_a[MAX_CHUNKS] = {};
     bool gh_pending = false;
     bool r2_pending = false;              // the chunk exchanges of the last H*At pass have not been joined by the main stream yet
-    bool inv_done[2] = {false, false};    // the inverse of this side's current Gram matrix is in place (ordered before the main stream)
-    // timing
-    bool timing = false;
-    // a pair of event records around a launch costs ~11 us of idle time (5.7 us in front of the kernel, 5.8 behind it: measured
-    // on C2, where that was 23 of 119 us per iteration): passes shorter than ~0.2 ms are timed one launch in `timing_stride`
-    // and the totals scaled back up, so that measuring does not change what is measured
-    int timing_stride = 1;
-    unsigned pass_counter[2] = {0, 0}, pass_sampled[2] = {0, 0};     // passes seen / passes that carried events since enable_timing
-    bool pass_timed[2] = {false, false};     // this W'A / H*At pass (all of its launches, and the collectives behind it) is a timed sample
-    struct TimedSpan { hipEvent_t e0, e1; int counts; };     // counts: this span completes one launch (a pass cut into chunks is ONE launch)
-    // 0: W'A passes, 1: H*At passes, 2: the big collectives of a sharded run (on st2), 3: what the MAIN stream spends waiting
-    // for events of the collective stream (the exposed part of the exchange: the bracket holds nothing but the wait)
-    // 4: the same bracket around a wait for an event that completed long ago -- what a bracket costs by itself (three packets
-    // through the command processor, ~15 us): exposure = slot 3 - brackets x the average of slot 4
-    std::vector<TimedSpan> ev[6];       // 0 / 1: the passes, 2 - 4: collectives, waits, calibration, 5: the block-pivoting launches
-    std::vector<TimedSpan> span_pool;   // event pairs whose times have been read (resolve_events): span_open hands them out again
-    double acc_ms[6] = {0, 0, 0, 0, 0, 0};
-    int launches[6] = {0, 0, 0, 0, 0, 0};
-    hipEvent_t ev_cal = nullptr;          // recorded once on the collective stream
-    unsigned cal_counter = 0;
+};
+
+// The solver handle.  Its subsystems are members held by value, each with its comment at its struct above; every device block,
+// pinned block, event and stream of every one of them is created through the handle's single `own`.
+struct smk_solver {
+    smk_options o;
+    const smk_matrix* a = nullptr;
+    int k = 0, KP = 0, kpp = 0, nsplit = 3;
+    i64 m = 0, n = 0;
+    hipStream_t st = nullptr;
+    smk::Owned own;                       // every device block, pinned block, event and stream below was created through it and is released by it alone
+    double *H = nullptr, *Wt = nullptr, *Gw = nullptr, *Gh = nullptr, *gram_scratch = nullptr;
+    double* seg_pieces[2] = {nullptr, nullptr};     // sparse A, spmm_seg.hip: partial sums of the long columns of pass 0 / 1
+    double *Wprev = nullptr, *hals_scratch = nullptr, *pg_partials = nullptr, *scal = nullptr, *tmpW = nullptr;
+    double* wide_tmp = nullptr;           // k > 128: max(m, n) x KP, the product X G of the MU rule and of the gradients
+    double* tmpH = nullptr;               // k x n compact copy of H for the host (get_factors)
+    // RANK2 (rank2.hip): scratch of the fused solve / progress kernels (ticket + partial sums), W'W of the W just solved
+    // (before its normalisation), and -- sparse A -- compact N x 2 copies of the factors for the gather products
+    double *r2_scratch = nullptr, *r2_prog = nullptr, *Graw = nullptr, *Hc = nullptr, *Wc = nullptr;
+    ResidentRank2 r2p;
+    ProductGuard guard;
+    bool wc_valid = false;
+    double* nnls_scratch = nullptr;       // BPP: inverses of W'W and HH' + path selectors (k in (16, 64]), two halves
+    int hals_ep_blocks = 0;               // HALS, k <= 32: Gram partials the sweeps' epilogues may write into gram_scratch (0: epilogues off)
+    hipStream_t st_inv = nullptr;         // the 0.1 ms single-workgroup inversions run here, beside the streaming products
+    hipEvent_t ev_g[2] = {nullptr, nullptr}, ev_inv[2] = {nullptr, nullptr};
+    Handoff hand[2];                      // by factor: 0 = W, 1 = H
+    void forget_handoffs() { hand[0].reset(); hand[1].reset(); }
+    double *xscale[2] = {nullptr, nullptr}, *oscale[2] = {nullptr, nullptr};   // fp16 two-term products: row scales of W / H (from the Gram diagonal) and their inverses
+    // k in (8, 16], BPP, fp16 form, one GPU (C2): the NNLS launch also PACKS the factor it solves (row scales from an a-priori
+    // bound, NnlsPack) and the reduction of its Gram partials rides in the streaming pass that follows (Handoff::tail_nblk),
+    // so nothing stands between the solve and the product.
+    bool pack_in_solve = false;              // the shape qualifies (decided with the plans)
+    bool pack_in_solve_off = false;          // latched by pack_fail_soft
+    // HALS: the fused W sweep needs every workgroup resident; if its bounded polls ever expire (flag -3) the run is
+    // repeated from the initial factors on the one-launch-per-column path, latched for the life of the handle
+    double *W0c = nullptr, *H0c = nullptr;
+    bool hals_multi = false;
+    int hals_calls = 0;
+    void *packW = nullptr, *packH = nullptr;
+    double *P1 = nullptr, *P2 = nullptr;
+    float* R2red = nullptr;
+    BigProdPlan pl1, pl2;                 // first group of each pass (row splits, P layout)
+    BigProdPlan pg1[MAX_GROUPS], pg2[MAX_GROUPS];   // all groups: k > 64 streams the big matrix once per 64 factor rows
+    int ng = 1;
+    int* fail_flag = nullptr;
+    int iter = 0;
+    bool have_factors = false, inited = false, normalized = false;
+    ProgressCheck pc;                     // the stopping rule's check (progress.cpp)
+    size_t pg_half = 2048;
+    Exchange ex;
+    Timing timing;
 };
 
 namespace smk {

@@ -308,7 +308,7 @@ int smk_svd_last_profile(int* host_trips, double* host_ms)
 int smk_solver_set_factors_nndsvd(smk_solver* s, const smk_svd_options* opts, int variant)
 {
     if (!s) { set_error("smk_solver_set_factors_nndsvd: null solver"); return SMK_BAD_PARAM; }
-    if (s->ar || s->comm || s->world > 1) { set_error("smk_solver_set_factors_nndsvd: not available on a solver with a communicator"); return SMK_UNSUPPORTED; }
+    if (s->ex.ar || s->ex.comm || s->ex.world > 1) { set_error("smk_solver_set_factors_nndsvd: not available on a solver with a communicator"); return SMK_UNSUPPORTED; }
     if (variant != SMK_NNDSVD && variant != SMK_NNDSVDA) { set_error("smk_solver_set_factors_nndsvd: unknown variant"); return SMK_BAD_PARAM; }
     SvdRun r;
     int rc = svd_args("smk_solver_set_factors_nndsvd", s->a, opts, s->k, r);

@@ -35,7 +35,7 @@ inline Maybe<uint64_t> u64_if_set(const char* e) { return {e != nullptr, e ? (ui
 #define SMK_SW_ONCE(fn, env, parse) inline auto fn() { static const auto v = [] { const char* e = std::getenv(env); return parse; }(); return v; }
 #define SMK_SW_LIVE(fn, env, parse) inline auto fn() { const char* e = std::getenv(env); return parse; }
 
-// ---- product form and streaming products (solver.cpp, bigprod.hip, matrix.cpp) ----------------------------------------------------
+// ---- product form and streaming products (solver.cpp, guard.cpp, bigprod.hip, matrix.cpp) -----------------------------------------
 SMK_SW_LIVE(nsplit,             "SMK_NSPLIT",               int_if_set(e))          // product form: 1 native fp32 / 2 two bf16 terms / 3 bf16x3 / 4 fp16 two-term / 8 accurate fp64; unset: chosen per solver (other numbers: the default form, but no spread measurement)
 SMK_SW_LIVE(bpp_small_accurate, "SMK_BPP_SMALL_ACCURATE",   on_unless_0(e))         // BPP, k in (32, 64], A of at most 2^24 entries takes the accurate form (0: keeps the fp16 form; the test suite sets it)
 SMK_SW_LIVE(bp_variant,         "SMK_BP_VARIANT",           int_if_set(e))          // streaming-kernel variant (unset: by storage, form and length)
@@ -72,7 +72,7 @@ SMK_SW_ONCE(hals_w_multi,       "SMK_HALS_W",               starts_with(e, 'm'))
 SMK_SW_ONCE(hals_spin,          "SMK_HALS_SPIN",            int_or(e, 0))           // bound of the persistent sweep's exchange polls (<= 0: 2^22; tests set 1 to force the fallback)
 SMK_SW_ONCE(hals_nt,            "SMK_HALS_NT",              int_or(e, 256))         // smallest workgroup size of the persistent W sweep
 
-// ---- stopping rule and timing (solver.cpp) ---------------------------------------------------------------------------------------
+// ---- stopping rule and timing (solver.cpp, progress.cpp, timing.cpp) -------------------------------------------------------------
 SMK_SW_ONCE(sync_progress,      "SMK_SYNC_PROGRESS",        on_if_nonzero(e))       // check the stopping rule synchronously every iteration
 SMK_SW_ONCE(progress_fused,     "SMK_PROGRESS_FUSED",       on_unless_0(e))         // the check as two launches without a copy packet; 0: four stream operations
 SMK_SW_ONCE(progress_defer,     "SMK_PROGRESS_DEFER",       on_unless_0(e))         // BPP, k <= 16: the check rides in the next iteration's NNLS launches
@@ -99,7 +99,7 @@ SMK_SW_ONCE(r2p_wgs,            "SMK_R2P_WGS",              int_or(e, 0))       
 SMK_SW_ONCE(r2p_lds,            "SMK_R2P_LDS",              int_or(e, 1))           // 0: products and offsets only in LDS, no row-index copies
 SMK_SW_ONCE(r2p_profile,        "SMK_R2P_PROFILE",          on_if_nonzero(e))       // the kernel's phase timers per factorisation on stderr
 
-// ---- several GPUs (facade.cpp, solver.cpp, comm.cpp) -----------------------------------------------------------------------------
+// ---- several GPUs (facade.cpp, attach.cpp, solver.cpp, comm.cpp) -----------------------------------------------------------------
 SMK_SW_LIVE(num_gpus,           "SMK_NUM_GPUS",             int_or(e, 0))           // Nmf() runs column-sharded over n devices, at most 16 (<= 1: one device)
 SMK_SW_LIVE(shards_on_one_gpu,  "SMK_SHARDS_ON_ONE_GPU",    on_if_nonzero(e))       // all shards / HierNMF2 workers on the current device, stand-in collectives
 SMK_SW_LIVE(comm_force,         "SMK_COMM_FORCE",           on_if_nonzero(e))       // the collectives are issued at world 1 too

@@ -20,7 +20,7 @@ def shard_columns(n: int, world: int, rank: int):
 
 
 def chunk_geometry(m: int, world: int, chunks: int | None = None):
-    """The block-cyclic row layout of the native exchange (solver.cpp: smk_solver_attach_comm).
+    """The block-cyclic row layout of the native exchange (attach.cpp: smk_solver_attach_comm).
 
     The rows of A (= rows of W) are cut into ``nchunk`` chunks of ``world * blk`` rows; block r of a chunk belongs to
     rank r.  A chunk is one contiguous range of the H*At pass, the send buffer of one reduce-scatter and the receive

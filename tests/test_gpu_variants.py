@@ -164,7 +164,7 @@ def test_hals_blocked_w_sweep_with_more_rows_than_threads(gpu):
 def test_runtime_guard_of_the_product_form():
     """Opt-in (SMK_GUARD_EVERY=n, BPP): every n iterations the solver compares the fast product form with the accurate one on a
     column sample and changes to the accurate form when cond(Gram) x (product discrepancy) says that one iteration could move
-    the factors by the 1e-4 bar (solver.cpp: guard_step).  On data whose planted factor has nearly collinear columns the guard
+    the factors by the 1e-4 bar (guard.cpp: guard_step).  On data whose planted factor has nearly collinear columns the guard
     must fire at k = 8 -- far below the static k > 64 rule -- and the run must end inside the bar; on uniform noise it must look
     and leave the fast form alone.  Without the switch nothing looks.  (Own processes: the switches are read once per process.)"""
     import json
