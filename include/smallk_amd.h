@@ -343,6 +343,26 @@ int smk_kl_last_profile(int* entry_passes, int* divergence_passes);
  * the same plan, rank and gathered factor as 0 / 1: one gather of the same rows without the dot product and the quotient */
 int smk_kl_step_time(const smk_matrix* a, int which, int k, int reps, double* ms);
 
+/* ---- the same iteration on a DENSE resident matrix: the sums run over every entry of the stored matrix (bf16 or fp32
+ * storage, widened exactly; a stored 0 contributes nothing), so on the same data the result is smk_nmf_kl_device's up to summation
+ * order.  Each half-iteration is one streaming read of one stored copy: A for H, the stored transpose for W; two chained fp64
+ * matrix-core contractions per tile, no m x n temporary.  Options, statistics, views and the stopping rule are smk_nmf_kl_device's.
+ * SMK_BAD_PARAM: as there (a negative stored value included).  SMK_UNSUPPORTED: a sparse matrix, k > 128, a column shard, and a
+ * single-copy matrix when update_w != 0 (the W step needs the stored transpose; the fold-in on a single copy is served).  On an
+ * error W and H are untouched. */
+int smk_nmf_kl_dense_device(const smk_matrix* a, int k, const smk_kl_options* o, void* W, int dtW, int64_t rsW, int64_t csW,
+                            void* H, int dtH, int64_t rsH, int64_t csH, void* stream, smk_kl_stats* stats);
+/* out[0 .. 2] as smk_matrix_kl_divergence_device, over every entry with a > EPS; one read of A, a single copy is served */
+int smk_matrix_kl_divergence_dense_device(const smk_matrix* a, int k, const void* W, int dtW, int64_t rsW, int64_t csW,
+                                          const void* H, int dtH, int64_t rsH, int64_t csH, void* stream, double* out);
+/* diagnostics of the calling thread's last smk_nmf_kl_dense_device call: streaming passes over A or A' that updated a factor, and
+ * passes over A that formed the divergence */
+int smk_kl_dense_last_profile(int* matrix_passes, int* divergence_passes);
+/* measurement (tools/kl_dense_rate.py): the average time in ms of `reps` launches on synthetic factors of rank k.  which: 0 the H
+ * step with its finish (over A), 1 the W step with its finish (over the stored transpose), 2 the residual pass of
+ * smk_matrix_residual on A at the same rank: one product over the same bytes, the floor to compare with */
+int smk_kl_dense_step_time(const smk_matrix* a, int which, int k, int reps, double* ms);
+
 /* ---- labels, memberships, top terms and fold-in, on the device (the device twins of smk_compute_assignments,
  * smk_compute_fuzzy_assignments and smk_top_terms below: the same comparisons in the same order, so the same integers and the
  * same membership bits; no k <= n and no height >= width requirement) -----------------------------------------------------

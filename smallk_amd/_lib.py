@@ -174,6 +174,10 @@ SYMBOLS = {
     "smk_matrix_kl_divergence_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _dp]),
     "smk_kl_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "smk_kl_step_time": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp]),
+    "smk_nmf_kl_dense_device": (C.c_int, [_vp, C.c_int, C.POINTER(KlOptions), _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, C.POINTER(KlStats)]),
+    "smk_matrix_kl_divergence_dense_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _dp]),
+    "smk_kl_dense_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "smk_kl_dense_step_time": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp]),
     "smk_labels_device": (C.c_int, [_vp, C.c_int, _i64, _i64, C.c_int, _i64, _vp, _vp, _vp]),
     "smk_top_terms_device": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, _vp, _vp]),
     "smk_solver_labels": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),

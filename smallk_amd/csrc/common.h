@@ -457,6 +457,8 @@ int launch_spmm_seg(const SegPlan& sp, const i64* colptr, const double* val, con
 // against the stored values of A, the same bits on every run.  Wt: m x k with ldf doubles per row of W, H: n columns of ldf
 // doubles; factor rows from k on are never read.  scratch: residual_*_scratch_elems doubles.  Dense: one read of A, never of A'.
 size_t residual_dense_scratch_elems(i64 m, i64 n, int num_cus);
+// how a dense streaming launch is cut: 64 x 64 tiles, S spans of tps row tiles per column tile (S <= 32, every span non-empty)
+void residual_dense_shape(i64 m, i64 n, int num_cus, i64* row_tiles, i64* col_tiles, i64* tps, int* S);
 int launch_residual_dense(const void* A, int storage, i64 ldA, i64 m, i64 n, const double* Wt, const double* H, int ldf, int k,
                           double* scratch, double* col_r, double* col_a, double* out2, int num_cus, hipStream_t st);
 // sparse: the segments of CSC(A) read-only (the piece buffer is part of scratch); G = W'W (ldg doubles per row); col_merged: the sum
@@ -515,6 +517,21 @@ int launch_kl_divergence(const SegPlan& sp, const i64* colptr, const double* val
                          const double* sums_x, double* divpart, double* out4, double* host_out, hipStream_t st);
 int kl_sums_blocks(i64 N);
 int launch_kl_factor_sums(const double* X, int k, i64 N, double* part, double* out, hipStream_t st);
+
+// kl_dense.hip: the same iteration on a dense stored matrix, one streaming read per half-iteration, k <= 128.  The
+// matrix is `rows` x `cols` as stored (A for the H step, the stored transpose for the W step; ld elements per column); R (KP x
+// rows, only read) the factor of its rows, X (KP x cols) the factor of its columns, both with pitch KP = kp_of(k).
+// launch_kl_dense_step: per entry q = a / max(r_i . x_j, 2^-23), num_j += q r_i on the fp64 matrix cores, then launch_kl_step's
+// update of X in place.  launch_kl_dense_divergence: launch_kl_divergence's four numbers over every stored entry.  Matrix rows /
+// columns past rows / cols and factor rows >= k are not relied on; X's are written as zeros.  scratch: kl_dense_scratch_elems
+// doubles.  launch_kl_dense_negative: *flag (an int in device memory, zeroed by the caller) becomes 1 if a stored value is < 0.
+// Fixed summation orders throughout: the same bits on every run.
+size_t kl_dense_scratch_elems(i64 rows, i64 cols, int k, int num_cus);
+int launch_kl_dense_step(const void* A, int storage, i64 ld, i64 rows, i64 cols, const double* R, double* X, int k, const double* base, int unit,
+                         double l1, double l2, int flush, double* scratch, int num_cus, hipStream_t st);
+int launch_kl_dense_divergence(const void* A, int storage, i64 ld, i64 rows, i64 cols, const double* R, const double* X, int k, const double* sums_r,
+                               const double* sums_x, double* scratch, double* out4, double* host_out, int num_cus, hipStream_t st);
+int launch_kl_dense_negative(const void* A, int storage, i64 ld, i64 rows, i64 cols, int* flag, hipStream_t st);
 
 // assign.hip: labels / memberships of the columns of H and the top terms of the columns of W, the factors fp64 or fp32 (DT_*) in
 // their k-contiguous layout: column c of H at H + c * ldc, row i of W at W + i * ld (elements).  The host functions' comparisons in

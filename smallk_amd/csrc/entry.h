@@ -119,6 +119,16 @@ inline int check_penalties(const std::string& w, double alpha_w, double alpha_h,
     return SMK_OK;
 }
 
+// what every entry of the two KL-divergence drivers (kl.cpp, kl_dense.cpp) checks first
+inline int kl_args(const std::string& w, const smk_matrix* a, int k, const void* W, int dtW, const void* H, int dtH)
+{
+    if (int rc = require_init()) return rc;
+    if (!a || !W || !H) { set_error(w + ": null argument"); return SMK_BAD_PARAM; }
+    if (k < 1) { set_error(w + ": k < 1"); return SMK_BAD_PARAM; }
+    if (k > a->m || k > a->n_global) { set_error(w + ": k exceeds min(m, n)"); return SMK_BAD_PARAM; }
+    return check_factor_dtypes(w, "W and H", dtW, dtH);
+}
+
 // ... and what they weigh: the l1 and l2 terms of H scale with m, those of W with n (scikit-learn's convention on X = A')
 struct Penalties {
     double l1h, l2h, l1w, l2w;

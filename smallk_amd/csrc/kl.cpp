@@ -141,16 +141,7 @@ static int kl_loop(KlRun& r, const smk_kl_options& o, smk_kl_stats* stats)
     return 0;
 }
 
-// what both entries check first
-static int kl_args(const std::string& w, const smk_matrix* a, int k, const void* W, int dtW, const void* H, int dtH)
-{
-    if (int rc = require_init()) return rc;
-    if (!a || !W || !H) { set_error(w + ": null argument"); return SMK_BAD_PARAM; }
-    if (k < 1) { set_error(w + ": k < 1"); return SMK_BAD_PARAM; }
-    if (k > a->m || k > a->n_global) { set_error(w + ": k exceeds min(m, n)"); return SMK_BAD_PARAM; }
-    return check_factor_dtypes(w, "W and H", dtW, dtH);
-}
-
+// (what both entries check first: entry.h's kl_args, shared with kl_dense.cpp)
 static int kl_supported(const std::string& w, const smk_matrix* a, int k)
 {
     if (k > 128) { set_error(w + ": k > 128 is not supported yet"); return SMK_UNSUPPORTED; }

@@ -255,7 +255,7 @@ static int matrix_make_transpose(smk_matrix* a)
 // and hipHostRegister of each chunk of the caller's buffer (52 GB/s).  Both slower, both removed.
 int smk_matrix_upload_f64(smk_matrix* a, const double* host, int64_t ld)
 {
-    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; }     // new contents: scale, column spread and norms are measured again on first use
+    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; a->kl_negative = -1; }     // new contents: scale, column spread and norms are measured again on first use
     if (!a || !host || ld < a->m || a->sparse) return SMK_BAD_PARAM;
     const size_t budget = (size_t)64 << 20;   // staging bytes
     i64 chunk = (i64)(budget / ((size_t)a->m * sizeof(double)));
@@ -282,7 +282,7 @@ int smk_matrix_upload_f64(smk_matrix* a, const double* host, int64_t ld)
 
 int smk_matrix_fill_uniform(smk_matrix* a, uint64_t seed)
 {
-    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; }
+    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; a->kl_negative = -1; }
     if (!a || a->sparse) return SMK_BAD_PARAM;
     int rc = launch_fill_uniform(a->A, a->storage, a->ldA, a->m, a->n, a->ldA, a->colsA, 0, a->c0, a->m, seed,
                                  a->storage == SMK_STORE_BF16 ? 1 : 0, ctx().stream);
@@ -295,7 +295,7 @@ int smk_matrix_fill_uniform(smk_matrix* a, uint64_t seed)
 
 int smk_matrix_fill_planted(smk_matrix* a, uint64_t seed, int kstar, double threshold, double noise)
 {
-    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; }
+    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; a->kl_negative = -1; }
     if (!a || a->sparse || kstar < 1 || kstar > 4096 || !(threshold >= 0.0 && threshold < 1.0) || !(noise >= 0.0)) return SMK_BAD_PARAM;
     int rc = launch_fill_planted(a->A, a->storage, a->ldA, a->m, a->n, a->ldA, a->colsA, a->c0, a->m, seed, kstar, threshold,
                                  noise, a->storage == SMK_STORE_BF16 ? 1 : 0, ctx().stream);
@@ -336,7 +336,7 @@ int smk_matrix_download_f64(const smk_matrix* a, double* host, int64_t ld)
 // source (adopt.hip) instead of a conversion pass and a transpose pass that reads A again.
 int smk_matrix_adopt_device(smk_matrix* a, const void* src, int dtype, int64_t row_stride, int64_t col_stride, void* stream)
 {
-    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; }     // new contents, as in smk_matrix_upload_f64
+    if (a) { a->ascale = 0.f; a->col_spread_log2 = -1; a->colnorm_max = a->rownorm_max = -1.0; a->kl_negative = -1; }     // new contents, as in smk_matrix_upload_f64
     if (!a || a->sparse) return SMK_BAD_PARAM;
     int rc = check_device_view(src, dtype, a->m, a->n, row_stride, col_stride, false, "smk_matrix_adopt_device");
     if (rc) return rc;

@@ -391,8 +391,8 @@ __global__ __launch_bounds__(256) void residual_sparse_finish_kernel(const doubl
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 // spans of row tiles per column tile: enough workgroups for four per CU, never more than 32 (the partials are [S][n] doubles;
-// one per row tile would be 2 GB at a 1 M x 1 M matrix's shape), every span non-empty
-static void residual_dense_shape(i64 m, i64 n, int num_cus, i64* row_tiles, i64* col_tiles, i64* tps, int* S)
+// one per row tile would be 2 GB at a 1 M x 1 M matrix's shape), every span non-empty.  (kl_dense.hip cuts its launches by the same rule.)
+void residual_dense_shape(i64 m, i64 n, int num_cus, i64* row_tiles, i64* col_tiles, i64* tps, int* S)
 {
     const i64 rt = (m + RES_T - 1) / RES_T, ctl = (n + RES_T - 1) / RES_T;
     i64 want = ((i64)4 * num_cus + ctl - 1) / ctl;

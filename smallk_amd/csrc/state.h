@@ -77,7 +77,8 @@ struct smk_matrix {
     // merged entries.  Looked up once: a sparse matrix does not change after creation.
     mutable int dup_state = -1;
     mutable double* dup_colsq = nullptr;
-    // sparse A, kl.cpp: whether a stored value is negative (the KL divergence refuses such a matrix): -1 = not yet looked, 0 = no, 1 = yes
+    // kl.cpp (sparse A) / kl_dense.cpp (dense A; reset with new contents): whether a stored value is negative (the KL divergence
+    // refuses such a matrix): -1 = not yet looked, 0 = no, 1 = yes
     mutable int kl_negative = -1;
     mutable smk::Owned own;                          // every device block above (the lazily built stored transpose included); the blocked CSC and the segment plans free themselves
 };

@@ -84,8 +84,8 @@ class Residual:
 
 @dataclass
 class KlDivergence:
-    """D(A || W H) of ``SparseMatrix.kl_divergence`` and its two large terms: sum a log(a / w_i . h_j) over the stored entries
-    and sum WH (D = a_log_ratio - sum a + sum_wh)."""
+    """D(A || W H) of ``SparseMatrix.kl_divergence`` / ``DenseMatrix.kl_divergence`` and its two large terms: sum a log(a / w_i . h_j)
+    over the stored entries and sum WH (D = a_log_ratio - sum a + sum_wh)."""
     divergence: float
     a_log_ratio: float
     sum_wh: float
@@ -346,6 +346,26 @@ class DenseMatrix:
                                                 _p(col) if per_column else None), "smk_matrix_residual")
         return Residual(r.value, a.value, col)
 
+    def kl_divergence(self, W, H) -> KlDivergence:
+        """The generalised Kullback-Leibler divergence D(A || W H) = sum a log(a / w_i . h_j) - sum a + sum WH over every entry
+        of the stored A (the terms of a = 0 are sum WH's alone), computed on the device in fp64 in one streaming read of A (dot
+        products below 2^-23 count as 2^-23, as in scikit-learn).  W (height, k) and H (k, ncols): both numpy arrays, or both
+        float64 / float32 torch tensors in GPU memory (any strides).  A single-copy matrix is served."""
+        return self._kl_divergence("smk_matrix_kl_divergence_dense_device", W, H)
+
+    def _kl_divergence(self, entry, W, H) -> KlDivergence:
+        on_device, k = _residual_factors(W, H, self.height, self.ncols, "kl_divergence")
+        if not on_device:
+            import torch
+            dev = torch.device("cuda", L.lib().smk_current_device())
+            W = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64)).to(dev)
+            H = torch.from_numpy(np.ascontiguousarray(H, dtype=np.float64)).to(dev)
+        wp, wt, (wrs, wcs) = _tensor_view(W, "kl_divergence(W)", kinds="factor")
+        hp, ht, (hrs, hcs) = _tensor_view(H, "kl_divergence(H)", kinds="factor")
+        out = (C.c_double * 3)()
+        L.check(getattr(L.lib(), entry)(self._h, k, wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), out), entry)
+        return KlDivergence(out[0], out[1], out[2])
+
     def svd(self, k, *, oversample=8, power_iters=2, seed=0, omega=None):
         """The k leading singular triplets of the stored A, computed on the device in fp64 (randomised range finder with
         ``power_iters`` power iterations on min(k + oversample, m, n) columns; k + oversample <= 128): ``(U, S, V)`` with U (m, k)
@@ -463,18 +483,7 @@ class SparseMatrix(DenseMatrix):
         """The generalised Kullback-Leibler divergence D(A || W H) = sum a log(a / w_i . h_j) - sum a + sum WH over the stored
         entries of A, computed on the device in fp64 (dot products below 2^-23 count as 2^-23, as in scikit-learn).  W (height, k)
         and H (k, ncols): both numpy arrays, or both float64 / float32 torch tensors in GPU memory (any strides)."""
-        on_device, k = _residual_factors(W, H, self.height, self.ncols, "kl_divergence")
-        if not on_device:
-            import torch
-            dev = torch.device("cuda", L.lib().smk_current_device())
-            W = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64)).to(dev)
-            H = torch.from_numpy(np.ascontiguousarray(H, dtype=np.float64)).to(dev)
-        wp, wt, (wrs, wcs) = _tensor_view(W, "kl_divergence(W)", kinds="factor")
-        hp, ht, (hrs, hcs) = _tensor_view(H, "kl_divergence(H)", kinds="factor")
-        out = (C.c_double * 3)()
-        L.check(L.lib().smk_matrix_kl_divergence_device(self._h, k, wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), out),
-                "smk_matrix_kl_divergence_device")
-        return KlDivergence(out[0], out[1], out[2])
+        return self._kl_divergence("smk_matrix_kl_divergence_device", W, H)
 
 
 def load_matrix_market(path):
@@ -827,7 +836,7 @@ def _penalised_fit(what, kind, entry, stats_type, last_two, result_type, A, W0, 
 
 
 def _last_profile(entry):
-    """the two counters ``entry`` (smk_cd_last_profile / smk_kl_last_profile) reports for this thread's last run"""
+    """the two counters ``entry`` (smk_cd_last_profile / smk_kl_last_profile / smk_kl_dense_last_profile) reports for this thread's last run"""
     p, s = C.c_int(0), C.c_int(0)
     L.check(getattr(L.lib(), entry)(C.byref(p), C.byref(s)), entry)
     return p.value, s.value
@@ -897,6 +906,21 @@ def nmf_kl(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, ma
 def kl_last_profile():
     """(sweeps over the stored entries that updated a factor, sweeps that formed the divergence) of this thread's last ``nmf_kl``"""
     return _last_profile("smk_kl_last_profile")
+
+
+def nmf_kl_dense(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True, inplace=False) -> KlResult:
+    """``nmf_kl`` on a resident ``DenseMatrix`` A (m, n) -- counts or intensities without many zeros: a spectrogram, an image, word
+    counts over a small vocabulary.  The same objective, arguments, stopping rule and result as ``nmf_kl``; the sums run over every
+    entry of the stored A (bf16 or fp32 storage, widened exactly), so on the same data the two agree up to summation order.  Each
+    half-iteration is one streaming read of one stored copy (A for H, the stored transpose for W), hence a ``single_copy`` matrix
+    serves ``update_W=False`` only.  A must store no negative value.  (The estimator ``NMF`` takes sparse X for this loss.)"""
+    return _penalised_fit("nmf_kl_dense", "DenseMatrix", "smk_nmf_kl_dense_device", L.KlStats, lambda st: (st.error_init, st.error), KlResult,
+                          A, W0, H0, alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio, tol=tol, max_iter=max_iter, update_W=update_W, inplace=inplace)
+
+
+def kl_dense_last_profile():
+    """(streaming passes over A or A' that updated a factor, passes that formed the divergence) of this thread's last ``nmf_kl_dense``"""
+    return _last_profile("smk_kl_dense_last_profile")
 
 
 def cd_sweep(G, R, X, l1=0.0, l2=0.0):
