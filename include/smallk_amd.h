@@ -363,6 +363,33 @@ int smk_kl_dense_last_profile(int* matrix_passes, int* divergence_passes);
  * smk_matrix_residual on A at the same rank: one product over the same bytes, the floor to compare with */
 int smk_kl_dense_step_time(const smk_matrix* a, int which, int k, int reps, double* ms);
 
+/* ---- NMF of a resident DENSE matrix under another beta-divergence, by multiplicative updates -------------------
+ * smk_nmf_kl_dense_device for any beta >= 0 other than 2: scikit-learn's NMF(solver="mu", beta_loss=beta) on X = A', beta = 0 being
+ * "itakura-saito" -- the loss of a power spectrogram.  Options, orientation, penalties, stopping rule, fold-in and results are
+ * smk_nmf_kl_device's; stats->error = sqrt(2 D_beta(A || W H)).  Per entry of the stored A with d = w_i . h_j the numerator takes
+ * a d^(beta - 2) and the denominator d^(beta - 1) (d clamped at 2^-23 from below where the exponent is negative), the quotient of
+ * the two sums is raised to gamma = 1 / (2 - beta) below beta = 1, 1 / (beta - 1) above 2 and 1 between, and factor entries below
+ * 2^-52 become zero when beta < 1.  Each half-iteration is one streaming read of one stored copy and forms both sums on the matrix
+ * cores; beta = 0 costs divisions only, any other beta one double-precision pow per entry and half-iteration (DESIGN.md 21 has
+ * the measured cost).  beta = 1 forwards to smk_nmf_kl_dense_device: the same bits.  The same bits on every run.
+ * SMK_BAD_PARAM: as smk_nmf_kl_dense_device, a beta that is negative or not finite, a negative stored value, and for beta <= 0 a
+ * stored zero (add a small value to the matrix, or use a positive beta).  SMK_UNSUPPORTED: beta = 2 (the Frobenius solvers:
+ * smk_nmf_run, smk_nmf_cd_device), a sparse matrix, k > 128, a column shard, a single-copy matrix when update_w != 0.  On an error
+ * W and H are untouched. */
+int smk_nmf_beta_dense_device(const smk_matrix* a, int k, double beta, const smk_kl_options* o, void* W, int dtW, int64_t rsW,
+                              int64_t csW, void* H, int dtH, int64_t rsH, int64_t csH, void* stream, smk_kl_stats* stats);
+/* out[0] = D_beta(A || W H) (not clamped) over the entries with a > 2^-23, then the sums it is formed from.  beta = 0: out[1] =
+ * sum a / d, out[2] = sum log(a / d), out[3] = m n, D = out[1] - out[3] - out[2].  Other beta: out[1] = sum a^beta, out[2] =
+ * sum a d^(beta - 1), out[3] = sum d^beta over every entry, D = (out[1] - beta out[2] + (beta - 1) out[3]) / (beta (beta - 1)).
+ * beta = 1: smk_matrix_kl_divergence_dense_device's three numbers and out[3] = 0.  One read of A; a single copy is served. */
+int smk_matrix_beta_divergence_dense_device(const smk_matrix* a, int k, double beta, const void* W, int dtW, int64_t rsW,
+                                            int64_t csW, const void* H, int dtH, int64_t rsH, int64_t csH, void* stream, double* out);
+/* diagnostics of the calling thread's last smk_nmf_beta_dense_device call (beta != 1), as smk_kl_dense_last_profile */
+int smk_beta_dense_last_profile(int* matrix_passes, int* divergence_passes);
+/* measurement (tools/beta_dense_rate.py), as smk_kl_dense_step_time.  which: 0 the H step with its finish (over A), 1 the W step
+ * (over the stored transpose), 2 the KL step of kl_dense.hip on the same matrix and rank, 3 the residual pass.  beta != 1 */
+int smk_beta_dense_step_time(const smk_matrix* a, int which, int k, double beta, int reps, double* ms);
+
 /* ---- labels, memberships, top terms and fold-in, on the device (the device twins of smk_compute_assignments,
  * smk_compute_fuzzy_assignments and smk_top_terms below: the same comparisons in the same order, so the same integers and the
  * same membership bits; no k <= n and no height >= width requirement) -----------------------------------------------------

@@ -178,6 +178,10 @@ SYMBOLS = {
     "smk_matrix_kl_divergence_dense_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _dp]),
     "smk_kl_dense_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "smk_kl_dense_step_time": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp]),
+    "smk_nmf_beta_dense_device": (C.c_int, [_vp, C.c_int, C.c_double, C.POINTER(KlOptions), _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, C.POINTER(KlStats)]),
+    "smk_matrix_beta_divergence_dense_device": (C.c_int, [_vp, C.c_int, C.c_double, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _dp]),
+    "smk_beta_dense_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "smk_beta_dense_step_time": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_int, _dp]),
     "smk_labels_device": (C.c_int, [_vp, C.c_int, _i64, _i64, C.c_int, _i64, _vp, _vp, _vp]),
     "smk_top_terms_device": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, _vp, _vp]),
     "smk_solver_labels": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),

@@ -524,7 +524,7 @@ int launch_kl_factor_sums(const double* X, int k, i64 N, double* part, double* o
 // launch_kl_dense_step: per entry q = a / max(r_i . x_j, 2^-23), num_j += q r_i on the fp64 matrix cores, then launch_kl_step's
 // update of X in place.  launch_kl_dense_divergence: launch_kl_divergence's four numbers over every stored entry.  Matrix rows /
 // columns past rows / cols and factor rows >= k are not relied on; X's are written as zeros.  scratch: kl_dense_scratch_elems
-// doubles.  launch_kl_dense_negative: *flag (an int in device memory, zeroed by the caller) becomes 1 if a stored value is < 0.
+// doubles.  launch_kl_dense_negative: *flag (an int in device memory, zeroed by the caller) gains bit 0 if a stored value is < 0 and bit 1 if one is <= 0.
 // Fixed summation orders throughout: the same bits on every run.
 size_t kl_dense_scratch_elems(i64 rows, i64 cols, int k, int num_cus);
 int launch_kl_dense_step(const void* A, int storage, i64 ld, i64 rows, i64 cols, const double* R, double* X, int k, const double* base, int unit,
@@ -532,6 +532,19 @@ int launch_kl_dense_step(const void* A, int storage, i64 ld, i64 rows, i64 cols,
 int launch_kl_dense_divergence(const void* A, int storage, i64 ld, i64 rows, i64 cols, const double* R, const double* X, int k, const double* sums_r,
                                const double* sums_x, double* scratch, double* out4, double* host_out, int num_cus, hipStream_t st);
 int launch_kl_dense_negative(const void* A, int storage, i64 ld, i64 rows, i64 cols, int* flag, hipStream_t st);
+
+// beta_dense.hip: the multiplicative update of another beta-divergence on a dense stored matrix, beta >= 0 other than
+// 1 and 2, k <= 128, in kl_dense.hip's frame and with its arguments.  launch_beta_dense_step: per entry qn = a dn^(beta - 2) and qd =
+// dd^(beta - 1) (d = r_i . x_j; dn clamped at 2^-23 from below when beta < 2, dd when beta < 1), num_j += qn r_i and den_j += qd r_i
+// on the fp64 matrix cores, then x_j[t] *= (num / (den + l1 + l2 x_j[t]))^gamma in place (kl_dev.h: beta_update).
+// launch_beta_dense_divergence: out4 (and host_out when not null, pinned host memory) = D and the three sums it is formed from --
+// beta = 0: sum a / d, sum log(a / d), rows * cols; else sum a^beta, sum a d^(beta - 1), sum d^beta.  scratch:
+// beta_dense_scratch_elems doubles.  Fixed summation orders throughout: the same bits on every run.
+size_t beta_dense_scratch_elems(i64 rows, i64 cols, int k, int num_cus);
+int launch_beta_dense_step(const void* A, int storage, i64 ld, i64 rows, i64 cols, const double* R, double* X, int k, double beta, double l1,
+                           double l2, int flush, double* scratch, int num_cus, hipStream_t st);
+int launch_beta_dense_divergence(const void* A, int storage, i64 ld, i64 rows, i64 cols, const double* R, const double* X, int k, double beta,
+                                 double* scratch, double* out4, double* host_out, int num_cus, hipStream_t st);
 
 // assign.hip: labels / memberships of the columns of H and the top terms of the columns of W, the factors fp64 or fp32 (DT_*) in
 // their k-contiguous layout: column c of H at H + c * ldc, row i of W at W + i * ld (elements).  The host functions' comparisons in

@@ -129,6 +129,9 @@ inline int kl_args(const std::string& w, const smk_matrix* a, int k, const void*
     return check_factor_dtypes(w, "W and H", dtW, dtH);
 }
 
+// kl_dense.cpp: refuses a dense matrix that stores a negative value (SMK_BAD_PARAM); fills a->kl_negative and a->kl_zero once per contents
+int kl_dense_sign_check(const smk_matrix* a, const std::string& w);
+
 // ... and what they weigh: the l1 and l2 terms of H scale with m, those of W with n (scikit-learn's convention on X = A')
 struct Penalties {
     double l1h, l2h, l1w, l2w;

@@ -27,8 +27,8 @@ struct KlDenseRun {
 static thread_local int g_kld_matrix_passes = 0, g_kld_divergence_passes = 0;
 
 // no stored value may be negative: looked up once per matrix by a reduction on the device (the matrix's contents change only
-// through upload / adopt / fill, which reset the record)
-static int kl_dense_sign_check(const smk_matrix* a, const std::string& w)
+// through upload / adopt / fill, which reset the record).  The same look records whether a zero is stored (beta_dense.cpp).
+int kl_dense_sign_check(const smk_matrix* a, const std::string& w)
 {
     static std::mutex mu;             // lazily built part of a shared, nominally const matrix (as kl.cpp's)
     std::lock_guard<std::mutex> lk(mu);
@@ -43,7 +43,8 @@ static int kl_dense_sign_check(const smk_matrix* a, const std::string& w)
         SMK_HIP(hipMemcpyAsync(&neg, flag, sizeof(int), hipMemcpyDeviceToHost, e.st));
         rc = e.sync();
         if (rc) return rc;
-        a->kl_negative = neg ? 1 : 0;
+        a->kl_zero = (neg >> 1) & 1;
+        a->kl_negative = neg & 1;
     }
     if (a->kl_negative == 1) { set_error(w + ": the matrix stores a negative value"); return SMK_BAD_PARAM; }
     return 0;

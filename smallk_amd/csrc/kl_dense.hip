@@ -249,7 +249,7 @@ __global__ __launch_bounds__(1024) void kl_dense_total_kernel(const double* __re
     }
 }
 
-// is a stored value negative?  A workgroup walks columns, its threads the rows of a column; only rows < m and columns < n are read
+// is a stored value negative (bit 0 of *flag), is one zero or negative (bit 1: what beta <= 0 refuses, beta_dense.cpp)?  A workgroup walks columns, its threads the rows of a column; only rows < m and columns < n are read
 template <int EBYTES>
 __global__ __launch_bounds__(256) void kl_dense_negative_kernel(const unsigned char* __restrict__ A, i64 lda_bytes, i64 m, i64 n, int* flag)
 {
@@ -260,10 +260,11 @@ __global__ __launch_bounds__(256) void kl_dense_negative_kernel(const unsigned c
             float v;
             if constexpr (EBYTES == 2) v = bf16_bits_to_f32(((const unsigned short*)col)[r]);
             else v = ((const float*)col)[r];
-            if (v < 0.f) found = 1;
+            if (v < 0.f) found |= 1;
+            if (!(v > 0.f)) found |= 2;
         }
     }
-    if (found) atomicOr(flag, 1);
+    if (found) atomicOr(flag, found);
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------

@@ -80,6 +80,9 @@ struct smk_matrix {
     // kl.cpp (sparse A) / kl_dense.cpp (dense A; reset with new contents): whether a stored value is negative (the KL divergence
     // refuses such a matrix): -1 = not yet looked, 0 = no, 1 = yes
     mutable int kl_negative = -1;
+    // dense A, beta_dense.cpp: whether a stored value is zero or negative (beta <= 0 refuses such a matrix); written by the look that
+    // fills kl_negative and valid while kl_negative >= 0, so every reset of that record resets this one
+    mutable int kl_zero = 0;
     mutable smk::Owned own;                          // every device block above (the lazily built stored transpose included); the blocked CSC and the segment plans free themselves
 };
 

@@ -96,6 +96,21 @@ class KlDivergence:
         return math.sqrt(2.0 * max(self.divergence, 0.0))
 
 
+@dataclass
+class BetaDivergence:
+    """D_beta(A || W H) of ``DenseMatrix.beta_divergence`` and the sums it is formed from.  beta = 0: (sum a / d, sum log(a / d),
+    m n) with D = sums[0] - sums[2] - sums[1]; beta = 1: (sum a log(a / d), sum WH, 0); any other beta: (sum a^beta,
+    sum a d^(beta - 1), sum d^beta) with D = (sums[0] - beta sums[1] + (beta - 1) sums[2]) / (beta (beta - 1))."""
+    beta: float
+    divergence: float
+    sums: tuple
+
+    @property
+    def error(self) -> float:
+        """sqrt(2 max(D, 0)): scikit-learn's ``reconstruction_err_`` for this loss"""
+        return math.sqrt(2.0 * max(self.divergence, 0.0))
+
+
 def _residual_factors(W, H, height, ncols, what):
     """The checks of ``DenseMatrix.residual`` made before the library is called: both factors on the host (array-likes of
     numbers) or both torch tensors, 2-D, W (height, k) and H (k, ncols) with k >= 1.  Returns (on_device, k)."""
@@ -352,6 +367,26 @@ class DenseMatrix:
         products below 2^-23 count as 2^-23, as in scikit-learn).  W (height, k) and H (k, ncols): both numpy arrays, or both
         float64 / float32 torch tensors in GPU memory (any strides).  A single-copy matrix is served."""
         return self._kl_divergence("smk_matrix_kl_divergence_dense_device", W, H)
+
+    def beta_divergence(self, W, H, beta_loss) -> "BetaDivergence":
+        """The beta-divergence D_beta(A || W H) of ``nmf_beta_dense`` (``beta_loss`` as there) over the entries of the stored A with
+        a > 2^-23, computed on the device in fp64 in one streaming read of A, with the three sums it is formed from.  W and H as in
+        ``kl_divergence``.  A single-copy matrix is served."""
+        beta = _beta_of("beta_divergence", beta_loss)
+        if isinstance(self, SparseMatrix):
+            raise ValueError("beta_divergence: takes a resident DenseMatrix (SparseMatrix has kl_divergence)")
+        on_device, k = _residual_factors(W, H, self.height, self.ncols, "beta_divergence")
+        if not on_device:
+            import torch
+            dev = torch.device("cuda", L.lib().smk_current_device())
+            W = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64)).to(dev)
+            H = torch.from_numpy(np.ascontiguousarray(H, dtype=np.float64)).to(dev)
+        wp, wt, (wrs, wcs) = _tensor_view(W, "beta_divergence(W)", kinds="factor")
+        hp, ht, (hrs, hcs) = _tensor_view(H, "beta_divergence(H)", kinds="factor")
+        out = (C.c_double * 4)()
+        entry = "smk_matrix_beta_divergence_dense_device"
+        L.check(getattr(L.lib(), entry)(self._h, k, C.c_double(beta), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), out), entry)
+        return BetaDivergence(beta, out[0], (out[1], out[2], out[3]))
 
     def _kl_divergence(self, entry, W, H) -> KlDivergence:
         on_device, k = _residual_factors(W, H, self.height, self.ncols, "kl_divergence")
@@ -808,9 +843,11 @@ def transform(A, W, *, H0=None):
         solver.close()
 
 
-def _penalised_fit(what, kind, entry, stats_type, last_two, result_type, A, W0, H0, *, alpha_W, alpha_H, l1_ratio, tol, max_iter, update_W, inplace):
+def _penalised_fit(what, kind, entry, stats_type, last_two, result_type, A, W0, H0, *, alpha_W, alpha_H, l1_ratio, tol, max_iter, update_W, inplace,
+                   before_options=()):
     """What ``nmf_cd`` and ``nmf_kl`` share: the checks made before the library is called, the start as tensors on the GPU, the options,
-    the C entry ``entry`` with its statistics struct and the result as ``result_type(W, H, n_iter, converged, *last_two(stats))``."""
+    the C entry ``entry`` with its statistics struct and the result as ``result_type(W, H, n_iter, converged, *last_two(stats))``.
+    ``before_options``: what the entry takes between k and the options (``nmf_beta_dense``: beta)."""
     if not isinstance(A, DenseMatrix):
         raise ValueError(f"{what}: A must be a resident {kind}, got {type(A).__name__}")
     on_device, k = _residual_factors(W0, H0, A.height, A.ncols, what)
@@ -829,7 +866,7 @@ def _penalised_fit(what, kind, entry, stats_type, last_two, result_type, A, W0, 
     wp, wt, (wrs, wcs) = _tensor_view(W, f"{what}(W0)", kinds="factor")
     hp, ht, (hrs, hcs) = _tensor_view(H, f"{what}(H0)", kinds="factor")
     st = stats_type()
-    L.check(getattr(L.lib(), entry)(A._h, k, C.byref(o), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), C.byref(st)), entry)
+    L.check(getattr(L.lib(), entry)(A._h, k, *before_options, C.byref(o), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), C.byref(st)), entry)
     if not on_device:
         W, H = W.cpu().numpy(), H.cpu().numpy()
     return result_type(W, H, st.iterations, bool(st.converged), *last_two(st))
@@ -921,6 +958,48 @@ def nmf_kl_dense(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e
 def kl_dense_last_profile():
     """(streaming passes over A or A' that updated a factor, passes that formed the divergence) of this thread's last ``nmf_kl_dense``"""
     return _last_profile("smk_kl_dense_last_profile")
+
+
+def _beta_of(what, beta_loss):
+    """``beta_loss`` as a number: scikit-learn's names "itakura-saito" (0) and "kullback-leibler" (1), or a finite number >= 0 other
+    than 2 (the Frobenius norm has solvers of its own).  Raised here, before any library call."""
+    names = {"itakura-saito": 0.0, "kullback-leibler": 1.0}
+    if isinstance(beta_loss, str):
+        if beta_loss == "frobenius":
+            raise ValueError(f"{what}: beta_loss='frobenius' (beta = 2) is what nmf_cd and NmfSolver minimise")
+        if beta_loss not in names:
+            raise ValueError(f"{what}: beta_loss must be one of {sorted(names)} or a number, got {beta_loss!r}")
+        return names[beta_loss]
+    if isinstance(beta_loss, bool) or not isinstance(beta_loss, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{what}: beta_loss must be one of {sorted(names)} or a number, got {beta_loss!r}")
+    beta = float(beta_loss)
+    if not math.isfinite(beta) or beta < 0.0:
+        raise ValueError(f"{what}: beta_loss must be finite and >= 0, got {beta_loss!r}")
+    if beta == 2.0:
+        raise ValueError(f"{what}: beta_loss=2 is the Frobenius norm, which nmf_cd and NmfSolver minimise")
+    return beta
+
+
+def nmf_beta_dense(A, W0, H0, *, beta_loss, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True, inplace=False) -> KlResult:
+    """``nmf_kl_dense`` under another beta-divergence -- scikit-learn's ``solver="mu"`` with ``beta_loss`` = "itakura-saito" (beta = 0,
+    the scale-invariant loss a power spectrogram is fitted under), "kullback-leibler" (beta = 1: ``nmf_kl_dense`` itself, the same
+    bits) or any number >= 0 other than 2 -- on a resident ``DenseMatrix`` A (m, n).  Arguments, orientation, penalties, stopping rule
+    and result are ``nmf_kl``'s; ``error`` is sqrt(2 D_beta(A || W H)).  Each half-iteration is one streaming read of one stored
+    copy, hence a ``single_copy`` matrix serves ``update_W=False`` only.  A must store no negative value and, for beta <= 0, no zero
+    (add a small value first).  beta = 0 costs divisions only; any other beta pays a double-precision power per entry and
+    half-iteration (DESIGN.md 21 has the measured cost)."""
+    beta = _beta_of("nmf_beta_dense", beta_loss)
+    if isinstance(A, SparseMatrix):
+        raise ValueError(f"nmf_beta_dense: A must be a resident DenseMatrix, got {type(A).__name__}")
+    return _penalised_fit("nmf_beta_dense", "DenseMatrix", "smk_nmf_beta_dense_device", L.KlStats, lambda st: (st.error_init, st.error), KlResult,
+                          A, W0, H0, alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio, tol=tol, max_iter=max_iter, update_W=update_W, inplace=inplace,
+                          before_options=(C.c_double(beta),))
+
+
+def beta_dense_last_profile():
+    """(streaming passes over A or A' that updated a factor, passes that formed the divergence) of this thread's last ``nmf_beta_dense``
+    (beta != 1)"""
+    return _last_profile("smk_beta_dense_last_profile")
 
 
 def cd_sweep(G, R, X, l1=0.0, l2=0.0):
