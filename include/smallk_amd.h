@@ -343,6 +343,38 @@ int smk_kl_last_profile(int* entry_passes, int* divergence_passes);
  * the same plan, rank and gathered factor as 0 / 1: one gather of the same rows without the dot product and the quotient */
 int smk_kl_step_time(const smk_matrix* a, int which, int k, int reps, double* ms);
 
+/* ---- NMF fitted to the stored entries of a sparse matrix only: masked coordinate descent --------------------------
+ * An entry that the matrix does not store is "not measured" (a missing rating, a clipped bin, an entry held out on purpose), not 0.
+ * Omega = the stored entries (i, j, a), stored zeros included.  Minimises  1/2 sum over Omega of (a - w_i . h_j)^2  plus the penalty
+ * terms of smk_nmf_cd_device, with its orientation, options, penalty scaling and stopping rule.  One iteration sweeps H, then W with
+ * the new H.  The H sweep takes every column j by itself and t = 0 .. k-1 in order, the residuals r = a - w_i . h_j of the column's
+ * entries kept current:  grad = -sum W[i, t] r + l1 + l2 H[t, j],  hess = sum W[i, t]^2 + l2  (sums over the stored entries of column
+ * j);  violation += |H[t, j] == 0 ? min(0, grad) : grad|;  unless hess == 0, H[t, j] = max(H[t, j] - grad / hess, 0).  A column
+ * without stored entries follows the same formulas.  The W sweep is the same over the rows.  When every entry is stored this is
+ * smk_nmf_cd_device's iteration up to rounding.  update_w = 0: W stays as given and only the H sweep repeats (fold-in of new
+ * columns).  stats->error = sqrt(sum over Omega of (a - w_i . h_j)^2) of the factors returned.  fp64, every sum in a fixed order: the
+ * same bits on every call.  The host reads the violation once per iteration.
+ * SMK_BAD_PARAM: a null pointer, k < 1, k > min(m, n), a negative alpha, l1_ratio outside [0, 1], tol < 0, max_iter < 1, a bad view.
+ * SMK_UNSUPPORTED: a dense matrix, k > 128, a column shard, a matrix that stores an entry twice (the mask is then not a set),
+ * SMK_SPMM_SEG_LEN above 64.  Negative stored values are served, as by smk_nmf_cd_device.  On an error W and H are untouched. */
+typedef struct smk_masked_stats { int iterations; int converged; double violation_init, violation, error; } smk_masked_stats;
+/* W (m x k) and H (k x ncols) are in/out views in device memory (SMK_DT_F64 / SMK_DT_F32, strides in elements, the caller's stream) */
+int smk_nmf_masked_device(const smk_matrix* a, int k, const smk_cd_options* o, void* W, int dtW, int64_t rsW, int64_t csW,
+                          void* H, int dtH, int64_t rsH, int64_t csH, void* stream, smk_masked_stats* stats);
+/* out3[0] = sum over the stored entries of `a` of (a - w_i . h_j)^2, out3[1] = that of a^2, out3[2] = their number, of the given
+ * factors (views as above, only read): the held-out score when `a` holds the entries withheld from the fit.  col_r / col_a (both or
+ * neither): ncols doubles each in device memory, the first two sums per column.  The error returns of smk_nmf_masked_device that apply */
+int smk_matrix_masked_residual_device(const smk_matrix* a, int k, const void* W, int dtW, int64_t rsW, int64_t csW,
+                                      const void* H, int dtH, int64_t rsH, int64_t csH, double* col_r, double* col_a, void* stream,
+                                      double* out3);
+/* diagnostics of the calling thread's last smk_nmf_masked_device call: sweeps over the stored entries that updated a factor, and
+ * sweeps that formed the residual */
+int smk_masked_last_profile(int* entry_sweeps, int* residual_sweeps);
+/* measurement (tools/masked_rate.py): the average time in ms of `reps` launches on synthetic factors of rank k.  which: 0 the H sweep
+ * (over CSC(A)), 1 the W sweep (over CSC(A')), 2 the H step of smk_nmf_kl_device on the same matrix and rank, 3 the plain gather product
+ * launch_spmm_seg on the same plan: one gather of the same rows without the coordinate chain */
+int smk_masked_step_time(const smk_matrix* a, int which, int k, int reps, double* ms);
+
 /* ---- the same iteration on a DENSE resident matrix: the sums run over every entry of the stored matrix (bf16 or fp32
  * storage, widened exactly; a stored 0 contributes nothing), so on the same data the result is smk_nmf_kl_device's up to summation
  * order.  Each half-iteration is one streaming read of one stored copy: A for H, the stored transpose for W; two chained fp64

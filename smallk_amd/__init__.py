@@ -10,7 +10,8 @@ from .solver import (DenseMatrix, SparseMatrix, NmfSolver, NmfResult, nmf, nmf_s
                      nnls_blockpivot, nmf_sharded, Comm, thread_context_begin, thread_context_end, trim_device_cache,
                      Residual, relative_error, labels_device, top_terms_device, transform, NNDSVD_VARIANTS, nmf_cd, cd_sweep, CdResult,
                      nmf_kl, nmf_kl_dense, kl_dense_last_profile, KlResult, KlDivergence,
-                     nmf_beta_dense, beta_dense_last_profile, BetaDivergence)
+                     nmf_beta_dense, beta_dense_last_profile, BetaDivergence,
+                     nmf_masked, masked_last_profile, MaskedResult, MaskedResidual, holdout_split)
 from .estimator import NMF
 from .api import SmallkAPI
 from . import hierclust
@@ -18,7 +19,7 @@ from . import flatclust
 from .hierclust import hier_nmf2, TreeResults, TreeRouter
 
 __all__ = ["DenseMatrix", "SparseMatrix", "nmf_sparse", "load_matrix_market", "NmfSolver", "NmfResult", "nmf", "nmf_device", "initialize", "finalize", "is_initialized",
-           "make_options", "uniform_host", "nnls_blockpivot", "nmf_sharded", "Comm", "set_stream", "thread_context_begin", "thread_context_end", "trim_device_cache", "SmallkAPI", "hierclust", "flatclust", "hier_nmf2", "TreeResults", "TreeRouter", "Residual", "relative_error", "labels_device", "top_terms_device", "transform", "NNDSVD_VARIANTS", "nmf_cd", "cd_sweep", "CdResult", "nmf_kl", "nmf_kl_dense", "kl_dense_last_profile", "KlResult", "KlDivergence", "nmf_beta_dense", "beta_dense_last_profile", "BetaDivergence", "NMF", "Vocabulary", "_lib"]
+           "make_options", "uniform_host", "nnls_blockpivot", "nmf_sharded", "Comm", "set_stream", "thread_context_begin", "thread_context_end", "trim_device_cache", "SmallkAPI", "hierclust", "flatclust", "hier_nmf2", "TreeResults", "TreeRouter", "Residual", "relative_error", "labels_device", "top_terms_device", "transform", "NNDSVD_VARIANTS", "nmf_cd", "cd_sweep", "CdResult", "nmf_kl", "nmf_kl_dense", "kl_dense_last_profile", "KlResult", "KlDivergence", "nmf_beta_dense", "beta_dense_last_profile", "BetaDivergence", "nmf_masked", "masked_last_profile", "MaskedResult", "MaskedResidual", "holdout_split", "NMF", "Vocabulary", "_lib"]
 
 
 def __getattr__(name):

@@ -87,6 +87,13 @@ class KlStats(C.Structure):
     _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("error_init", C.c_double), ("error", C.c_double)]
 
 
+class MaskedStats(C.Structure):
+    """struct smk_masked_stats: iterations run, whether the rule stopped them, the violation of iteration 1 and of the last one,
+    sqrt(sum over the stored entries of (a - w_i . h_j)^2) of the result."""
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("violation_init", C.c_double), ("violation", C.c_double),
+                ("error", C.c_double)]
+
+
 class TreeNodeInfo(C.Structure):
     """struct smk_tree_node: the scalar fields of TreeNode<T> (hierclust/include/tree.hpp:31-50)."""
     _fields_ = [("priority", C.c_double), ("parent", C.c_uint), ("left_child", C.c_uint), ("right_child", C.c_uint),
@@ -174,6 +181,10 @@ SYMBOLS = {
     "smk_matrix_kl_divergence_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _dp]),
     "smk_kl_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "smk_kl_step_time": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp]),
+    "smk_nmf_masked_device": (C.c_int, [_vp, C.c_int, C.POINTER(CdOptions), _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, C.POINTER(MaskedStats)]),
+    "smk_matrix_masked_residual_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _vp, _vp, _dp]),
+    "smk_masked_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "smk_masked_step_time": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp]),
     "smk_nmf_kl_dense_device": (C.c_int, [_vp, C.c_int, C.POINTER(KlOptions), _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, C.POINTER(KlStats)]),
     "smk_matrix_kl_divergence_dense_device": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _dp]),
     "smk_kl_dense_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -518,6 +518,24 @@ int launch_kl_divergence(const SegPlan& sp, const i64* colptr, const double* val
 int kl_sums_blocks(i64 N);
 int launch_kl_factor_sums(const double* X, int k, i64 N, double* part, double* out, hipStream_t st);
 
+// masked_cd.hip: coordinate descent on the stored entries only, k <= 128, factors KP x N with pitch KP = kp_of(k); the
+// plan's segments hold at most masked_seg_len_max() entries.  launch_masked_sweep: one sweep over the plan `sp` of one CSC (colptr /
+// val the arrays the plan was built on) -- per column, for t = 0 .. k-1 in order, grad = -sum_e G[i_e, t] r_e + l1 + l2 x[t], hess =
+// sum_e G[i_e, t]^2 + l2 over the stored entries e of the column with their residuals r_e = a_e - g_{i_e} . x kept current, |projected
+// gradient| added to the violation, x[t] = max(x[t] - grad / hess, 0) unless hess == 0; X in place, G only read.  res: sp.nnz doubles
+// (null if the plan has no long column); viol_partials: masked_sweep_partials(sp) doubles, for launch_cd_violation.  Rows >= k of G
+// and X are not relied on; X's are written as zeros.  launch_masked_residual: out3 (and host_out when not null, pinned host memory) =
+// sum over the stored entries of (a - g_i . x_j)^2, of a^2, and their number; col_r / col_a (both or neither; ncols doubles): the
+// first two per column; scratch: masked_residual_scratch_elems(sp) doubles.  Fixed summation orders throughout: the same bits on
+// every run.
+int masked_seg_len_max();
+int masked_sweep_partials(const SegPlan& sp);
+int launch_masked_sweep(const SegPlan& sp, const i64* colptr, const double* val, const double* G, double* X, int k, double l1, double l2,
+                        double* res, double* viol_partials, hipStream_t st);
+size_t masked_residual_scratch_elems(const SegPlan& sp);
+int launch_masked_residual(const SegPlan& sp, const i64* colptr, const double* val, const double* G, const double* X, int k, double* scratch,
+                           double* col_r, double* col_a, double* out3, double* host_out, hipStream_t st);
+
 // kl_dense.hip: the same iteration on a dense stored matrix, one streaming read per half-iteration, k <= 128.  The
 // matrix is `rows` x `cols` as stored (A for the H step, the stored transpose for the W step; ld elements per column); R (KP x
 // rows, only read) the factor of its rows, X (KP x cols) the factor of its columns, both with pitch KP = kp_of(k).

@@ -111,6 +111,27 @@ class BetaDivergence:
         return math.sqrt(2.0 * max(self.divergence, 0.0))
 
 
+@dataclass
+class MaskedResidual:
+    """What ``SparseMatrix.masked_residual`` returns: the sum over the stored entries of (a - w_i . h_j)^2, of a^2, and their number;
+    with ``per_column`` the first two per column (numpy arrays, or torch tensors on the GPU when the factors were tensors)."""
+    resid_sq: float
+    norm_sq: float
+    count: int
+    col_resid_sq: object = None
+    col_norm_sq: object = None
+
+    @property
+    def rmse(self) -> float:
+        """the root of the mean squared error over the stored entries; nan for a matrix without any"""
+        return math.sqrt(self.resid_sq / self.count) if self.count > 0 else math.nan
+
+    @property
+    def relative(self) -> float:
+        """sqrt(resid_sq / norm_sq); nan when every stored value is zero"""
+        return math.sqrt(self.resid_sq / self.norm_sq) if self.norm_sq > 0 else math.nan
+
+
 def _residual_factors(W, H, height, ncols, what):
     """The checks of ``DenseMatrix.residual`` made before the library is called: both factors on the host (array-likes of
     numbers) or both torch tensors, 2-D, W (height, k) and H (k, ncols) with k >= 1.  Returns (on_device, k)."""
@@ -501,6 +522,42 @@ class SparseMatrix(DenseMatrix):
     def from_scipy(cls, A):
         A = A.tocsc()
         return cls(A.data, A.indices, A.indptr, A.shape)
+
+    @classmethod
+    def from_observed(cls, X, mask):
+        """The matrix whose stored entries are the entries of the dense array ``X`` where the boolean array ``mask`` is true -- the
+        observed ones, for ``nmf_masked``.  An observed 0 is stored as a zero: it is a measurement, not a gap."""
+        X = np.asarray(X, dtype=np.float64)
+        mask = np.asarray(mask)
+        if X.ndim != 2 or mask.shape != X.shape or mask.dtype != np.bool_:
+            raise ValueError(f"SparseMatrix.from_observed: X {X.shape} must be 2-D and mask {mask.shape} a boolean array of its shape")
+        cols, rows = np.nonzero(mask.T)                  # column by column, rows ascending
+        indptr = np.concatenate([[0], np.cumsum(mask.sum(axis=0))])
+        return cls(X[rows, cols], rows, indptr, X.shape)
+
+    def masked_residual(self, W, H, *, per_column=False) -> MaskedResidual:
+        """The squared error of W H over the STORED entries of this matrix only, stored zeros included, computed on the device in
+        fp64: the held-out score of ``nmf_masked`` when this matrix holds the entries withheld from the fit.  W (height, k) and
+        H (k, ncols): both numpy arrays, or both float64 / float32 torch tensors in GPU memory (any strides).  The matrix must
+        store no entry twice."""
+        import torch
+        what = "masked_residual"
+        on_device, k = _residual_factors(W, H, self.height, self.ncols, what)
+        dev = torch.device("cuda", L.lib().smk_current_device())
+        if not on_device:
+            W = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64)).to(dev)
+            H = torch.from_numpy(np.ascontiguousarray(H, dtype=np.float64)).to(dev)
+        wp, wt, (wrs, wcs) = _tensor_view(W, f"{what}(W)", kinds="factor")
+        hp, ht, (hrs, hcs) = _tensor_view(H, f"{what}(H)", kinds="factor")
+        cr = torch.empty(self.ncols, dtype=torch.float64, device=W.device) if per_column else None
+        ca = torch.empty(self.ncols, dtype=torch.float64, device=W.device) if per_column else None
+        out = (C.c_double * 3)()
+        entry = "smk_matrix_masked_residual_device"
+        L.check(getattr(L.lib(), entry)(self._h, k, wp, wt, wrs, wcs, hp, ht, hrs, hcs, C.c_void_p(cr.data_ptr()) if per_column else None,
+                                        C.c_void_p(ca.data_ptr()) if per_column else None, _stream_of(W), out), entry)
+        if per_column and not on_device:
+            cr, ca = cr.cpu().numpy(), ca.cpu().numpy()
+        return MaskedResidual(out[0], out[1], int(out[2]), cr, ca)
 
     def product(self, X, *, transposed=False, reps=0):
         """The sparse Gemm by itself: X (k x height) * A, or with ``transposed`` X (k x width) * A'; returns the k x ncols
@@ -943,6 +1000,69 @@ def nmf_kl(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, ma
 def kl_last_profile():
     """(sweeps over the stored entries that updated a factor, sweeps that formed the divergence) of this thread's last ``nmf_kl``"""
     return _last_profile("smk_kl_last_profile")
+
+
+@dataclass
+class MaskedResult:
+    """What ``nmf_masked`` returns: the factors (numpy arrays, or torch tensors on the GPU when the start was tensors), the iterations
+    run, whether the stopping rule ended them, the violation of iteration 1 and of the last one, and the root of the summed squared
+    error over the stored entries."""
+    W: object
+    H: object
+    n_iter: int
+    converged: bool
+    violation_init: float
+    violation: float
+    error: float
+
+
+def nmf_masked(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True, inplace=False) -> MaskedResult:
+    """NMF fitted to the STORED entries of a resident ``SparseMatrix`` A (m, n) only, by cyclic coordinate descent: an entry that A
+    does not store is "not measured" -- a missing rating, an empty well, an entry held out on purpose (``holdout_split``) -- where
+    every other solver here reads it as 0.  Stored zeros are measurements (``SparseMatrix.from_observed``).  Minimises
+
+        1/2 sum over the stored (i, j, a) of (a - w_i . h_j)^2 + the penalty terms of ``nmf_cd``
+
+    with ``nmf_cd``'s arguments, orientation and stopping rule; when every entry is stored it is ``nmf_cd``'s iteration up to
+    rounding.  ``update_W=False``: W stays, only H is fitted (fold-in of new columns against fixed rows).  A must store no entry
+    twice.  ``SparseMatrix.masked_residual`` of the held-out entries scores the fit."""
+    if not isinstance(A, SparseMatrix):
+        raise ValueError(f"nmf_masked: A must be a resident SparseMatrix, got {type(A).__name__}")
+    return _penalised_fit("nmf_masked", "SparseMatrix", "smk_nmf_masked_device", L.MaskedStats,
+                          lambda st: (st.violation_init, st.violation, st.error), MaskedResult,
+                          A, W0, H0, alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio, tol=tol, max_iter=max_iter, update_W=update_W, inplace=inplace)
+
+
+def masked_last_profile():
+    """(sweeps over the stored entries that updated a factor, sweeps that formed the residual) of this thread's last ``nmf_masked``"""
+    return _last_profile("smk_masked_last_profile")
+
+
+def holdout_split(A, fraction, seed):
+    """Split the stored entries of A -- a scipy sparse matrix or a CSC triple (data, indices, indptr, shape) -- at random into two
+    CSC triples of the same shape: ``(train, test)``, ``test`` holding round(fraction * nnz) of them.  Host code, numpy only.  A
+    stored zero stays a stored entry of its part (the triples are built by index: scipy arithmetic would drop it).  The same
+    split for the same seed."""
+    if hasattr(A, "tocsc"):
+        A = A.tocsc()
+        data, indices, indptr, shape = A.data, A.indices, A.indptr, A.shape
+    else:
+        data, indices, indptr, shape = A
+    data, indices, indptr = np.asarray(data, dtype=np.float64), np.asarray(indices), np.asarray(indptr).astype(np.int64)
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError(f"holdout_split: fraction {fraction} must lie in [0, 1]")
+    nnz, ncols = data.shape[0], int(shape[1])
+    if indptr.shape[0] != ncols + 1 or indptr[0] != 0 or indptr[-1] != nnz or indices.shape[0] != nnz:
+        raise ValueError("holdout_split: not a CSC triple of that shape")
+    held = np.zeros(nnz, dtype=bool)
+    held[np.random.default_rng(seed).permutation(nnz)[:int(round(fraction * nnz))]] = True
+    col = np.repeat(np.arange(ncols), np.diff(indptr))
+
+    def part(keep):
+        ptr = np.concatenate([[0], np.cumsum(np.bincount(col[keep], minlength=ncols))]).astype(np.int64)
+        return data[keep].copy(), indices[keep].astype(np.uint32), ptr, (int(shape[0]), ncols)
+
+    return part(~held), part(held)
 
 
 def nmf_kl_dense(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True, inplace=False) -> KlResult:
