@@ -422,6 +422,25 @@ int smk_beta_dense_last_profile(int* matrix_passes, int* divergence_passes);
  * (over the stored transpose), 2 the KL step of kl_dense.hip on the same matrix and rank, 3 the residual pass.  beta != 1 */
 int smk_beta_dense_step_time(const smk_matrix* a, int which, int k, double beta, int reps, double* ms);
 
+/* ---- the fp32 form of the two losses above that people fit in fp32 everywhere else ----------------------------
+ * smk_nmf_beta_dense_device for beta = 1 (Kullback-Leibler) and beta = 0 (Itakura-Saito) with the per-entry work in fp32 on the
+ * fp32 matrix cores: the dot product d = w_i . h_j, the clamp at 2^-23, the quotients (a / d; a / d^2 and 1 / d) and their
+ * contraction with the factor slab.  Between steps the factors are fp32: the start is rounded once on the way in (from an fp64 or
+ * fp32 view) and the result is widened exactly on the way out.  Per factor entry the partial sums are added in a fixed order in
+ * fp64 and the update formula is applied in fp64 and rounded once.  stats->error_init, the stopping rule and stats->error come from
+ * the fp64 divergence of the current fp32 factors: stats->error is, to the bit, what smk_matrix_beta_divergence_dense_device returns
+ * for the factors that come back.  Arguments, orientation, penalties, fold-in, the 2^-52 flush and the refusals are
+ * smk_nmf_beta_dense_device's; in addition SMK_UNSUPPORTED for any beta other than 0 and 1 (the power's rounding is amplified by
+ * |beta - 2|; take the fp64 form).  The same bits on every run.  On an error W and H are untouched. */
+int smk_nmf_beta_dense_f32_device(const smk_matrix* a, int k, double beta, const smk_kl_options* o, void* W, int dtW, int64_t rsW,
+                                  int64_t csW, void* H, int dtH, int64_t rsH, int64_t csH, void* stream, smk_kl_stats* stats);
+/* diagnostics of the calling thread's last smk_nmf_beta_dense_f32_device call, as smk_kl_dense_last_profile */
+int smk_beta_dense_f32_last_profile(int* matrix_passes, int* divergence_passes);
+/* measurement (tools/beta_dense_f32_rate.py), as smk_kl_dense_step_time; beta 0 or 1.  which: 0 the fp32 H step with its finish
+ * (over A), 1 the fp32 W step (over the stored transpose), 2 the fp64 step of the same beta on the same matrix and rank -- the
+ * thing to compare with --, 3 the residual pass */
+int smk_beta_dense_f32_step_time(const smk_matrix* a, int which, int k, double beta, int reps, double* ms);
+
 /* ---- labels, memberships, top terms and fold-in, on the device (the device twins of smk_compute_assignments,
  * smk_compute_fuzzy_assignments and smk_top_terms below: the same comparisons in the same order, so the same integers and the
  * same membership bits; no k <= n and no height >= width requirement) -----------------------------------------------------

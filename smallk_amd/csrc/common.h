@@ -564,6 +564,19 @@ int launch_beta_dense_step(const void* A, int storage, i64 ld, i64 rows, i64 col
 int launch_beta_dense_divergence(const void* A, int storage, i64 ld, i64 rows, i64 cols, const double* R, const double* X, int k, double beta,
                                  double* scratch, double* out4, double* host_out, int num_cus, hipStream_t st);
 
+// beta_dense_f32.hip: the fp32 form of the KL (beta = 1) and Itakura-Saito (beta = 0) steps above, k <= 128.  R and X
+// are fp32 factors with pitch beta_dense_f32_pitch(k) = max(kp_of(k), 16) floats, rows >= k zero; X64 (pitch kp_of(k)) is kept as the
+// exact fp64 widening of X, which is what the fp64 divergence and row-sum launches read.  launch_beta_dense_f32_step: d, the clamp,
+// the quotients and both contractions in fp32 on the fp32 matrix cores; per factor entry the spans in span order and the update
+// (kl_update with base / unit at beta = 1, beta_update at beta = 0) in fp64, rounded once.  scratch: beta_dense_f32_scratch_bytes.
+// launch_beta_dense_f32_narrow: X64 (N columns) rounded once into X, and X64 replaced by the widening of the result.
+// Fixed summation orders throughout: the same bits on every run.
+int beta_dense_f32_pitch(int k);
+size_t beta_dense_f32_scratch_bytes(i64 rows, i64 cols, int k, double beta, int num_cus);
+int launch_beta_dense_f32_step(const void* A, int storage, i64 ld, i64 rows, i64 cols, const float* R, float* X, double* X64, int k, double beta,
+                               const double* base, int unit, double l1, double l2, int flush, float* scratch, int num_cus, hipStream_t st);
+int launch_beta_dense_f32_narrow(double* X64, float* X, int k, i64 N, hipStream_t st);
+
 // assign.hip: labels / memberships of the columns of H and the top terms of the columns of W, the factors fp64 or fp32 (DT_*) in
 // their k-contiguous layout: column c of H at H + c * ldc, row i of W at W + i * ld (elements).  The host functions' comparisons in
 // the host functions' order: the same integers, the same membership bits.  memb: k * n floats (document c at c * k) or null.

@@ -1065,14 +1065,40 @@ def holdout_split(A, fraction, seed):
     return part(~held), part(held)
 
 
-def nmf_kl_dense(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True, inplace=False) -> KlResult:
+def _check_precision(what, precision, beta):
+    """``precision`` of the dense beta-divergence solvers: "fp64" (the default) or "fp32", which serves beta = 0 and beta = 1.  Raised
+    here, before any library call."""
+    if precision not in ("fp64", "fp32"):
+        raise ValueError(f"{what}: precision must be 'fp64' or 'fp32', got {precision!r}")
+    if precision == "fp32" and beta not in (0.0, 1.0):
+        raise ValueError(f"{what}: precision='fp32' serves beta_loss 'itakura-saito' (0) and 'kullback-leibler' (1); beta = {beta} takes 'fp64'")
+    return precision == "fp32"
+
+
+def _fit_f32(what, beta, A, W0, H0, **kw):
+    """the fp32 form of both dense losses: one entry (``smk_nmf_beta_dense_f32_device``), beta between k and the options"""
+    return _penalised_fit(what, "DenseMatrix", "smk_nmf_beta_dense_f32_device", L.KlStats, lambda st: (st.error_init, st.error), KlResult,
+                          A, W0, H0, before_options=(C.c_double(beta),), **kw)
+
+
+def nmf_kl_dense(A, W0, H0, *, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True, inplace=False,
+                 precision="fp64") -> KlResult:
     """``nmf_kl`` on a resident ``DenseMatrix`` A (m, n) -- counts or intensities without many zeros: a spectrogram, an image, word
     counts over a small vocabulary.  The same objective, arguments, stopping rule and result as ``nmf_kl``; the sums run over every
     entry of the stored A (bf16 or fp32 storage, widened exactly), so on the same data the two agree up to summation order.  Each
     half-iteration is one streaming read of one stored copy (A for H, the stored transpose for W), hence a ``single_copy`` matrix
-    serves ``update_W=False`` only.  A must store no negative value.  (The estimator ``NMF`` takes sparse X for this loss.)"""
+    serves ``update_W=False`` only.  A must store no negative value.  (The estimator ``NMF`` takes sparse X for this loss.)
+
+    ``precision="fp32"`` does the per-entry work -- the dot product, the clamp, the quotient and its contraction --
+    in fp32 on the fp32 matrix cores and keeps the factors as fp32 between steps: the start is rounded to fp32 once, the result is
+    exactly representable in fp32 whatever the views' type.  ``error_init``, the stopping rule and ``error`` are still the fp64
+    divergence of those factors, so ``error`` equals ``A.kl_divergence(W, H).error`` of the result bit for bit.  Expect the factors
+    some 1e-6 of their largest entry from the fp64 form's after a few dozen iterations.  The default "fp64" is unchanged."""
+    kw = dict(alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio, tol=tol, max_iter=max_iter, update_W=update_W, inplace=inplace)
+    if _check_precision("nmf_kl_dense", precision, 1.0):
+        return _fit_f32("nmf_kl_dense", 1.0, A, W0, H0, **kw)
     return _penalised_fit("nmf_kl_dense", "DenseMatrix", "smk_nmf_kl_dense_device", L.KlStats, lambda st: (st.error_init, st.error), KlResult,
-                          A, W0, H0, alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio, tol=tol, max_iter=max_iter, update_W=update_W, inplace=inplace)
+                          A, W0, H0, **kw)
 
 
 def kl_dense_last_profile():
@@ -1100,26 +1126,41 @@ def _beta_of(what, beta_loss):
     return beta
 
 
-def nmf_beta_dense(A, W0, H0, *, beta_loss, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True, inplace=False) -> KlResult:
+def nmf_beta_dense(A, W0, H0, *, beta_loss, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True, inplace=False,
+                   precision="fp64") -> KlResult:
     """``nmf_kl_dense`` under another beta-divergence -- scikit-learn's ``solver="mu"`` with ``beta_loss`` = "itakura-saito" (beta = 0,
     the scale-invariant loss a power spectrogram is fitted under), "kullback-leibler" (beta = 1: ``nmf_kl_dense`` itself, the same
     bits) or any number >= 0 other than 2 -- on a resident ``DenseMatrix`` A (m, n).  Arguments, orientation, penalties, stopping rule
     and result are ``nmf_kl``'s; ``error`` is sqrt(2 D_beta(A || W H)).  Each half-iteration is one streaming read of one stored
     copy, hence a ``single_copy`` matrix serves ``update_W=False`` only.  A must store no negative value and, for beta <= 0, no zero
     (add a small value first).  beta = 0 costs divisions only; any other beta pays a double-precision power per entry and
-    half-iteration (DESIGN.md 21 has the measured cost)."""
+    half-iteration (DESIGN.md 21 has the measured cost).
+
+    ``precision="fp32"`` is ``nmf_kl_dense``'s: for "itakura-saito" and "kullback-leibler" the per-entry work (d, the clamp, a / d^2
+    and 1 / d, both contractions) runs in fp32 on the fp32 matrix cores and the factors are fp32 between steps, while ``error_init``,
+    the stopping rule and ``error`` stay the fp64 divergence of those factors (``error`` equals ``A.beta_divergence(W, H,
+    beta_loss).error`` of the result bit for bit).  Any other beta raises ``ValueError`` with it: the power's rounding is
+    amplified by |beta - 2|.  The default "fp64" is unchanged."""
     beta = _beta_of("nmf_beta_dense", beta_loss)
+    f32 = _check_precision("nmf_beta_dense", precision, beta)
     if isinstance(A, SparseMatrix):
         raise ValueError(f"nmf_beta_dense: A must be a resident DenseMatrix, got {type(A).__name__}")
+    kw = dict(alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio, tol=tol, max_iter=max_iter, update_W=update_W, inplace=inplace)
+    if f32:
+        return _fit_f32("nmf_beta_dense", beta, A, W0, H0, **kw)
     return _penalised_fit("nmf_beta_dense", "DenseMatrix", "smk_nmf_beta_dense_device", L.KlStats, lambda st: (st.error_init, st.error), KlResult,
-                          A, W0, H0, alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio, tol=tol, max_iter=max_iter, update_W=update_W, inplace=inplace,
-                          before_options=(C.c_double(beta),))
+                          A, W0, H0, before_options=(C.c_double(beta),), **kw)
 
 
 def beta_dense_last_profile():
     """(streaming passes over A or A' that updated a factor, passes that formed the divergence) of this thread's last ``nmf_beta_dense``
     (beta != 1)"""
     return _last_profile("smk_beta_dense_last_profile")
+
+
+def beta_dense_f32_last_profile():
+    """the same two counters of this thread's last ``nmf_kl_dense`` / ``nmf_beta_dense`` with ``precision="fp32"``"""
+    return _last_profile("smk_beta_dense_f32_last_profile")
 
 
 def cd_sweep(G, R, X, l1=0.0, l2=0.0):
