@@ -441,6 +441,37 @@ int smk_beta_dense_f32_last_profile(int* matrix_passes, int* divergence_passes);
  * thing to compare with --, 3 the residual pass */
 int smk_beta_dense_f32_step_time(const smk_matrix* a, int which, int k, double beta, int reps, double* ms);
 
+/* ---- the dense multiplicative update fitted to the MEASURED entries only ---------------------------------------
+ * An entry of a dense matrix whose stored value is NaN is "not measured" (a clipped bin, a dead pixel, a failed well, an entry held
+ * out on purpose); every other stored value is a measurement, 0 included.  Omega = the non-NaN entries.  smk_nmf_kl_dense_device's
+ * iteration for beta = 2 (Frobenius), 1 (Kullback-Leibler) and 0 (Itakura-Saito) with every sum over entries restricted to Omega:
+ *   H[t, j] *= (sum_{i in Omega_j} W[i, t] qn_ij / (sum_{i in Omega_j} W[i, t] qd_ij + l1 + l2 H[t, j]))^gamma,   d = w_i . h_j,
+ *   beta = 2: qn = a, qd = d;  beta = 1: qn = a / max(d, 2^-23), qd = 1;  beta = 0: r = 1 / max(d, 2^-23), qn = r r a, qd = r,
+ * gamma = 1/2 at beta = 0 and 1 otherwise, a denominator of 0 counted as 2^-23 (so a column without a measured entry goes to 0),
+ * the 2^-52 flush of smk_nmf_beta_dense_device (none at beta = 2), then the same for W over the stored transpose with the new H.
+ * D over Omega: 1/2 sum (a - d)^2;  sum_{a > 2^-23} a log(a / d) - sum a + sum d;  sum_{a > 2^-23} (a / d - log(a / d)) - |Omega|
+ * (d clamped in the quotients).  stats->error = sqrt(2 max(D, 0)); options, orientation, penalties, fold-in and the stopping rule
+ * are smk_nmf_kl_device's.  The mask is inside both stored copies: each half-iteration is still one streaming read of one copy,
+ * both sums on the fp64 matrix cores, no second matrix.  A matrix without a NaN gives smk_nmf_beta_dense_device's iteration at
+ * beta = 0 and smk_nmf_kl_dense_device's at beta = 1 up to rounding.  The same bits on every run.  Under bf16 storage an adopted
+ * tensor must carry the canonical quiet NaN (0x7FC00000): the rounding to bf16 turns a NaN with a full payload into -0.
+ * SMK_BAD_PARAM: as smk_nmf_kl_dense_device; a measured negative value; at beta = 0 a measured zero; a matrix without a measured
+ * entry.  SMK_UNSUPPORTED: a beta other than 0, 1, 2; a sparse matrix; k > 128; a column shard; a single-copy matrix when
+ * update_w != 0.  On an error W and H are untouched. */
+int smk_nmf_masked_dense_device(const smk_matrix* a, int k, double beta, const smk_kl_options* o, void* W, int dtW, int64_t rsW,
+                                int64_t csW, void* H, int dtH, int64_t rsH, int64_t csH, void* stream, smk_kl_stats* stats);
+/* out[0] = D over the measured entries of `a` (not clamped), out[1 .. 3] the sums it is formed from -- beta = 2: sum (a - d)^2,
+ * sum a^2, 0;  beta = 1: sum a log(a / d), sum a, sum d;  beta = 0: sum a / d, sum log(a / d), 0 --, out[4] the number of measured
+ * entries: the held-out score when `a` holds the entries withheld from the fit.  One read of A; a single copy is served. */
+int smk_matrix_masked_divergence_dense_device(const smk_matrix* a, int k, double beta, const void* W, int dtW, int64_t rsW,
+                                              int64_t csW, const void* H, int dtH, int64_t rsH, int64_t csH, void* stream, double* out);
+/* diagnostics of the calling thread's last smk_nmf_masked_dense_device call, as smk_kl_dense_last_profile */
+int smk_masked_dense_last_profile(int* matrix_passes, int* divergence_passes);
+/* measurement (tools/masked_dense_rate.py), as smk_kl_dense_step_time.  which: 0 the H step with its finish (over A), 1 the W step
+ * (over the stored transpose), 2 the beta = 0 step of beta_dense.hip over A at the same rank, whatever `beta` is: the kernel this
+ * one was derived from */
+int smk_masked_dense_step_time(const smk_matrix* a, int which, int k, double beta, int reps, double* ms);
+
 /* ---- labels, memberships, top terms and fold-in, on the device (the device twins of smk_compute_assignments,
  * smk_compute_fuzzy_assignments and smk_top_terms below: the same comparisons in the same order, so the same integers and the
  * same membership bits; no k <= n and no height >= width requirement) -----------------------------------------------------

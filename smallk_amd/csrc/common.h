@@ -577,6 +577,22 @@ int launch_beta_dense_f32_step(const void* A, int storage, i64 ld, i64 rows, i64
                                const double* base, int unit, double l1, double l2, int flush, float* scratch, int num_cus, hipStream_t st);
 int launch_beta_dense_f32_narrow(double* X64, float* X, int k, i64 N, hipStream_t st);
 
+// masked_dense.hip: the dense steps for beta = 2, 1, 0 with every sum restricted to the measured entries -- a stored NaN is "not
+// measured"  --, k <= 128, in beta_dense.hip's frame and with its arguments; `beta` is the integer itself.
+// launch_masked_dense_step: num_j += qn r_i and den_j += qd r_i over the measured entries of column j on the fp64 matrix cores (qn, qd:
+// a, d at beta = 2; a / max(d, EPS), 1 at beta = 1; beta_dense.hip's at beta = 0), then beta_update in place (gamma = 1/2 at beta = 0).
+// launch_masked_dense_divergence: out5 (and host_out when not null, pinned host memory) = D over the measured entries, the three sums
+// it is formed from -- beta = 2: sum (a - d)^2, sum a^2, 0; beta = 1: sum a log(a / d), sum a, sum d; beta = 0: sum a / d,
+// sum log(a / d), 0 -- and the number of measured entries.  launch_masked_dense_look: *flag (zeroed by the caller) |= 1 for a measured
+// negative value, 2 for a measured zero, 4 for any measured entry.  scratch: masked_dense_scratch_elems doubles.  Fixed summation
+// orders throughout: the same bits on every run.
+size_t masked_dense_scratch_elems(i64 rows, i64 cols, int k, int num_cus);
+int launch_masked_dense_step(const void* A, int storage, i64 ld, i64 rows, i64 cols, const double* R, double* X, int k, int beta, double l1, double l2,
+                             int flush, double* scratch, int num_cus, hipStream_t st);
+int launch_masked_dense_divergence(const void* A, int storage, i64 ld, i64 rows, i64 cols, const double* R, const double* X, int k, int beta,
+                                   double* scratch, double* out5, double* host_out, int num_cus, hipStream_t st);
+int launch_masked_dense_look(const void* A, int storage, i64 ld, i64 rows, i64 cols, int* flag, hipStream_t st);
+
 // assign.hip: labels / memberships of the columns of H and the top terms of the columns of W, the factors fp64 or fp32 (DT_*) in
 // their k-contiguous layout: column c of H at H + c * ldc, row i of W at W + i * ld (elements).  The host functions' comparisons in
 // the host functions' order: the same integers, the same membership bits.  memb: k * n floats (document c at c * k) or null.

@@ -112,6 +112,27 @@ class BetaDivergence:
 
 
 @dataclass
+class MaskedDivergence:
+    """D_beta(A || W H) over the measured (non-NaN) entries of a ``DenseMatrix`` (``DenseMatrix.masked_divergence``), their number
+    and the sums D is formed from.  beta = 2: (sum (a - d)^2, sum a^2, 0) with D = sums[0] / 2; beta = 1: (sum a log(a / d), sum a,
+    sum d) with D = sums[0] - sums[1] + sums[2]; beta = 0: (sum a / d, sum log(a / d), 0) with D = sums[0] - count - sums[1]."""
+    beta: float
+    divergence: float
+    count: int
+    sums: tuple
+
+    @property
+    def error(self) -> float:
+        """sqrt(2 max(D, 0)): what ``nmf_masked_dense`` reports and stops on"""
+        return math.sqrt(2.0 * max(self.divergence, 0.0))
+
+    @property
+    def mean(self) -> float:
+        """D / count: the held-out score to compare between ranks; nan for a matrix without a measured entry"""
+        return self.divergence / self.count if self.count > 0 else math.nan
+
+
+@dataclass
 class MaskedResidual:
     """What ``SparseMatrix.masked_residual`` returns: the sum over the stored entries of (a - w_i . h_j)^2, of a^2, and their number;
     with ``per_column`` the first two per column (numpy arrays, or torch tensors on the GPU when the factors were tensors)."""
@@ -408,6 +429,40 @@ class DenseMatrix:
         entry = "smk_matrix_beta_divergence_dense_device"
         L.check(getattr(L.lib(), entry)(self._h, k, C.c_double(beta), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), out), entry)
         return BetaDivergence(beta, out[0], (out[1], out[2], out[3]))
+
+    @classmethod
+    def from_observed(cls, X, mask, *, storage="f32"):
+        """The resident matrix of the dense array ``X`` with "not measured" written where the boolean array ``mask`` is false, for
+        ``nmf_masked_dense``: those entries are stored as the canonical quiet NaN (0x7FC00000 in fp32, 0x7FC0 in bf16), every other
+        entry as a measurement, 0 included.  A tensor adopted under bf16 storage must carry that same NaN: the rounding to bf16
+        turns a NaN with a full payload into -0."""
+        X = np.array(X, dtype=np.float64)
+        mask = np.asarray(mask)
+        if X.ndim != 2 or mask.shape != X.shape or mask.dtype != np.bool_:
+            raise ValueError(f"DenseMatrix.from_observed: X {X.shape} must be 2-D and mask {mask.shape} a boolean array of its shape")
+        X[~mask] = np.float64(np.uint32(0x7FC00000).view(np.float32))
+        return cls.from_host(X, storage=storage)
+
+    def masked_divergence(self, W, H, beta_loss) -> "MaskedDivergence":
+        """The divergence of ``nmf_masked_dense`` (``beta_loss`` as there) over the MEASURED entries of the stored A only -- those
+        whose stored value is not NaN --, computed on the device in fp64 in one streaming read of A, with their number: the held-out
+        score when this matrix holds the entries withheld from the fit (``holdout_split_dense``); compare ``.mean`` between ranks.
+        W and H as in ``kl_divergence``.  A single-copy matrix is served."""
+        beta = _masked_beta_of("masked_divergence", beta_loss)
+        if isinstance(self, SparseMatrix):
+            raise ValueError("masked_divergence: takes a resident DenseMatrix (SparseMatrix has masked_residual)")
+        on_device, k = _residual_factors(W, H, self.height, self.ncols, "masked_divergence")
+        if not on_device:
+            import torch
+            dev = torch.device("cuda", L.lib().smk_current_device())
+            W = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64)).to(dev)
+            H = torch.from_numpy(np.ascontiguousarray(H, dtype=np.float64)).to(dev)
+        wp, wt, (wrs, wcs) = _tensor_view(W, "masked_divergence(W)", kinds="factor")
+        hp, ht, (hrs, hcs) = _tensor_view(H, "masked_divergence(H)", kinds="factor")
+        out = (C.c_double * 5)()
+        entry = "smk_matrix_masked_divergence_dense_device"
+        L.check(getattr(L.lib(), entry)(self._h, k, C.c_double(beta), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), out), entry)
+        return MaskedDivergence(beta, out[0], int(out[4]), (out[1], out[2], out[3]))
 
     def _kl_divergence(self, entry, W, H) -> KlDivergence:
         on_device, k = _residual_factors(W, H, self.height, self.ncols, "kl_divergence")
@@ -1063,6 +1118,62 @@ def holdout_split(A, fraction, seed):
         return data[keep].copy(), indices[keep].astype(np.uint32), ptr, (int(shape[0]), ncols)
 
     return part(~held), part(held)
+
+
+def holdout_split_dense(X, fraction, seed):
+    """Split the measured (non-NaN) entries of the dense array X at random into two float64 arrays of its shape: ``(train, test)``,
+    ``test`` holding round(fraction * measured) of them and NaN elsewhere, ``train`` the rest; an entry that X does not measure is
+    NaN in both.  Host code, numpy only.  The same split for the same seed (``holdout_split``'s draw, over the measured entries in
+    row-major order)."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError(f"holdout_split_dense: X {X.shape} must be 2-D")
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError(f"holdout_split_dense: fraction {fraction} must lie in [0, 1]")
+    measured = np.flatnonzero(~np.isnan(X))
+    nnz = measured.shape[0]
+    held = np.zeros(X.size, dtype=bool)
+    held[measured[np.random.default_rng(seed).permutation(nnz)[:int(round(fraction * nnz))]]] = True
+    held = held.reshape(X.shape)
+    return np.where(held, np.nan, X), np.where(held, X, np.nan)
+
+
+def _masked_beta_of(what, beta_loss):
+    """``beta_loss`` of the masked dense solver as a number: "frobenius" (2), "kullback-leibler" (1), "itakura-saito" (0) or one of
+    those three numbers.  Raised here, before any library call."""
+    names = {"frobenius": 2.0, "kullback-leibler": 1.0, "itakura-saito": 0.0}
+    if isinstance(beta_loss, str) and beta_loss in names:
+        return names[beta_loss]
+    if isinstance(beta_loss, (int, float, np.integer, np.floating)) and not isinstance(beta_loss, bool) and float(beta_loss) in (0.0, 1.0, 2.0):
+        return float(beta_loss)
+    raise ValueError(f"{what}: beta_loss must be one of {sorted(names)} or 2, 1, 0, got {beta_loss!r}")
+
+
+def nmf_masked_dense(A, W0, H0, *, beta_loss="frobenius", alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True,
+                     inplace=False) -> KlResult:
+    """NMF fitted to the MEASURED entries of a resident ``DenseMatrix`` A (m, n) only, by multiplicative updates under
+    ``beta_loss`` = "frobenius" (2), "kullback-leibler" (1) or "itakura-saito" (0).  An entry whose stored value is NaN is "not
+    measured" -- a clipped time-frequency bin, a dead pixel, a failed well, an entry held out on purpose (``holdout_split_dense``) --
+    and every other stored value is a measurement, 0 included (``DenseMatrix.from_observed``).  The iteration is
+    ``nmf_kl_dense`` / ``nmf_beta_dense``'s with every sum over entries restricted to the measured ones, numerators and
+    denominators alike; arguments, orientation, penalties, stopping rule and result are ``nmf_kl``'s, ``error`` is
+    sqrt(2 D) with D over the measured entries (``A.masked_divergence``).  A row or column without a measured entry gets a zero
+    factor row.  On a matrix without NaN it is ``nmf_beta_dense(..., "itakura-saito")`` / ``nmf_kl_dense`` up to rounding.  Each
+    half-iteration is one streaming read of one stored copy -- the mask costs no byte --, hence a ``single_copy`` matrix serves
+    ``update_W=False`` only.  The measured values must not be negative and, for "itakura-saito", not zero.  Under bf16 storage a
+    tensor adopted with ``from_device`` must carry canonical NaNs (``float("nan")``; see ``from_observed``)."""
+    beta = _masked_beta_of("nmf_masked_dense", beta_loss)
+    if isinstance(A, SparseMatrix):
+        raise ValueError("nmf_masked_dense: A must be a resident DenseMatrix with NaN where nothing was measured (nmf_masked takes a SparseMatrix)")
+    return _penalised_fit("nmf_masked_dense", "DenseMatrix", "smk_nmf_masked_dense_device", L.KlStats, lambda st: (st.error_init, st.error), KlResult,
+                          A, W0, H0, before_options=(C.c_double(beta),), alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio, tol=tol,
+                          max_iter=max_iter, update_W=update_W, inplace=inplace)
+
+
+def masked_dense_last_profile():
+    """(streaming passes over A or A' that updated a factor, passes that formed the divergence) of this thread's last
+    ``nmf_masked_dense``"""
+    return _last_profile("smk_masked_dense_last_profile")
 
 
 def _check_precision(what, precision, beta):
