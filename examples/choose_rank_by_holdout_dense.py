@@ -50,7 +50,7 @@ def main():
         print("  k   mean held-out divergence   mean training divergence")
         for k in KS:
             W0, H0 = start(k, np.nanmean(train))
-            fit = smallk_amd.nmf_masked_dense(A_train, W0, H0, beta_loss="itakura-saito", tol=1e-5, max_iter=500)
+            fit = smallk_amd.nmf_masked_dense(A_train, W0, H0, beta_loss="itakura-saito", tol=1e-5, max_iter=500, precision="fp32")
             held = A_test.masked_divergence(fit.W, fit.H, "itakura-saito")
             seen = A_train.masked_divergence(fit.W, fit.H, "itakura-saito")
             scores[k] = held.mean

@@ -472,6 +472,25 @@ int smk_masked_dense_last_profile(int* matrix_passes, int* divergence_passes);
  * one was derived from */
 int smk_masked_dense_step_time(const smk_matrix* a, int which, int k, double beta, int reps, double* ms);
 
+/* ---- the fp32 form of the masked solver above -------------------------------------------------------------------
+ * smk_nmf_masked_dense_device for beta = 2, 1 and 0 with the per-entry work in fp32 on the fp32 matrix cores: d = w_i . h_j, the
+ * clamp at 2^-23, the quotients and BOTH contractions of every beta (at beta = 1 the denominator is the contraction of the factor
+ * slab with the 0 / 1 mask).  "Measured" is the same test on the bits; a NaN is selected away before any arithmetic.  Between
+ * steps the factors are fp32: the start is rounded once on the way in (from an fp64 or fp32 view) and the result is widened
+ * exactly on the way out.  Per factor entry the partial sums are added in a fixed order in fp64 and the update formula (the 0 ->
+ * 2^-23 denominator and the flushes included) is applied in fp64 and rounded once.  stats->error_init, the stopping rule and
+ * stats->error come from the fp64 masked divergence of the current fp32 factors: stats->error is, to the bit, what
+ * smk_matrix_masked_divergence_dense_device returns for the factors that come back.  Arguments, orientation, penalties, fold-in and
+ * the refusals are smk_nmf_masked_dense_device's.  The same bits on every run.  On an error W and H are untouched. */
+int smk_nmf_masked_dense_f32_device(const smk_matrix* a, int k, double beta, const smk_kl_options* o, void* W, int dtW, int64_t rsW,
+                                    int64_t csW, void* H, int dtH, int64_t rsH, int64_t csH, void* stream, smk_kl_stats* stats);
+/* diagnostics of the calling thread's last smk_nmf_masked_dense_f32_device call, as smk_kl_dense_last_profile */
+int smk_masked_dense_f32_last_profile(int* matrix_passes, int* divergence_passes);
+/* measurement (tools/masked_dense_f32_rate.py), as smk_kl_dense_step_time; beta 0, 1 or 2.  which: 0 the fp32 H step with its
+ * finish (over A), 1 the fp32 W step (over the stored transpose), 2 the fp64 masked step of the same beta on the same matrix and
+ * rank -- the thing to compare with */
+int smk_masked_dense_f32_step_time(const smk_matrix* a, int which, int k, double beta, int reps, double* ms);
+
 /* ---- labels, memberships, top terms and fold-in, on the device (the device twins of smk_compute_assignments,
  * smk_compute_fuzzy_assignments and smk_top_terms below: the same comparisons in the same order, so the same integers and the
  * same membership bits; no k <= n and no height >= width requirement) -----------------------------------------------------

@@ -593,6 +593,16 @@ int launch_masked_dense_divergence(const void* A, int storage, i64 ld, i64 rows,
                                    double* scratch, double* out5, double* host_out, int num_cus, hipStream_t st);
 int launch_masked_dense_look(const void* A, int storage, i64 ld, i64 rows, i64 cols, int* flag, hipStream_t st);
 
+// masked_dense_f32.hip: the fp32 form of the masked steps above, k <= 128, with beta_dense_f32.hip's factors: R and X
+// fp32 with pitch beta_dense_f32_pitch(k), rows >= k zero, X64 (pitch kp_of(k)) kept as the exact fp64 widening of X (what
+// launch_masked_dense_divergence reads; launch_beta_dense_f32_narrow rounds the start).  launch_masked_dense_f32_step: d, the clamp,
+// the quotients and both contractions of every beta in fp32 on the fp32 matrix cores, a NaN selected away before any of it; per
+// factor entry the spans in span order and beta_update in fp64, rounded once.  scratch: masked_dense_f32_scratch_bytes.  Fixed
+// summation orders throughout: the same bits on every run.
+size_t masked_dense_f32_scratch_bytes(i64 rows, i64 cols, int k, int num_cus);
+int launch_masked_dense_f32_step(const void* A, int storage, i64 ld, i64 rows, i64 cols, const float* R, float* X, double* X64, int k, int beta,
+                                 double l1, double l2, int flush, float* scratch, int num_cus, hipStream_t st);
+
 // assign.hip: labels / memberships of the columns of H and the top terms of the columns of W, the factors fp64 or fp32 (DT_*) in
 // their k-contiguous layout: column c of H at H + c * ldc, row i of W at W + i * ld (elements).  The host functions' comparisons in
 // the host functions' order: the same integers, the same membership bits.  memb: k * n floats (document c at c * k) or null.

@@ -132,6 +132,11 @@ inline int kl_args(const std::string& w, const smk_matrix* a, int k, const void*
 // kl_dense.cpp: refuses a dense matrix that stores a negative value (SMK_BAD_PARAM); fills a->kl_negative and a->kl_zero once per contents
 int kl_dense_sign_check(const smk_matrix* a, const std::string& w);
 
+// masked_dense.cpp, for its fp32 form too (masked_dense_f32.cpp): beta itself as 0, 1 or 2 (SMK_UNSUPPORTED otherwise), and the
+// conditions on the matrix and its measured data -- one look at the stored values per call
+int masked_dense_beta(const std::string& w, double beta, int* out);
+int masked_dense_supported(const std::string& w, const smk_matrix* a, int k, int beta, bool needs_transpose);
+
 // ... and what they weigh: the l1 and l2 terms of H scale with m, those of W with n (scikit-learn's convention on X = A')
 struct Penalties {
     double l1h, l2h, l1w, l2w;

@@ -28,7 +28,7 @@ struct MaskedDenseRun {
 static thread_local int g_md_matrix_passes = 0, g_md_divergence_passes = 0;
 
 // beta itself: 0, 1 or 2 (SMK_UNSUPPORTED otherwise; a NaN compares unequal to all three)
-static int masked_dense_beta(const std::string& w, double beta, int* out)
+int masked_dense_beta(const std::string& w, double beta, int* out)
 {
     if (beta != 0.0 && beta != 1.0 && beta != 2.0) { set_error(w + ": beta must be 0, 1 or 2"); return SMK_UNSUPPORTED; }
     *out = (int)beta;
@@ -36,7 +36,7 @@ static int masked_dense_beta(const std::string& w, double beta, int* out)
 }
 
 // kl_dense.cpp's conditions on the matrix, then the measured data: some, none negative, and no zero at beta = 0
-static int masked_dense_supported(const std::string& w, const smk_matrix* a, int k, int beta, bool needs_transpose)
+int masked_dense_supported(const std::string& w, const smk_matrix* a, int k, int beta, bool needs_transpose)
 {
     if (a->sparse) { set_error(w + ": takes a dense matrix, NaN where nothing was measured (smk_nmf_masked_device takes a sparse one)"); return SMK_UNSUPPORTED; }
     if (k > 128) { set_error(w + ": k > 128 is not supported yet"); return SMK_UNSUPPORTED; }

@@ -1150,7 +1150,7 @@ def _masked_beta_of(what, beta_loss):
 
 
 def nmf_masked_dense(A, W0, H0, *, beta_loss="frobenius", alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True,
-                     inplace=False) -> KlResult:
+                     inplace=False, precision="fp64") -> KlResult:
     """NMF fitted to the MEASURED entries of a resident ``DenseMatrix`` A (m, n) only, by multiplicative updates under
     ``beta_loss`` = "frobenius" (2), "kullback-leibler" (1) or "itakura-saito" (0).  An entry whose stored value is NaN is "not
     measured" -- a clipped time-frequency bin, a dead pixel, a failed well, an entry held out on purpose (``holdout_split_dense``) --
@@ -1161,11 +1161,21 @@ def nmf_masked_dense(A, W0, H0, *, beta_loss="frobenius", alpha_W=0.0, alpha_H="
     factor row.  On a matrix without NaN it is ``nmf_beta_dense(..., "itakura-saito")`` / ``nmf_kl_dense`` up to rounding.  Each
     half-iteration is one streaming read of one stored copy -- the mask costs no byte --, hence a ``single_copy`` matrix serves
     ``update_W=False`` only.  The measured values must not be negative and, for "itakura-saito", not zero.  Under bf16 storage a
-    tensor adopted with ``from_device`` must carry canonical NaNs (``float("nan")``; see ``from_observed``)."""
+    tensor adopted with ``from_device`` must carry canonical NaNs (``float("nan")``; see ``from_observed``).
+
+    ``precision="fp32"`` serves all three losses: the per-entry work -- the dot product, the clamp, the quotients and
+    both contractions -- runs in fp32 on the fp32 matrix cores and the factors are fp32 between steps (the start is rounded to fp32
+    once, the result is exactly representable in fp32), while ``error_init``, the stopping rule and ``error`` stay the fp64
+    divergence of those factors: ``error`` equals ``A.masked_divergence(W, H, beta_loss).error`` of the result bit for bit.  Expect
+    the factors some 1e-6 of their largest entry from the fp64 form's after a few dozen iterations -- nothing a held-out score
+    sees -- at 0.47 to 0.66 of the time per iteration (DESIGN.md 25 has the measured table).  The default "fp64" is unchanged."""
     beta = _masked_beta_of("nmf_masked_dense", beta_loss)
+    if precision not in ("fp64", "fp32"):
+        raise ValueError(f"nmf_masked_dense: precision must be 'fp64' or 'fp32', got {precision!r}")
     if isinstance(A, SparseMatrix):
         raise ValueError("nmf_masked_dense: A must be a resident DenseMatrix with NaN where nothing was measured (nmf_masked takes a SparseMatrix)")
-    return _penalised_fit("nmf_masked_dense", "DenseMatrix", "smk_nmf_masked_dense_device", L.KlStats, lambda st: (st.error_init, st.error), KlResult,
+    entry = "smk_nmf_masked_dense_f32_device" if precision == "fp32" else "smk_nmf_masked_dense_device"
+    return _penalised_fit("nmf_masked_dense", "DenseMatrix", entry, L.KlStats, lambda st: (st.error_init, st.error), KlResult,
                           A, W0, H0, before_options=(C.c_double(beta),), alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio, tol=tol,
                           max_iter=max_iter, update_W=update_W, inplace=inplace)
 
@@ -1174,6 +1184,11 @@ def masked_dense_last_profile():
     """(streaming passes over A or A' that updated a factor, passes that formed the divergence) of this thread's last
     ``nmf_masked_dense``"""
     return _last_profile("smk_masked_dense_last_profile")
+
+
+def masked_dense_f32_last_profile():
+    """the same two counters of this thread's last ``nmf_masked_dense`` with ``precision="fp32"``"""
+    return _last_profile("smk_masked_dense_f32_last_profile")
 
 
 def _check_precision(what, precision, beta):
