@@ -491,6 +491,34 @@ int smk_masked_dense_f32_last_profile(int* matrix_passes, int* divergence_passes
  * rank -- the thing to compare with */
 int smk_masked_dense_f32_step_time(const smk_matrix* a, int which, int k, double beta, int reps, double* ms);
 
+/* ---- weighted masked beta-divergence NMF on dense matrices: a weight per entry -----------------------------------
+ * smk_nmf_masked_dense_f32_device with a second resident matrix `v` of a's height, width, storage type and stored copies that
+ * holds a weight w_ij >= 0 per entry.  Minimises sum over the measured (i, j) of w_ij d_beta(a_ij | (W H)_ij) plus the penalty terms:
+ * the masked update with w inside both sums.  A NaN in `a` is "not measured" whatever its weight; a stored 0 in `a` is a
+ * measurement; a weight 0 removes an entry exactly as a NaN does.  The arithmetic is the fp32 form's (above): the per-entry
+ * quantities are formed as there and then multiplied by the weight in fp32, the factors are fp32 between steps, every sum per
+ * factor entry and the update formula are fp64; stats->error_init, the stopping rule and stats->error come from the fp64 weighted
+ * divergence of the current factors: stats->error is, to the bit, what smk_matrix_weighted_divergence_dense_device returns for
+ * the factors that come back.  With every weight 1 the result is smk_nmf_masked_dense_f32_device's bit for bit; without penalties a
+ * weight matrix scaled by a power of two gives the same factors.  Arguments, orientation, penalties, fold-in and the refusals
+ * are smk_nmf_masked_dense_f32_device's.  SMK_BAD_PARAM besides: `v` differs from `a` in height, width, storage type, leading
+ * dimension or in having one or two stored copies; a weight is negative, NaN or infinite; no measured entry has a positive weight.
+ * The same bits on every run.  On an error W and H are untouched. */
+int smk_nmf_weighted_dense_device(const smk_matrix* a, const smk_matrix* v, int k, double beta, const smk_kl_options* o, void* W, int dtW,
+                                  int64_t rsW, int64_t csW, void* H, int dtH, int64_t rsH, int64_t csH, void* stream, smk_kl_stats* stats);
+/* out[0] = D_w = sum over the measured entries of w d_beta(a | d) (not clamped), out[1 .. 3] the sums of
+ * smk_matrix_masked_divergence_dense_device with w in every term, out[4] the number of measured entries, out[5] the sum of their
+ * weights (at beta = 0, D_w = out[1] - out[5] - out[2]).  fp64; one read of A and of V; a single copy is served. */
+int smk_matrix_weighted_divergence_dense_device(const smk_matrix* a, const smk_matrix* v, int k, double beta, const void* W, int dtW,
+                                                int64_t rsW, int64_t csW, const void* H, int dtH, int64_t rsH, int64_t csH, void* stream,
+                                                double* out);
+/* diagnostics of the calling thread's last smk_nmf_weighted_dense_device call, as smk_kl_dense_last_profile */
+int smk_weighted_dense_last_profile(int* matrix_passes, int* divergence_passes);
+/* measurement (tools/weighted_dense_rate.py), as smk_kl_dense_step_time; beta 0, 1 or 2.  which: 0 the weighted H step with its
+ * finish (over A and V), 1 the weighted W step (over the stored transposes), 2 the fp32 masked step of the same beta on the same
+ * matrix and rank */
+int smk_weighted_dense_step_time(const smk_matrix* a, const smk_matrix* v, int which, int k, double beta, int reps, double* ms);
+
 /* ---- labels, memberships, top terms and fold-in, on the device (the device twins of smk_compute_assignments,
  * smk_compute_fuzzy_assignments and smk_top_terms below: the same comparisons in the same order, so the same integers and the
  * same membership bits; no k <= n and no height >= width requirement) -----------------------------------------------------

@@ -603,6 +603,21 @@ size_t masked_dense_f32_scratch_bytes(i64 rows, i64 cols, int k, int num_cus);
 int launch_masked_dense_f32_step(const void* A, int storage, i64 ld, i64 rows, i64 cols, const float* R, float* X, double* X64, int k, int beta,
                                  double l1, double l2, int flush, float* scratch, int num_cus, hipStream_t st);
 
+// weighted_dense.hip: the fp32 masked step and the fp64 masked divergence above with a weight w >= 0 per entry from a second stored
+// matrix V of A's shape, leading dimension and storage; the arguments are theirs with V behind A.
+// launch_weighted_dense_step: qn and qd formed as launch_masked_dense_f32_step forms them, then each times w in fp32, an entry of
+// weight 0 selected to +0; with every weight 1 its bits.  launch_weighted_dense_divergence: out6 (and host_out when not null, pinned
+// host memory) = D_w, the three sums of launch_masked_dense_divergence with w in every term, the number of measured entries and the
+// sum of their weights.  launch_weighted_dense_look: *flag (zeroed by the caller) |= 1 for a weight that is negative, NaN or
+// infinite, 2 for a measured entry of A with a positive weight.  scratch: weighted_dense_scratch_bytes serves both.  Fixed summation
+// orders throughout: the same bits on every run.
+size_t weighted_dense_scratch_bytes(i64 rows, i64 cols, int k, int num_cus);
+int launch_weighted_dense_step(const void* A, const void* V, int storage, i64 ld, i64 rows, i64 cols, const float* R, float* X, double* X64, int k,
+                               int beta, double l1, double l2, int flush, float* scratch, int num_cus, hipStream_t st);
+int launch_weighted_dense_divergence(const void* A, const void* V, int storage, i64 ld, i64 rows, i64 cols, const double* R, const double* X, int k,
+                                     int beta, double* scratch, double* out6, double* host_out, int num_cus, hipStream_t st);
+int launch_weighted_dense_look(const void* A, const void* V, int storage, i64 ld, i64 rows, i64 cols, int* flag, hipStream_t st);
+
 // assign.hip: labels / memberships of the columns of H and the top terms of the columns of W, the factors fp64 or fp32 (DT_*) in
 // their k-contiguous layout: column c of H at H + c * ldc, row i of W at W + i * ld (elements).  The host functions' comparisons in
 // the host functions' order: the same integers, the same membership bits.  memb: k * n floats (document c at c * k) or null.

@@ -115,11 +115,14 @@ class BetaDivergence:
 class MaskedDivergence:
     """D_beta(A || W H) over the measured (non-NaN) entries of a ``DenseMatrix`` (``DenseMatrix.masked_divergence``), their number
     and the sums D is formed from.  beta = 2: (sum (a - d)^2, sum a^2, 0) with D = sums[0] / 2; beta = 1: (sum a log(a / d), sum a,
-    sum d) with D = sums[0] - sums[1] + sums[2]; beta = 0: (sum a / d, sum log(a / d), 0) with D = sums[0] - count - sums[1]."""
+    sum d) with D = sums[0] - sums[1] + sums[2]; beta = 0: (sum a / d, sum log(a / d), 0) with D = sums[0] - count - sums[1].
+    From ``DenseMatrix.weighted_divergence`` every term carries its entry's weight, ``weight`` is the sum of the weights of the
+    measured entries and takes the place of ``count`` in the beta = 0 formula and in ``mean``."""
     beta: float
     divergence: float
     count: int
     sums: tuple
+    weight: float = None
 
     @property
     def error(self) -> float:
@@ -128,8 +131,10 @@ class MaskedDivergence:
 
     @property
     def mean(self) -> float:
-        """D / count: the held-out score to compare between ranks; nan for a matrix without a measured entry"""
-        return self.divergence / self.count if self.count > 0 else math.nan
+        """D / count (weighted: D / the sum of the weights): the held-out score to compare between ranks; nan for a matrix without a
+        measured entry"""
+        over = self.count if self.weight is None else self.weight
+        return self.divergence / over if over > 0 else math.nan
 
 
 @dataclass
@@ -463,6 +468,27 @@ class DenseMatrix:
         entry = "smk_matrix_masked_divergence_dense_device"
         L.check(getattr(L.lib(), entry)(self._h, k, C.c_double(beta), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), out), entry)
         return MaskedDivergence(beta, out[0], int(out[4]), (out[1], out[2], out[3]))
+
+    def weighted_divergence(self, V, W, H, beta_loss) -> "MaskedDivergence":
+        """The divergence of ``nmf_weighted_dense`` (``beta_loss`` as there): the sum over the MEASURED entries of the stored A of
+        w d_beta(a | (W H)), the weights w >= 0 being the entries of the resident ``DenseMatrix`` V of this matrix's shape, storage and
+        stored copies.  Computed on the device in fp64 in one streaming read of A and V; ``.weight`` is the sum of the weights of the
+        measured entries and ``.mean`` = D / that sum.  W and H as in ``kl_divergence``.  A single-copy pair is served."""
+        beta = _masked_beta_of("weighted_divergence", beta_loss)
+        if isinstance(self, SparseMatrix) or isinstance(V, SparseMatrix) or not isinstance(V, DenseMatrix):
+            raise ValueError("weighted_divergence: takes a resident DenseMatrix and a resident DenseMatrix of weights")
+        on_device, k = _residual_factors(W, H, self.height, self.ncols, "weighted_divergence")
+        if not on_device:
+            import torch
+            dev = torch.device("cuda", L.lib().smk_current_device())
+            W = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64)).to(dev)
+            H = torch.from_numpy(np.ascontiguousarray(H, dtype=np.float64)).to(dev)
+        wp, wt, (wrs, wcs) = _tensor_view(W, "weighted_divergence(W)", kinds="factor")
+        hp, ht, (hrs, hcs) = _tensor_view(H, "weighted_divergence(H)", kinds="factor")
+        out = (C.c_double * 6)()
+        entry = "smk_matrix_weighted_divergence_dense_device"
+        L.check(getattr(L.lib(), entry)(self._h, V._h, k, C.c_double(beta), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), out), entry)
+        return MaskedDivergence(beta, out[0], int(out[4]), (out[1], out[2], out[3]), out[5])
 
     def _kl_divergence(self, entry, W, H) -> KlDivergence:
         on_device, k = _residual_factors(W, H, self.height, self.ncols, "kl_divergence")
@@ -956,10 +982,11 @@ def transform(A, W, *, H0=None):
 
 
 def _penalised_fit(what, kind, entry, stats_type, last_two, result_type, A, W0, H0, *, alpha_W, alpha_H, l1_ratio, tol, max_iter, update_W, inplace,
-                   before_options=()):
+                   before_options=(), after_matrix=()):
     """What ``nmf_cd`` and ``nmf_kl`` share: the checks made before the library is called, the start as tensors on the GPU, the options,
     the C entry ``entry`` with its statistics struct and the result as ``result_type(W, H, n_iter, converged, *last_two(stats))``.
-    ``before_options``: what the entry takes between k and the options (``nmf_beta_dense``: beta)."""
+    ``before_options``: what the entry takes between k and the options (``nmf_beta_dense``: beta); ``after_matrix``: between the matrix
+    and k (``nmf_weighted_dense``: the handle of the weights)."""
     if not isinstance(A, DenseMatrix):
         raise ValueError(f"{what}: A must be a resident {kind}, got {type(A).__name__}")
     on_device, k = _residual_factors(W0, H0, A.height, A.ncols, what)
@@ -978,7 +1005,7 @@ def _penalised_fit(what, kind, entry, stats_type, last_two, result_type, A, W0, 
     wp, wt, (wrs, wcs) = _tensor_view(W, f"{what}(W0)", kinds="factor")
     hp, ht, (hrs, hcs) = _tensor_view(H, f"{what}(H0)", kinds="factor")
     st = stats_type()
-    L.check(getattr(L.lib(), entry)(A._h, k, *before_options, C.byref(o), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), C.byref(st)), entry)
+    L.check(getattr(L.lib(), entry)(A._h, *after_matrix, k, *before_options, C.byref(o), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), C.byref(st)), entry)
     if not on_device:
         W, H = W.cpu().numpy(), H.cpu().numpy()
     return result_type(W, H, st.iterations, bool(st.converged), *last_two(st))
@@ -1189,6 +1216,36 @@ def masked_dense_last_profile():
 def masked_dense_f32_last_profile():
     """the same two counters of this thread's last ``nmf_masked_dense`` with ``precision="fp32"``"""
     return _last_profile("smk_masked_dense_f32_last_profile")
+
+
+def nmf_weighted_dense(A, V, W0, H0, *, beta_loss="frobenius", alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True,
+                       inplace=False) -> KlResult:
+    """``nmf_masked_dense`` with a weight per entry: minimises the sum over the MEASURED entries of A of w_ij d_beta(a_ij | (W H)_ij)
+    plus the penalty terms, the weights w_ij >= 0 being the entries of V, a second resident ``DenseMatrix`` of A's shape, storage
+    and stored copies (``single_copy`` alike) -- inverse variances of a spectrum, band weights of a time-frequency matrix,
+    confidences of counts, per-document weights.  The update is the masked one with w inside both sums.  A NaN in A is "not
+    measured" whatever its weight, a stored 0 in A is a measurement, and a weight 0 removes an entry exactly as a NaN does; a row or
+    column whose entries are all unmeasured or of weight 0 gets a zero factor row.  Everything else -- ``beta_loss``, arguments,
+    orientation, penalties, fold-in, stopping rule, refusals and result -- is ``nmf_masked_dense``'s; ``error`` is sqrt(2 D_w) and
+    equals ``A.weighted_divergence(V, W, H, beta_loss).error`` of the result bit for bit.  V must hold no negative value, NaN or
+    infinity, and some measured entry must have a positive weight.
+
+    There is no ``precision`` keyword: the arithmetic is that of ``nmf_masked_dense(..., precision="fp32")`` --
+    the per-entry quantities in fp32 on the fp32 matrix cores, each then multiplied by its weight in fp32, fp32 factors between
+    steps, fp64 sums per factor entry, fp64 divergence.  With every weight 1 the result is that call's bit for bit; without
+    penalties V and 4 V give the same factors."""
+    beta = _masked_beta_of("nmf_weighted_dense", beta_loss)
+    if isinstance(A, SparseMatrix) or isinstance(V, SparseMatrix) or not isinstance(V, DenseMatrix):
+        raise ValueError("nmf_weighted_dense: A and the weights V must be resident DenseMatrix objects (NaN in A where nothing was measured)")
+    return _penalised_fit("nmf_weighted_dense", "DenseMatrix", "smk_nmf_weighted_dense_device", L.KlStats, lambda st: (st.error_init, st.error), KlResult,
+                          A, W0, H0, after_matrix=(V._h,), before_options=(C.c_double(beta),), alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio,
+                          tol=tol, max_iter=max_iter, update_W=update_W, inplace=inplace)
+
+
+def weighted_dense_last_profile():
+    """(streaming passes over A and V or their transposes that updated a factor, passes that formed the divergence) of this thread's
+    last ``nmf_weighted_dense``"""
+    return _last_profile("smk_weighted_dense_last_profile")
 
 
 def _check_precision(what, precision, beta):
