@@ -422,6 +422,30 @@ int smk_beta_dense_last_profile(int* matrix_passes, int* divergence_passes);
  * (over the stored transpose), 2 the KL step of kl_dense.hip on the same matrix and rank, 3 the residual pass.  beta != 1 */
 int smk_beta_dense_step_time(const smk_matrix* a, int which, int k, double beta, int reps, double* ms);
 
+/* ---- convolutive NMF of a resident DENSE matrix (NMFD) --------------------------------------------------------------
+ * A component is a pattern of T consecutive columns: A ~ Lambda, Lambda[i, j] = sum_{t < T} sum_{r < k} W_t[i, r] H[r, j - t] (terms
+ * with j - t < 0 are absent), fitted under beta = 1 (Kullback-Leibler) or beta = 0 (Itakura-Saito) by the multiplicative update,
+ * H first, then every slice of W with the new H -- smk_nmf_kl_dense_device's / smk_nmf_beta_dense_device's iteration, which T = 1
+ * is.  W is T slices of m x k: slice t is the view (rsW, csW) at W + t ssW elements; H is k x ncols.  Options, penalties (W's fall on
+ * every entry of every slice), stopping rule, fold-in (update_w = 0: the patterns stay; a single copy serves it), flushes and
+ * statistics are those entries'; stats->error = sqrt(2 D_beta(A || Lambda)).  Each half-iteration is one streaming read of one stored
+ * copy; the shifted copies of H exist nowhere in memory.  The same bits on every run.
+ * SMK_BAD_PARAM: as smk_nmf_beta_dense_device, T < 1, T > ncols.  SMK_UNSUPPORTED: a beta other than 0 and 1, T * roundup(k, 4) > 128,
+ * a sparse matrix, a column shard, a single-copy matrix when update_w != 0.  On an error W and H are untouched. */
+int smk_nmf_conv_dense_device(const smk_matrix* a, int k, int T, double beta, const smk_kl_options* o, void* W, int dtW, int64_t ssW,
+                              int64_t rsW, int64_t csW, void* H, int dtH, int64_t rsH, int64_t csH, void* stream, smk_kl_stats* stats);
+/* out[0] = D_beta(A || Lambda) (not clamped) over the entries with a > 2^-23, then the sums it is formed from.  beta = 0: out[1] =
+ * sum a / d, out[2] = sum log(a / d), out[3] = m n, D = out[1] - out[3] - out[2].  beta = 1: out[1] = sum a log(a / d), out[2] =
+ * sum Lambda over every entry, out[3] = 0, D = out[1] + (out[2] - sum a).  One read of A; a single copy is served. */
+int smk_matrix_conv_divergence_dense_device(const smk_matrix* a, int k, int T, double beta, const void* W, int dtW, int64_t ssW,
+                                            int64_t rsW, int64_t csW, const void* H, int dtH, int64_t rsH, int64_t csH, void* stream,
+                                            double* out);
+/* diagnostics of the calling thread's last smk_nmf_conv_dense_device call, as smk_kl_dense_last_profile */
+int smk_conv_dense_last_profile(int* matrix_passes, int* divergence_passes);
+/* measurement (tools/conv_dense_rate.py), as smk_kl_dense_step_time.  which: 0 the H step with its shift-add finish (over A), 1 the
+ * W step with its finish (over the stored transpose).  k and T * k are 8, 16, 32, 64 or 128 */
+int smk_conv_dense_step_time(const smk_matrix* a, int which, int k, int T, double beta, int reps, double* ms);
+
 /* ---- the fp32 form of the two losses above that people fit in fp32 everywhere else ----------------------------
  * smk_nmf_beta_dense_device for beta = 1 (Kullback-Leibler) and beta = 0 (Itakura-Saito) with the per-entry work in fp32 on the
  * fp32 matrix cores: the dot product d = w_i . h_j, the clamp at 2^-23, the quotients (a / d; a / d^2 and 1 / d) and their

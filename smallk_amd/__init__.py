@@ -13,7 +13,7 @@ from .solver import (DenseMatrix, SparseMatrix, NmfSolver, NmfResult, nmf, nmf_s
                      nmf_beta_dense, beta_dense_last_profile, beta_dense_f32_last_profile, BetaDivergence,
                      nmf_masked, masked_last_profile, MaskedResult, MaskedResidual, holdout_split,
                      nmf_masked_dense, masked_dense_last_profile, masked_dense_f32_last_profile, MaskedDivergence, holdout_split_dense,
-                     nmf_weighted_dense, weighted_dense_last_profile)
+                     nmf_weighted_dense, weighted_dense_last_profile, nmf_conv_dense, conv_dense_last_profile)
 from .estimator import NMF
 from .api import SmallkAPI
 from . import hierclust
@@ -21,7 +21,7 @@ from . import flatclust
 from .hierclust import hier_nmf2, TreeResults, TreeRouter
 
 __all__ = ["DenseMatrix", "SparseMatrix", "nmf_sparse", "load_matrix_market", "NmfSolver", "NmfResult", "nmf", "nmf_device", "initialize", "finalize", "is_initialized",
-           "make_options", "uniform_host", "nnls_blockpivot", "nmf_sharded", "Comm", "set_stream", "thread_context_begin", "thread_context_end", "trim_device_cache", "SmallkAPI", "hierclust", "flatclust", "hier_nmf2", "TreeResults", "TreeRouter", "Residual", "relative_error", "labels_device", "top_terms_device", "transform", "NNDSVD_VARIANTS", "nmf_cd", "cd_sweep", "CdResult", "nmf_kl", "nmf_kl_dense", "kl_dense_last_profile", "KlResult", "KlDivergence", "nmf_beta_dense", "beta_dense_last_profile", "beta_dense_f32_last_profile", "BetaDivergence", "nmf_masked", "masked_last_profile", "MaskedResult", "MaskedResidual", "holdout_split", "nmf_masked_dense", "masked_dense_last_profile", "masked_dense_f32_last_profile", "MaskedDivergence", "holdout_split_dense", "nmf_weighted_dense", "weighted_dense_last_profile", "NMF", "Vocabulary", "_lib"]
+           "make_options", "uniform_host", "nnls_blockpivot", "nmf_sharded", "Comm", "set_stream", "thread_context_begin", "thread_context_end", "trim_device_cache", "SmallkAPI", "hierclust", "flatclust", "hier_nmf2", "TreeResults", "TreeRouter", "Residual", "relative_error", "labels_device", "top_terms_device", "transform", "NNDSVD_VARIANTS", "nmf_cd", "cd_sweep", "CdResult", "nmf_kl", "nmf_kl_dense", "kl_dense_last_profile", "KlResult", "KlDivergence", "nmf_beta_dense", "beta_dense_last_profile", "beta_dense_f32_last_profile", "BetaDivergence", "nmf_masked", "masked_last_profile", "MaskedResult", "MaskedResidual", "holdout_split", "nmf_masked_dense", "masked_dense_last_profile", "masked_dense_f32_last_profile", "MaskedDivergence", "holdout_split_dense", "nmf_weighted_dense", "weighted_dense_last_profile", "nmf_conv_dense", "conv_dense_last_profile", "NMF", "Vocabulary", "_lib"]
 
 
 def __getattr__(name):

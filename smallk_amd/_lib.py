@@ -207,6 +207,10 @@ SYMBOLS = {
     "smk_matrix_weighted_divergence_dense_device": (C.c_int, [_vp, _vp, C.c_int, C.c_double, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _dp]),
     "smk_weighted_dense_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "smk_weighted_dense_step_time": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_int, _dp]),
+    "smk_nmf_conv_dense_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.POINTER(KlOptions), _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, C.POINTER(KlStats)]),
+    "smk_matrix_conv_divergence_dense_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, _dp]),
+    "smk_conv_dense_last_profile": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "smk_conv_dense_step_time": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _dp]),
     "smk_labels_device": (C.c_int, [_vp, C.c_int, _i64, _i64, C.c_int, _i64, _vp, _vp, _vp]),
     "smk_top_terms_device": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, _vp, _vp]),
     "smk_solver_labels": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),

@@ -435,6 +435,19 @@ class DenseMatrix:
         L.check(getattr(L.lib(), entry)(self._h, k, C.c_double(beta), wp, wt, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), out), entry)
         return BetaDivergence(beta, out[0], (out[1], out[2], out[3]))
 
+    def conv_divergence(self, W, H, beta_loss) -> "BetaDivergence":
+        """The divergence D_beta(A || model) of ``nmf_conv_dense`` (W (T, height, k), H (k, ncols) and ``beta_loss`` as there) over the
+        entries of the stored A with a > 2^-23, computed on the device in fp64 in one streaming read of A, with the sums it is formed
+        from as ``beta_divergence`` gives them.  A single-copy matrix is served."""
+        beta = _conv_beta_of("conv_divergence", beta_loss)
+        T, k = _conv_factors("conv_divergence", self, W, H)
+        wp, wt, (wss, wrs, wcs) = _tensor_view(W, "conv_divergence(W)", ndim=3, kinds="factor")
+        hp, ht, (hrs, hcs) = _tensor_view(H, "conv_divergence(H)", kinds="factor")
+        out = (C.c_double * 4)()
+        entry = "smk_matrix_conv_divergence_dense_device"
+        L.check(getattr(L.lib(), entry)(self._h, k, T, C.c_double(beta), wp, wt, wss, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), out), entry)
+        return BetaDivergence(beta, out[0], (out[1], out[2], out[3]))
+
     @classmethod
     def from_observed(cls, X, mask, *, storage="f32"):
         """The resident matrix of the dense array ``X`` with "not measured" written where the boolean array ``mask`` is false, for
@@ -1344,6 +1357,62 @@ def beta_dense_last_profile():
 def beta_dense_f32_last_profile():
     """the same two counters of this thread's last ``nmf_kl_dense`` / ``nmf_beta_dense`` with ``precision="fp32"``"""
     return _last_profile("smk_beta_dense_f32_last_profile")
+
+
+def _conv_beta_of(what, beta_loss):
+    """``beta_loss`` of the convolutive model as 0.0 or 1.0: scikit-learn's names or the numbers themselves.  Raised here, before any
+    library call."""
+    names = {"itakura-saito": 0.0, "kullback-leibler": 1.0}
+    if isinstance(beta_loss, str) and beta_loss in names:
+        return names[beta_loss]
+    if not isinstance(beta_loss, (bool, str)) and isinstance(beta_loss, (int, float, np.integer, np.floating)) and float(beta_loss) in (0.0, 1.0):
+        return float(beta_loss)
+    raise ValueError(f"{what}: beta_loss must be one of {sorted(names)}, 0 or 1, got {beta_loss!r}")
+
+
+def _conv_factors(what, A, W, H):
+    """The checks of the convolutive entries made before the library is called: a resident DenseMatrix, W (T, height, k) and H
+    (k, ncols) float64 / float32 torch tensors in GPU memory.  Returns (T, k)."""
+    if not isinstance(A, DenseMatrix) or isinstance(A, SparseMatrix):
+        raise ValueError(f"{what}: A must be a resident DenseMatrix, got {type(A).__name__}")
+    for x, name in ((W, "W"), (H, "H")):
+        if not _is_tensor(x) or str(x.dtype) not in ("torch.float64", "torch.float32"):
+            raise ValueError(f"{what}: {name} must be a float64 / float32 torch tensor in GPU memory")
+    ws, hs = tuple(W.shape), tuple(H.shape)
+    if len(ws) != 3 or len(hs) != 2 or min(ws) < 1 or ws[1] != A.height or hs != (ws[2], A.ncols):
+        raise ValueError(f"{what}: W {ws} / H {hs} do not match (T, {A.height}, k) / (k, {A.ncols})")
+    return int(ws[0]), int(ws[2])
+
+
+def nmf_conv_dense(A, W0, H0, *, beta_loss, alpha_W=0.0, alpha_H="same", l1_ratio=0.0, tol=1e-4, max_iter=200, update_W=True, inplace=False) -> KlResult:
+    """Convolutive NMF (NMFD) on a resident ``DenseMatrix`` A (m, n): a component is a pattern of T consecutive columns,
+
+        A[i, j] ~ sum_{t < T} sum_{r < k} W[t, i, r] H[r, j - t]            (terms with j - t < 0 are absent),
+
+    fitted under ``beta_loss`` = "kullback-leibler" (1) or "itakura-saito" (0) by the multiplicative update -- ``nmf_kl_dense``'s /
+    ``nmf_beta_dense``'s iteration, which T = 1 is: H first, then every slice of W with the new H.  W0 (T, m, k) and H0 (k, n) are
+    float64 / float32 torch tensors in GPU memory (any strides); T is read from W0 and T * roundup(k, 4) <= 128, T <= n.  Penalties
+    (``alpha_W`` falls on every entry of every slice), stopping rule and the ``KlResult`` are ``nmf_kl``'s, with ``W`` of shape
+    (T, m, k) and ``error`` = sqrt(2 D_beta(A || model)).  ``update_W=False`` keeps the patterns and fits the activations H only
+    (transcription against a fixed dictionary); a ``single_copy`` matrix serves that alone.  A must store no negative value and, for
+    "itakura-saito", no zero.  The start is not modified unless ``inplace``."""
+    beta = _conv_beta_of("nmf_conv_dense", beta_loss)
+    T, k = _conv_factors("nmf_conv_dense", A, W0, H0)
+    if alpha_H == "same":
+        alpha_H = alpha_W
+    o = L.PenaltyOptions(float(alpha_W), float(alpha_H), float(l1_ratio), float(tol), int(max_iter), int(bool(update_W)))
+    W, H = (W0, H0) if inplace else (W0.clone(), H0.clone())
+    wp, wt, (wss, wrs, wcs) = _tensor_view(W, "nmf_conv_dense(W0)", ndim=3, kinds="factor")
+    hp, ht, (hrs, hcs) = _tensor_view(H, "nmf_conv_dense(H0)", kinds="factor")
+    st = L.KlStats()
+    entry = "smk_nmf_conv_dense_device"
+    L.check(getattr(L.lib(), entry)(A._h, k, T, C.c_double(beta), C.byref(o), wp, wt, wss, wrs, wcs, hp, ht, hrs, hcs, _stream_of(W), C.byref(st)), entry)
+    return KlResult(W, H, st.iterations, bool(st.converged), st.error_init, st.error)
+
+
+def conv_dense_last_profile():
+    """(streaming passes over A or A' that updated a factor, passes that formed the divergence) of this thread's last ``nmf_conv_dense``"""
+    return _last_profile("smk_conv_dense_last_profile")
 
 
 def cd_sweep(G, R, X, l1=0.0, l2=0.0):
